@@ -8,6 +8,13 @@ batch=1, 300 proposals, no dense-align  (BASELINE.json configs[1]).
     python bench.py --config 3      # BASELINE configs[3]: the 3769-id KITTI val list replayed from PNG files, sharded i mod N, gathered
     python bench.py --config 4      # BASELINE configs[4]: ResNet-50 trunk, 2x resolution (network input 1200x3974), batch = 4
 (same JSON contract; `config.workload` names the BASELINE entry; the default, --config 1, is the headline.)
+    python bench.py ... --full      # also every figure beside the headline (see below); off by default
+    python bench.py ... --dump-outputs DIR   # after the timed steps: what the last step computed, as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`); nothing else runs.
+--full adds what the line carried beside the headline before: the `sustained` soak, `one_pair_at_a_time`, the lazy-keypoint
+figure, `roofline` (per-layer tables, PMC traffic of child runs, in-mix tables), the exact-fp32 engine leg, the full-3-D-flow leg,
+the `parity` block and the CPU baseline (each still switched off by its own --no-* option).
 
 One step = one pass of the hot path over one synthetic stereo pair per GPU (batch = 1 per forward; by default four
 forwards are in flight per GPU, each on a HIP stream with a hardware queue of its own, `--streams 1` = strictly sequential, also reported):
@@ -71,9 +78,9 @@ def parse():
                     help='(multi-GPU) steps whose detection records share one RCCL all_gather')
     ap.add_argument('--no-3d-leg', action='store_true',
                     help='skip the short full-3-D-flow measurement (configs[2] flow: + borders, 4-DoF solve, dense alignment, '
-                         '3-DoF rectification) that the default line carries as `config.full_3d_flow`')
+                         '3-DoF rectification) that the --full line carries as `config.full_3d_flow`')
     ap.add_argument('--no-f32-leg', action='store_true',
-                    help='skip the short exact-fp32-engine measurement that the default line carries as `engines.f32`')
+                    help='skip the short exact-fp32-engine measurement that the --full line carries as `engines.f32`')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / collective check without a GPU: every rank packs fake detection records on the CPU and '
                          'gathers them over gloo; prints the JSON line with value 0 (used by the CPU tests)')
@@ -85,9 +92,9 @@ def parse():
                          'dataset offline); 4 = ResNet-50 trunk at network input 1200x3974, batch 4, forward + decode + class NMS')
     ap.add_argument('--layers-out', default='',
                     help='write the full per-layer roofline table (every conv launch: shape, bytes, time, own bound) to this file; '
-                         'the JSON line always carries the 15 layer groups that lose most time as roofline.layers')
+                         'the --full JSON line carries the 15 layer groups that lose most time as roofline.layers')
     ap.add_argument('--no-pmc', action='store_true',
-                    help='do not measure roofline.traffic in this run (default at N = 1, --config 1: two short child runs of '
+                    help='do not measure roofline.traffic in this run (default with --full at N = 1, --config 1: two short child runs of '
                          'this script under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `WRITE_SIZE`, about a minute); '
                          'the committed profiles/pmc_*_traffic.json is then quoted if it matches the kernel sources')
     ap.add_argument('--no-mix-layers', action='store_true',
@@ -105,7 +112,61 @@ def parse():
                          "one_pair_at_a_time leg always runs on the isolated plan set)")
     ap.add_argument('--height', type=int, default=375)
     ap.add_argument('--width', type=int, default=1242)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure (sustained soak, one_pair_at_a_time, lazy '
+                         'keypoints, roofline with per-layer / PMC / in-mix tables, fp32 engine leg, full-3-D-flow leg, parity '
+                         'block, CPU baseline); default: set up, warm up, time --steps, print the line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, '
+                         'float32 / float64; the inputs are seeded, so two builds can be compared output for output')
+    args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs the real hot path (not --dry-run)')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write name -> array (torch tensor or numpy) as path/<name>.npy: integers and float64 as float64, every other float as
+    float32.  The outputs of one step are far below DUMP_LIMIT_BYTES; a dump that would exceed it is an error, not a truncation."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float32 if a.dtype.kind == 'f' and a.dtype != np.float64 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return total
+
+
+# the first eight entries of the forward's 15-tuple (stereo_rcnn.py return order); the other seven are None in eval mode
+FORWARD_OUTPUTS = ('rois_left', 'rois_right', 'cls_prob', 'bbox_pred', 'dim_orien_pred', 'kpts_prob', 'left_border_prob',
+                   'right_border_prob')
+# one object of the 3-D flow (pipeline.collect_3d) as a row: scalars and vectors in this order, disparity NaN where not aligned
+OBJECT_FIELDS = (('score', 1), ('box_left', 4), ('box_right', 4), ('dim', 3), ('alpha', 1), ('xyz', 3), ('theta', 1), ('kpts', 5),
+                 ('aligned', 1), ('xyz_init', 3), ('theta_init', 1), ('roi_index', 1), ('disparity', 1))
+
+
+def objects_array(objs):
+    """pipeline.collect_3d's object list -> (n, 29) float64 in OBJECT_FIELDS order."""
+    import numpy as np
+    width = sum(w for _, w in OBJECT_FIELDS)
+    out = np.full((len(objs), width), np.nan)
+    for i, o in enumerate(objs):
+        c = 0
+        for key, w in OBJECT_FIELDS:
+            if key in o:
+                out[i, c:c + w] = np.asarray(o[key], dtype=np.float64).reshape(-1)
+            c += w
+    return out
 
 
 def cpu_baseline(cfg_id, height, width):
@@ -414,6 +475,26 @@ def _fake_objects_from_pixels(left):
     return objs
 
 
+def measure_config3_flops(model, root, frame_id, dev, slots):
+    """(--full) algorithmic conv work of one frame as the configs[3] flow runs it (keypoint tower on the kept detections only): one
+    eager frame with the counter on; the row-limited launches are counted at the share of their rows that ran."""
+    from stereo_rcnn_amd import engine, pipeline, test_net
+    from stereo_rcnn_amd.model.utils import kitti_utils
+    lu = torch.from_numpy(test_net.read_png_rgb(os.path.join(root, 'image_2', frame_id + '.png'))).to(dev)
+    ru = torch.from_numpy(test_net.read_png_rgb(os.path.join(root, 'image_3', frame_id + '.png'))).to(dev)
+    calib = kitti_utils.read_obj_calibration(os.path.join(root, 'calib', frame_id + '.txt'))
+    prog, model.use_program = model.use_program, False
+    engine.FlopCounter.enabled, engine.FlopCounter.flops, engine.FlopCounter.launches, engine.FlopCounter.bytes = True, 0.0, 0, 0.0
+    engine.FlopCounter.rows = []
+    objs0 = pipeline.detect_3d_images(model, lu, ru, calib, slot=slots + 1)
+    torch.cuda.synchronize()
+    rows, engine.FlopCounter.rows, engine.FlopCounter.enabled = engine.FlopCounter.rows, None, False
+    model.use_program = prog
+    kept = int(pipeline._stage(300, dev, slots + 1).rec_host[0, 0])       # detections class NMS kept in that frame
+    flops_pair = sum(r['flops'] * ((kept / 300.0) if r['name'].startswith('kpts') else 1.0) for r in rows)
+    return {'flops_pair': flops_pair, 'kept': kept, 'objects': len(objs0)}
+
+
 def run_config3(args, rank, local_rank, world, use_dist):
     """BASELINE configs[3] (the reference's test_net.py:109-136,217-225,329-334 over data/kitti/splits/val.txt): one step = one
     frame of the rank's shard through stereo_rcnn_amd.test_net.run_split -- everything between the PNG files and the KITTI result
@@ -483,22 +564,7 @@ def run_config3(args, rank, local_rank, world, use_dist):
             model.use_program = not args.no_program
             slots = max(1, args.streams) if args.streams > 0 else 4
             test_net.run_split(model, root, warm, res_dir, dev, solver='host', slots=slots, prefetch=prefetch)   # calibration, tuning, programs
-            # algorithmic conv work of one frame as this flow runs it (keypoint tower on the kept detections only): one eager frame
-            # with the counter on; the row-limited launches are counted at the share of their rows that ran
-            from stereo_rcnn_amd.model.utils import kitti_utils
-            lu = torch.from_numpy(test_net.read_png_rgb(os.path.join(root, 'image_2', warm[0] + '.png'))).to(dev)
-            ru = torch.from_numpy(test_net.read_png_rgb(os.path.join(root, 'image_3', warm[0] + '.png'))).to(dev)
-            calib = kitti_utils.read_obj_calibration(os.path.join(root, 'calib', warm[0] + '.txt'))
-            prog, model.use_program = model.use_program, False
-            engine.FlopCounter.enabled, engine.FlopCounter.flops, engine.FlopCounter.launches, engine.FlopCounter.bytes = True, 0.0, 0, 0.0
-            engine.FlopCounter.rows = []
-            objs0 = pipeline.detect_3d_images(model, lu, ru, calib, slot=slots + 1)
-            torch.cuda.synchronize()
-            rows, engine.FlopCounter.rows, engine.FlopCounter.enabled = engine.FlopCounter.rows, None, False
-            model.use_program = prog
-            kept = int(pipeline._stage(300, dev, slots + 1).rec_host[0, 0])       # detections class NMS kept in that frame
-            flops_pair = sum(r['flops'] * ((kept / 300.0) if r['name'].startswith('kpts') else 1.0) for r in rows)
-            roof = {'flops_pair': flops_pair, 'kept': kept, 'objects': len(objs0)}
+            roof = measure_config3_flops(model, root, warm[0], dev, slots) if args.full else None
             torch.cuda.synchronize()
             if use_dist:
                 dist.barrier()
@@ -557,13 +623,14 @@ def run_config3(args, rank, local_rank, world, use_dist):
             if not dry:
                 from stereo_rcnn_amd import engine as _e
                 nh, nw_, _ = _e.preprocess_size(h, w, 600)
+            if roof is not None:
                 ach = roof['flops_pair'] * (K * world / elapsed) / world / 1e12          # per GPU
                 roofline = {'bound': 'mfma', 'kernel': ENGINE_DESC[args.precision], 'achieved': round(ach, 2), 'peak': PEAKS[args.precision],
                             'unit': 'TFLOP/s', 'frac': round(ach / PEAKS[args.precision], 4), 'traffic': None,
                             'algorithmic_gflop_per_step': round(roof['flops_pair'] / 1e9, 1),
                             'execution': 'whole-flow mode: algorithmic conv FLOPs of one frame as this flow runs it (keypoint tower on the %d '
                                          'detections class NMS kept of 300 rois) x pairs/s per GPU; the kernel-level figure (HIP events per '
-                                         'launch, PMC traffic) is `python bench.py` (--config 1), same kernels' % roof['kept']}
+                                         'launch, PMC traffic) is `python bench.py --full` (--config 1), same kernels' % roof['kept']}
             res = {'metric': 'stereo pairs/sec @1242x375 ResNet-101', 'value': round(K * world / elapsed, 3), 'unit': 'stereo pairs/s',
                    'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': round(elapsed / max(K, 1) * 1e3, 3), 'higher_is_better': True,
                    'scaling': 'weak' if args.steps is not None else 'strong', 'vs_baseline': None,
@@ -586,8 +653,10 @@ def run_config3(args, rank, local_rank, world, use_dist):
                    'roofline': roofline}
             if dry:
                 res['dry_run'] = True
-            elif not args.no_cpu_baseline and world == 1:
+            elif args.full and not args.no_cpu_baseline and world == 1:
                 res['cpu_baseline'] = cpu_baseline(2, h, w)
+            if args.dump_outputs:               # the detection record of the last frame of the timed split (distributed.REC_COLS)
+                dump_outputs(args.dump_outputs, {'record': records[-1]})
             print(json.dumps(res), flush=True)
     finally:
         shutil.rmtree(root, ignore_errors=True)
@@ -784,24 +853,30 @@ def main():
                 pipeline.collect_3d_batch(old)
             hs = pipeline.launch_3d_batch(model, im_l, im_r, im_info, [calib] * B, [(src_h, src_w, 3)] * B, slot=slot, solver='host')
             pending[slot] = hs
+            st['last_slot'] = slot
             if gr is not None:
                 for b in range(B):
                     rec_bufs[gr[0]][gr[1] + b].copy_(hs[b].rec, non_blocking=True)
             gathered(gr)
             return
         out = model(im_l, im_r, im_info, slot=slot, alias_outputs=True)     # views of the slot's result buffers: consumed right below, in stream order
+        dets = []
         for b in range(B):
             o = pipeline.image_outputs(out, b) if B > 1 else out
             det = hpost.decode_detections(o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], im_info[b:b + 1])
             keep_idx, num = hpost.class_nms_device(det, 1, 0.05)
+            dets.append((det, keep_idx, num))
             if gr is not None:
                 sdist.pack_records_device(det, keep_idx, num, 1, out=rec_bufs[gr[0]][gr[1] + b])
+        st['last'] = (out, dets)            # --dump-outputs: valid until the next step on this slot
         gathered(gr)
 
     def drain():
         """flow '3d': collect every batch still in flight (inside the timed region)"""
         for slot in sorted(pending):
-            pipeline.collect_3d_batch(pending.pop(slot))
+            objs = pipeline.collect_3d_batch(pending.pop(slot))
+            if slot == st.get('last_slot'):
+                st['last_objs'] = objs          # --dump-outputs: the object lists of the last step's batch
 
     def finish_gathers():
         """gather the partially filled buffer of the last steps"""
@@ -863,11 +938,23 @@ def main():
                                  'detection records runs on a side stream, one per %d steps, overlapped with the following forwards' % G}
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el[0])
+        if args.dump_outputs and rank == 0:
+            dump = {}
+            if wl['flow'] == '3d':
+                for b, objs in enumerate(st['last_objs']):
+                    dump['objects_%d' % b] = objects_array(objs)
+            else:
+                out, dets = st['last']
+                dump.update((name, t) for name, t in zip(FORWARD_OUTPUTS, out))
+                for b, (det, keep_idx, num) in enumerate(dets):
+                    dump.update(('%s_%d' % (k, b), v) for k, v in det.items())
+                    dump['keep_idx_%d' % b], dump['num_kept_%d' % b] = keep_idx, num
+            dump_outputs(args.dump_outputs, dump)
 
         # ---- `sustained`: the same headline loop once the chip is warm -- a 2 s soak, then >= 300 steps (the 20-step default region
         #      is 0.13 s: boost clocks; profiles/bench_r04_f16x3_60steps.json put the warm figure ~3 % lower)
         sustained = None
-        if not args.no_sustained and world == 1 and wl['flow'] != '3d':
+        if args.full and not args.no_sustained and world == 1 and wl['flow'] != '3d':
             ts = time.perf_counter()
             soak_steps = 0
             while time.perf_counter() - ts < 2.0:
@@ -889,20 +976,22 @@ def main():
             drain()
 
         # host cost of enqueueing ONE step on an idle GPU (queues empty: no back-pressure from the runtime in the number)
-        enq = []
-        for _ in range(5):
+        host_enqueue_idle_ms = None
+        if args.full:
+            enq = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                te = time.perf_counter()
+                step(0, gather=False)
+                enq.append((time.perf_counter() - te) * 1e3)
+                drain()
             torch.cuda.synchronize()
-            te = time.perf_counter()
-            step(0, gather=False)
-            enq.append((time.perf_counter() - te) * 1e3)
-            drain()
-        torch.cuda.synchronize()
-        host_enqueue_idle_ms = sorted(enq)[len(enq) // 2]
+            host_enqueue_idle_ms = round(sorted(enq)[len(enq) // 2], 3)
 
         # the same K steps strictly one batch at a time (reported next to the headline when S > 1)
         single = None
         insitu = None                                  # the in-situ (latency) plan set, when the headline ran on the shipped one
-        if S > 1:
+        if args.full and S > 1:
             engine.set_tune_mode('isolated')       # one batch at a time runs on the plans tuned for that (the first step re-tunes / re-records)
             sstreams.set_pairs_in_flight(1)        # ... with the independent branches on side streams (latency mode)
             headline_plans = dict(engine._TUNED)
@@ -939,7 +1028,7 @@ def main():
 
         # ---- the product's default flow of the same step: keypoint branch after class NMS, on the kept detections only
         lazy_fig = None
-        if lazy_default and args.precision == 'f16x3' and not use_graph:
+        if args.full and lazy_default and args.precision == 'f16x3' and not use_graph:
             def lazy_step(slot):
                 if wl['flow'] == '3d':
                     return step(slot, gather=False)
@@ -989,7 +1078,7 @@ def main():
         #  `roofline.layers`: the per-layer table (every launch against ITS OWN bound), 15 worst groups; --layers-out = all.
         roofline = None
         engines = None
-        if rank == 0:
+        if args.full and rank == 0:
             L = _lib.lib()
             model.use_graph = False
             use_program = model.use_program
@@ -1180,7 +1269,7 @@ def main():
     #      ranks, aggregate pairs/s), so that on an 8-GPU node the host-solver side of the flow is measured under the load of
     #      all ranks: solver threads sized by LOCAL_WORLD_SIZE and pinned to the GPU's NUMA node (distributed.py).
     full3d = None
-    if args.config == 1 and not args.no_3d_leg:
+    if args.full and args.config == 1 and not args.no_3d_leg:
         if use_dist:
             dist.barrier()
         frame = (im_l, im_r, im_info, calib, (args.height, args.width, 3), float(im_info[0, 2]))
@@ -1228,7 +1317,7 @@ def main():
                        'weights': 'seeded random init, reference state_dict schema', 'hipgraph': use_graph,
                        'native_launch_program': bool(model.use_program),
                        'host_enqueue_ms_per_step': round(host_enqueue_ms, 3),
-                       'host_enqueue_ms_per_step_idle_gpu': round(host_enqueue_idle_ms, 3), 'plans_preloaded': plans_loaded,
+                       'host_enqueue_ms_per_step_idle_gpu': host_enqueue_idle_ms, 'plans_preloaded': plans_loaded,
                        'conv_engine': args.precision, 'pairs_in_flight': S * B, 'batches_in_flight': S,
                        'stream_placement': {'main_streams': sstreams.MAIN_KIND, 'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES'),
                                             'branch_side_streams': sstreams.SIDE_KIND,
@@ -1251,10 +1340,10 @@ def main():
             res['value_ms_note'] = 'ms_per_step is per batch of %d pairs; value = pairs/s' % B
         if sustained is not None:
             res['sustained'] = sustained
-        if not args.no_parity and world == 1 and args.config == 1:
+        if args.full and not args.no_parity and world == 1 and args.config == 1:
             import bench_parity
             res['parity'] = bench_parity.parity_block(dev, args.precision)
-        if not args.no_cpu_baseline and world == 1:          # the CPU path timed beside it: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU path timed beside it: rank 0 at N = 1 only
             res['cpu_baseline'] = cpu_baseline(args.config, src_h, src_w)
         print(json.dumps(res), flush=True)
     if args.plans and not plans_loaded and rank == 0:

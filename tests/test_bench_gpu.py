@@ -32,7 +32,7 @@ def _check(line, steps, warmup):
 
 
 def test_bench_single_process_line(dev):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1'], cwd=ROOT,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--full'], cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check(out.stdout.strip().splitlines()[-1], 4, 1)
@@ -70,7 +70,7 @@ def test_bench_under_torch_distributed_run(dev):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
                           '127.0.0.1', '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-                          '--warmup', '1', '--no-cpu-baseline', '--no-pmc'], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+                          '--warmup', '1', '--full', '--no-cpu-baseline', '--no-pmc'], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check([ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')][-1], 5, 1)
     assert 'all_gather' in d['config']['parallelism']
@@ -82,7 +82,7 @@ def test_bench_other_baseline_configs_are_driver_runnable(dev, cfg, batch):
     bench.py contract: one JSON line, `config.workload` names the BASELINE entry, value = pairs/s = batch / step time,
     roofline (with the per-layer table) included."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', str(cfg), '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline'], cwd=ROOT, capture_output=True, text=True, timeout=1200)
+                          '--full', '--no-cpu-baseline'], cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     assert KEYS <= set(d) and d['steps'] == 2 and d['n_gpus'] == 1 and d['unit'] == 'stereo pairs/s'
@@ -100,7 +100,7 @@ def test_bench_config3_val_list_replay_is_driver_runnable(dev):
     fused preprocessing, forward, full 3-D flow with the host solver, KITTI result files) and gathered -- one JSON line of the
     same contract, with the host-side split per pair and the rate at which one rank's host budget saturates."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '3', '--steps', '32', '--warmup', '8',
-                          '--no-cpu-baseline'], cwd=ROOT, capture_output=True, text=True, timeout=1200)
+                          '--full', '--no-cpu-baseline'], cwd=ROOT, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith('{')][-1])
     c = d['config']
@@ -114,3 +114,24 @@ def test_bench_config3_val_list_replay_is_driver_runnable(dev):
     assert c['host_saturation']['pairs_per_s_at_which_the_host_saturates'] > 10
     r = d['roofline']
     assert r['bound'] == 'mfma' and 0 < r['frac'] < 1 and 1200 < r['algorithmic_gflop_per_step'] < 1960
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(dev, tmp_path):
+    """A plain run (no --full) carries the headline only -- `value` over exactly --steps timed steps, `ms_per_step` -- and
+    --dump-outputs writes the last timed step's forward outputs, decoded detections and class-NMS keep list."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs',
+                          str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert KEYS <= set(d) and d['steps'] == 3 and d['warmup'] == 1 and d['n_gpus'] == 1
+    assert d['value'] > 20 and abs(d['value'] - 1e3 / d['ms_per_step']) < 0.05 * d['value']
+    assert d['roofline'] is None and 'cpu_baseline' not in d and 'parity' not in d and 'sustained' not in d
+    names = {f[:-4] for f in os.listdir(str(tmp_path))}
+    assert {'rois_left', 'cls_prob', 'bbox_pred', 'boxes_left_0', 'scores_0', 'keep_idx_0', 'num_kept_0'} <= names, names
+    got = {n: np.load(str(tmp_path / (n + '.npy'))) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got['rois_left'].shape == (1, 300, 5) and np.isfinite(got['bbox_pred']).all()
+    k = int(got['num_kept_0'][0])
+    assert 0 < k <= 300 and (got['keep_idx_0'][:k] >= 0).all() and (got['keep_idx_0'][k:] == -1).all()

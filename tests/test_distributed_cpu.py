@@ -290,3 +290,23 @@ def test_png_decode_worker_processes(tmp_path):
     finally:
         w.close()
     assert all(pr.poll() is not None for pr in w.procs) or not w.procs
+
+
+def test_bench_dump_outputs_helpers(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32 (float tensors) or float64 (integers, doubles), the
+    3-D flow's object lists as fixed-width float64 rows, and a dump beyond the 64 MB limit is refused, not truncated."""
+    import numpy as np
+    import bench
+    objs = [{'score': 0.9, 'box_left': np.arange(4.0), 'box_right': np.arange(4.0) + 1, 'dim': np.ones(3), 'alpha': 0.1,
+             'xyz': np.array([1.0, 2, 3]), 'theta': 0.2, 'kpts': np.arange(5.0), 'aligned': False, 'xyz_init': np.zeros(3),
+             'theta_init': 0.3, 'roi_index': 7}]
+    rows = bench.objects_array(objs)
+    assert rows.shape == (1, 29) and rows[0, 0] == 0.9 and rows[0, 27] == 7 and np.isnan(rows[0, 28])
+    n = bench.dump_outputs(str(tmp_path / 'd'), {'a': torch.arange(6, dtype=torch.int32), 'b': torch.ones(2, 3, dtype=torch.float16),
+                                                 'objects_0': rows})
+    got = {f: np.load(str(tmp_path / 'd' / f)) for f in sorted(os.listdir(str(tmp_path / 'd')))}
+    assert sorted(got) == ['a.npy', 'b.npy', 'objects_0.npy'] and n == 6 * 8 + 6 * 4 + 29 * 8
+    assert got['a.npy'].dtype == np.float64 and got['b.npy'].dtype == np.float32 and got['b.npy'].shape == (2, 3)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros((65 << 20) // 4, np.float32)})
+    assert not os.path.exists(str(tmp_path / 'big'))
