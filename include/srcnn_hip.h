@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -513,6 +513,59 @@ SRCNN_API int srcnn_prof_read(double *conv_ms, double *conv_flops, long long *co
  * returns the number of launches recorded (which may exceed max) or a negative error.  Does not reset the recording --
  * srcnn_prof_read / srcnn_prof_enable do.  Used by bench.py / tools/layer_table.py for the per-layer roofline table. */
 SRCNN_API int srcnn_prof_read_launches(float *ms, int max);
+
+/* ------------------------------------------------------------------ KITTI object evaluation
+ * The device side of stereo_rcnn_amd/kitti_eval.py, a restatement of the KITTI object devkit's evaluation
+ * (evaluate_object_3d_offline: cleanData / computeStatistics / eval_class).  A whole split is one ragged batch:
+ * frame f owns detection rows [det_off[f], det_off[f+1]), ground-truth rows [gt_off[f], gt_off[f+1]) (DontCare rows
+ * excluded) and don't-care rows [dc_off[f], dc_off[f+1]), each row SRCNN_KITTI_COLS doubles
+ * [x1 y1 x2 y2 h w l x y z ry alpha score] (score unused for ground truth, only x1..y2 used for don't-care rows).
+ * Overlap matrices are laid out per frame, ground-truth (or don't-care) major: frame f's det j x gt i overlap is
+ * ov_*[pair_off[f] + i * n_det(f) + j] with pair_off[f+1] - pair_off[f] = n_gt(f) * n_det(f), and its det j x
+ * don't-care k overlap is ov_dc[dcpair_off[f] + k * n_det(f) + j].  Everything is float64 with no "+1".
+ * LIMIT: at most SRCNN_KITTI_MAX_DET detections per frame (max_det_per_frame is the caller's count of the largest
+ * frame); a larger count returns SRCNN_ERR_ARG before anything is launched.  No workspace is needed. */
+#define SRCNN_KITTI_COLS 13
+#define SRCNN_KITTI_MAX_DET 4096
+#define SRCNN_KITTI_SLOTS 41
+typedef struct srcnn_kitti_split {
+    int n_frames;
+    int max_det_per_frame;
+    const int *det_off, *gt_off, *dc_off;    /* (n_frames + 1) row offsets */
+    const long long *pair_off, *dcpair_off;  /* (n_frames + 1) offsets into ov_img / ov_bev / ov_3d and ov_dc */
+    const double *det, *gt, *dc;             /* rows of SRCNN_KITTI_COLS doubles */
+    double *ov_img;                          /* 2-D IoU */
+    double *ov_bev;                          /* rotated-rectangle IoU in the x-z plane */
+    double *ov_3d;                           /* BEV intersection x height overlap (y is the bottom face), over the union volume */
+    double *ov_dc;                           /* 2-D intersection over the DETECTION's area (devkit criterion 0) */
+} srcnn_kitti_split;
+/* Fills ov_img, ov_bev, ov_3d and ov_dc of every frame (one workgroup per frame).  Degenerate geometry (identical or
+ * nested boxes, shared edges, zero extent, no contact) gives finite values; an empty union gives 0. */
+SRCNN_API int srcnn_kitti_overlaps(const srcnn_kitti_split *split, srcnn_stream_t stream);
+/* One match pass of computeStatistics over every (configuration c, threshold slot t, frame f): one wavefront per item,
+ * detections across the lanes (64-wide chunks), every greedy choice a cross-lane reduction.  A configuration is a
+ * (class, difficulty) flag set, a metric (0 image, 1 BEV, 2 3-D) and that metric's minimum overlap (strict >).
+ * compute_fp = 0 (pass 1, n_slots must be 1): gt_score[c * n_gt_total + g] = the score of the detection ground truth g
+ *   is a true positive with, -inf otherwise.
+ * compute_fp = 1 (pass 2): detections scoring below thresholds[c * n_slots + t] are left out; tp / fp / fn (int) and
+ *   similarity (double: sum over the frame's true positives, in ground-truth order, of (1 + cos(alpha_gt - alpha_det)) / 2;
+ *   -1 when tp + fp == 0; 0 for the BEV and 3-D metrics) go to index (c * n_slots + t) * n_frames + f.  Slots
+ *   t >= cfg_n_thresh[c] get zeros.  Results are deterministic: no atomics, fixed reduction order. */
+typedef struct srcnn_kitti_match_desc {
+    int n_cfg, n_slots, compute_fp;
+    int n_gt_total, n_det_total;             /* gt_off[n_frames], det_off[n_frames] */
+    const int *cfg_flags;                    /* (n_cfg) row of ign_gt / ign_det to use */
+    const int *cfg_metric;                   /* (n_cfg) 0 / 1 / 2 */
+    const double *cfg_min_overlap;           /* (n_cfg) */
+    const int *cfg_n_thresh;                 /* (n_cfg) pass 2: thresholds in use, <= n_slots */
+    const double *thresholds;                /* (n_cfg, n_slots) pass 2 */
+    const signed char *ign_gt;               /* (flag sets, n_gt_total): cleanData's ignored_gt, 0 / 1 / -1 */
+    const signed char *ign_det;              /* (flag sets, n_det_total): ignored_det, 0 / 1 / -1 */
+    double *gt_score;                        /* pass 1 output */
+    int *tp, *fp, *fn;                       /* pass 2 outputs */
+    double *similarity;
+} srcnn_kitti_match_desc;
+SRCNN_API int srcnn_kitti_match(const srcnn_kitti_split *split, const srcnn_kitti_match_desc *match, srcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

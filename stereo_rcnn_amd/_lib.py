@@ -39,6 +39,23 @@ class ConvDesc(ctypes.Structure):
                 ("up_top", c_void_p), ("up_format", c_int), ("up_H", c_int), ("up_W", c_int)]
 
 
+class KittiSplit(ctypes.Structure):
+    """struct srcnn_kitti_split (include/srcnn_hip.h): a ragged batch of frames, device pointers."""
+    _fields_ = [("n_frames", c_int), ("max_det_per_frame", c_int),
+                ("det_off", c_void_p), ("gt_off", c_void_p), ("dc_off", c_void_p),
+                ("pair_off", c_void_p), ("dcpair_off", c_void_p),
+                ("det", c_void_p), ("gt", c_void_p), ("dc", c_void_p),
+                ("ov_img", c_void_p), ("ov_bev", c_void_p), ("ov_3d", c_void_p), ("ov_dc", c_void_p)]
+
+
+class KittiMatchDesc(ctypes.Structure):
+    """struct srcnn_kitti_match_desc (include/srcnn_hip.h): one match pass, device pointers."""
+    _fields_ = [("n_cfg", c_int), ("n_slots", c_int), ("compute_fp", c_int), ("n_gt_total", c_int), ("n_det_total", c_int),
+                ("cfg_flags", c_void_p), ("cfg_metric", c_void_p), ("cfg_min_overlap", c_void_p), ("cfg_n_thresh", c_void_p),
+                ("thresholds", c_void_p), ("ign_gt", c_void_p), ("ign_det", c_void_p),
+                ("gt_score", c_void_p), ("tp", c_void_p), ("fp", c_void_p), ("fn", c_void_p), ("similarity", c_void_p)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "srcnn_version": (c_int, []),
@@ -136,6 +153,8 @@ _SIGNATURES = {
     "srcnn_prof_read_launches": (c_int, [ctypes.POINTER(ctypes.c_float), c_int]),
     "srcnn_prof_read": (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_double),
                                 ctypes.POINTER(ctypes.c_longlong)]),
+    "srcnn_kitti_overlaps": (c_int, [ctypes.POINTER(KittiSplit), c_void_p]),
+    "srcnn_kitti_match": (c_int, [ctypes.POINTER(KittiSplit), ctypes.POINTER(KittiMatchDesc), c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,387 @@
+"""CPU yardstick of stereo_rcnn_amd.kitti_eval: a literal, loop-by-loop Python transcription of the KITTI object devkit's
+evaluation (evaluate_object_3d_offline: cleanData, imageBoxOverlap / groundBoxOverlap / box3DOverlap, computeStatistics,
+getThresholds, eval_class) for small inputs.  The product never imports it.
+
+The BEV intersection here is computed by a different method than the device kernel's polygon clipping: the vertex set
+(corners of either box inside the other, plus every edge-edge crossing), sorted by angle about its centroid, shoelace area.
+Frames are lists of rows of kitti_eval.LABEL_DTYPE / RESULT_DTYPE arrays, the ground truth including its DontCare rows.
+"""
+import math
+
+CLASSES = ('Car', 'Pedestrian', 'Cyclist')
+DIFFICULTIES = ('easy', 'moderate', 'hard')
+MIN_HEIGHT = (40, 25, 25)
+MAX_OCCLUSION = (0, 1, 2)
+MAX_TRUNCATION = (0.15, 0.30, 0.50)
+N_SAMPLE_PTS = 41
+NO_DETECTION = -10000000.0
+IMAGE, GROUND, BOX3D = 0, 1, 2
+METRIC_NAMES = ('bbox', 'bev', '3d')
+DEFAULT_OVERLAPS = {'Car': ((0.7, 0.7, 0.7), (0.7, 0.5, 0.5)),
+                    'Pedestrian': ((0.5, 0.5, 0.5), (0.5, 0.25, 0.25)),
+                    'Cyclist': ((0.5, 0.5, 0.5), (0.5, 0.25, 0.25))}
+
+
+# ---------------------------------------------------------------- geometry
+
+def image_overlap(a, b, criterion=-1):
+    x1, y1 = max(a['x1'], b['x1']), max(a['y1'], b['y1'])
+    x2, y2 = min(a['x2'], b['x2']), min(a['y2'], b['y2'])
+    w, h = x2 - x1, y2 - y1
+    if w <= 0 or h <= 0:
+        return 0.0
+    inter = w * h
+    a_area = (a['x2'] - a['x1']) * (a['y2'] - a['y1'])
+    b_area = (b['x2'] - b['x1']) * (b['y2'] - b['y1'])
+    if criterion == -1:
+        den = a_area + b_area - inter
+    elif criterion == 0:
+        den = a_area
+    else:
+        den = b_area
+    return inter / den if den > 0 else 0.0
+
+
+def footprint(b):
+    """Ground-plane corners (x, z) + R c, R = [[cos ry, sin ry], [-sin ry, cos ry]]."""
+    c, s = math.cos(b['ry']), math.sin(b['ry'])
+    hl, hw = b['l'] / 2.0, b['w'] / 2.0
+    out = []
+    for cx, cz in ((hl, hw), (hl, -hw), (-hl, -hw), (-hl, hw)):
+        out.append((b['x'] + (c * cx + s * cz), b['z'] + (-s * cx + c * cz)))
+    return out
+
+
+def _cross(o, a, b):
+    return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+
+
+def _inside(p, poly, eps=1e-12):
+    s = [_cross(poly[k], poly[(k + 1) % 4], p) for k in range(4)]
+    return all(v >= -eps for v in s) or all(v <= eps for v in s)
+
+
+def _segment_crossing(p1, p2, q1, q2):
+    r = (p2[0] - p1[0], p2[1] - p1[1])
+    s = (q2[0] - q1[0], q2[1] - q1[1])
+    den = r[0] * s[1] - r[1] * s[0]
+    if den == 0:
+        return None                      # parallel: shared stretches are found by the inside tests of their end points
+    qp = (q1[0] - p1[0], q1[1] - p1[1])
+    t = (qp[0] * s[1] - qp[1] * s[0]) / den
+    u = (qp[0] * r[1] - qp[1] * r[0]) / den
+    if -1e-12 <= t <= 1 + 1e-12 and -1e-12 <= u <= 1 + 1e-12:
+        return (p1[0] + t * r[0], p1[1] + t * r[1])
+    return None
+
+
+def polygon_area(pts):
+    a = 0.0
+    for k in range(len(pts)):
+        x0, z0 = pts[k]
+        x1, z1 = pts[(k + 1) % len(pts)]
+        a += x0 * z1 - x1 * z0
+    return abs(a) / 2.0
+
+
+def bev_intersection(a, b):
+    """Area of the intersection of two convex quadrilaterals by the vertex-set / angle-sort method."""
+    if polygon_area(a) == 0.0 or polygon_area(b) == 0.0:
+        return 0.0
+    pts = [p for p in a if _inside(p, b)] + [q for q in b if _inside(q, a)]
+    for i in range(4):
+        for j in range(4):
+            x = _segment_crossing(a[i], a[(i + 1) % 4], b[j], b[(j + 1) % 4])
+            if x is not None:
+                pts.append(x)
+    if len(pts) < 3:
+        return 0.0
+    cx = sum(p[0] for p in pts) / len(pts)
+    cz = sum(p[1] for p in pts) / len(pts)
+    pts.sort(key=lambda p: math.atan2(p[1] - cz, p[0] - cx))
+    return polygon_area(pts)
+
+
+def ground_overlap(d, g):
+    inter = bev_intersection(footprint(d), footprint(g))
+    den = d['l'] * d['w'] + g['l'] * g['w'] - inter
+    return inter / den if den > 0 else 0.0
+
+
+def box3d_overlap(d, g):
+    inter = bev_intersection(footprint(d), footprint(g))
+    ymax = min(d['y'], g['y'])
+    ymin = max(d['y'] - d['h'], g['y'] - g['h'])
+    inter_vol = inter * max(0.0, ymax - ymin)
+    det_vol = d['h'] * d['w'] * d['l']
+    gt_vol = g['h'] * g['w'] * g['l']
+    den = det_vol + gt_vol - inter_vol
+    return inter_vol / den if den > 0 else 0.0
+
+
+OVERLAP = {IMAGE: image_overlap, GROUND: ground_overlap, BOX3D: box3d_overlap}
+
+
+# ---------------------------------------------------------------- devkit
+
+def clean_data(gt, det, current_class, difficulty):
+    """cleanData: (ignored_gt, ignored_det, dontcare, n_gt) of one frame."""
+    ignored_gt, ignored_det, dc = [], [], []
+    n_gt = 0
+    cls = current_class.lower()
+    for g in gt:
+        t = str(g['type']).lower()
+        if t == cls:
+            valid_class = 1
+        elif cls == 'pedestrian' and t == 'person_sitting':
+            valid_class = 0
+        elif cls == 'car' and t == 'van':
+            valid_class = 0
+        else:
+            valid_class = -1
+        height = abs(g['y1'] - g['y2'])
+        ignore = False
+        if (g['occluded'] > MAX_OCCLUSION[difficulty] or g['truncated'] > MAX_TRUNCATION[difficulty]
+                or height <= MIN_HEIGHT[difficulty]):
+            ignore = True
+        if valid_class == 1 and not ignore:
+            ignored_gt.append(0)
+            n_gt += 1
+        elif valid_class == 0 or (ignore and valid_class == 1):
+            ignored_gt.append(1)
+        else:
+            ignored_gt.append(-1)
+    for g in gt:
+        if str(g['type']).lower() == 'dontcare':
+            dc.append(g)
+    for d in det:
+        valid_class = 1 if str(d['type']).lower() == cls else -1
+        height = d['y2'] - d['y1']
+        if height < MIN_HEIGHT[difficulty]:
+            ignored_det.append(1)
+        elif valid_class == 1:
+            ignored_det.append(0)
+        else:
+            ignored_det.append(-1)
+    return ignored_gt, ignored_det, dc, n_gt
+
+
+def compute_statistics(gt, det, dc, ignored_gt, ignored_det, compute_fp, ov, dcov, min_overlap, metric, compute_aos,
+                       thresh=0.0):
+    """computeStatistics of one frame; ov[i][j] = overlap(det j, gt i), dcov[k][j] = criterion-0 overlap(det j, dc k)."""
+    stat = {'tp': 0, 'fp': 0, 'fn': 0, 'similarity': 0.0}
+    v, delta = [], []
+    assigned_detection = [False] * len(det)
+    for i in range(len(gt)):
+        if ignored_gt[i] == -1:
+            continue
+        det_idx = -1
+        valid_detection = NO_DETECTION
+        max_iou = 0.0
+        assigned_ignored_det = False
+        for j in range(len(det)):
+            if ignored_det[j] == -1:
+                continue
+            if assigned_detection[j]:
+                continue
+            if compute_fp and det[j]['score'] < thresh:
+                continue
+            overlap = ov[i][j]
+            if not compute_fp and overlap > min_overlap and det[j]['score'] > valid_detection:
+                det_idx = j
+                valid_detection = det[j]['score']
+            elif compute_fp and overlap > min_overlap and (overlap > max_iou or assigned_ignored_det) and ignored_det[j] == 0:
+                max_iou = overlap
+                det_idx = j
+                valid_detection = 1
+                assigned_ignored_det = False
+            elif compute_fp and overlap > min_overlap and valid_detection == NO_DETECTION and ignored_det[j] == 1:
+                det_idx = j
+                valid_detection = 1
+                assigned_ignored_det = True
+        if valid_detection == NO_DETECTION and ignored_gt[i] == 0:
+            stat['fn'] += 1
+        elif valid_detection != NO_DETECTION and (ignored_gt[i] == 1 or ignored_det[det_idx] == 1):
+            assigned_detection[det_idx] = True
+        elif valid_detection != NO_DETECTION:
+            stat['tp'] += 1
+            v.append(det[det_idx]['score'])
+            if compute_aos:
+                delta.append(gt[i]['alpha'] - det[det_idx]['alpha'])
+            assigned_detection[det_idx] = True
+    if compute_fp:
+        for j in range(len(det)):
+            if not (assigned_detection[j] or ignored_det[j] == -1 or ignored_det[j] == 1 or det[j]['score'] < thresh):
+                stat['fp'] += 1
+        nstuff = 0
+        if metric == IMAGE:
+            for k in range(len(dc)):
+                for j in range(len(det)):
+                    if assigned_detection[j]:
+                        continue
+                    if ignored_det[j] == -1 or ignored_det[j] == 1:
+                        continue
+                    if det[j]['score'] < thresh:
+                        continue
+                    if dcov[k][j] > min_overlap:
+                        assigned_detection[j] = True
+                        nstuff += 1
+        stat['fp'] -= nstuff
+        if compute_aos:
+            tmp = [0.0] * stat['fp']
+            for d in delta:
+                tmp.append((1.0 + math.cos(d)) / 2.0)
+            assert len(tmp) == stat['fp'] + stat['tp']
+            if stat['tp'] > 0 or stat['fp'] > 0:
+                s = 0.0
+                for x in tmp:
+                    s += x
+                stat['similarity'] = s
+            else:
+                stat['similarity'] = -1.0
+    stat['v'] = v
+    return stat
+
+
+def get_thresholds(v, n_groundtruth):
+    v = sorted(v, reverse=True)
+    t = []
+    current_recall = 0.0
+    for i in range(len(v)):
+        l_recall = (i + 1) / float(n_groundtruth)
+        if i < len(v) - 1:
+            r_recall = (i + 2) / float(n_groundtruth)
+        else:
+            r_recall = l_recall
+        if (r_recall - current_recall) < (current_recall - l_recall) and i < len(v) - 1:
+            continue
+        t.append(v[i])
+        current_recall += 1.0 / (N_SAMPLE_PTS - 1.0)
+    return t
+
+
+def ap_r11(precision):
+    p = suffix_max(precision)
+    s = 0
+    for i in range(0, N_SAMPLE_PTS, 4):
+        s += p[i]
+    return s / 11.0 * 100.0
+
+
+def ap_r40(precision):
+    p = suffix_max(precision)
+    s = 0
+    for i in range(1, N_SAMPLE_PTS):
+        s += p[i]
+    return s / 40.0 * 100.0
+
+
+def suffix_max(precision):
+    return [max(precision[i:]) for i in range(len(precision))]
+
+
+def frame_overlaps(gt, det, metric):
+    """ov[i][j] over every label row (DontCare included) and every detection; dcov[k][j] against the DontCare rows."""
+    f = OVERLAP[metric]
+    ov = [[f(d, g) for d in det] for g in gt]
+    dcs = [g for g in gt if str(g['type']).lower() == 'dontcare']
+    dcov = [[image_overlap(d, g, 0) for d in det] for g in dcs]
+    return ov, dcov
+
+
+def eval_class(gt_frames, det_frames, current_class, metric, difficulty, min_overlap, overlaps):
+    """eval_class: {'n_gt', 'thresholds', 'tp', 'fp', 'fn', 'precision', 'aos'} (precision / aos: 41 points, no max yet)."""
+    compute_aos = metric == IMAGE
+    ignored_gt, ignored_det, dontcare = [], [], []
+    n_gt = 0
+    v = []
+    for f in range(len(gt_frames)):
+        i_gt, i_det, dc, n = clean_data(gt_frames[f], det_frames[f], current_class, difficulty)
+        ignored_gt.append(i_gt)
+        ignored_det.append(i_det)
+        dontcare.append(dc)
+        n_gt += n
+        ov, dcov = overlaps[f]
+        st = compute_statistics(gt_frames[f], det_frames[f], dc, i_gt, i_det, False, ov, dcov, min_overlap, metric, False)
+        v.extend(st['v'])
+    if n_gt == 0:
+        return {'n_gt': 0, 'thresholds': [], 'tp': [], 'fp': [], 'fn': [], 'precision': [0.0] * N_SAMPLE_PTS,
+                'aos': [0.0] * N_SAMPLE_PTS}
+    thresholds = get_thresholds(v, n_gt)
+    pr = [{'tp': 0, 'fp': 0, 'fn': 0, 'similarity': 0.0} for _ in thresholds]
+    for t in range(len(thresholds)):
+        for f in range(len(gt_frames)):
+            ov, dcov = overlaps[f]
+            st = compute_statistics(gt_frames[f], det_frames[f], dontcare[f], ignored_gt[f], ignored_det[f], True, ov, dcov,
+                                    min_overlap, metric, compute_aos, thresholds[t])
+            pr[t]['tp'] += st['tp']
+            pr[t]['fp'] += st['fp']
+            pr[t]['fn'] += st['fn']
+            if st['similarity'] != -1:
+                pr[t]['similarity'] += st['similarity']
+    precision, aos = [0.0] * N_SAMPLE_PTS, [0.0] * N_SAMPLE_PTS
+    for t in range(len(thresholds)):
+        den = pr[t]['tp'] + pr[t]['fp']
+        precision[t] = pr[t]['tp'] / float(den) if den > 0 else 0.0
+        if compute_aos:
+            aos[t] = pr[t]['similarity'] / float(den) if den > 0 else 0.0
+    return {'n_gt': n_gt, 'thresholds': thresholds, 'tp': [p['tp'] for p in pr], 'fp': [p['fp'] for p in pr],
+            'fn': [p['fn'] for p in pr], 'precision': precision, 'aos': aos}
+
+
+def evaluate(gt_frames, det_frames, classes=CLASSES, overlap_sets=None):
+    """Same layout as stereo_rcnn_amd.kitti_eval.evaluate (class -> overlap key -> metric -> difficulty -> entry)."""
+    sets = dict(DEFAULT_OVERLAPS)
+    sets.update(overlap_sets or {})
+    cache = {}
+    out = {}
+    for cls in classes:
+        if not any(str(d['type']).lower() == cls.lower() for det in det_frames for d in det):
+            continue
+        out[cls] = {}
+        for triple in sets[cls]:
+            key = ', '.join('%.2f' % x for x in triple)
+            res = {'bbox': {}, 'bev': {}, '3d': {}, 'aos': {}}
+            for metric in (IMAGE, GROUND, BOX3D):
+                if metric not in cache:
+                    cache[metric] = [frame_overlaps(g, d, metric) for g, d in zip(gt_frames, det_frames)]
+                for diff in range(3):
+                    r = eval_class(gt_frames, det_frames, cls, metric, diff, triple[metric], cache[metric])
+                    n = r['n_gt']
+                    e = {'R11': ap_r11(r['precision']) if n else None, 'R40': ap_r40(r['precision']) if n else None,
+                         'precision': suffix_max(r['precision']), 'n_gt': n, 'thresholds': r['thresholds'],
+                         'tp': r['tp'], 'fp': r['fp'], 'fn': r['fn']}
+                    res[METRIC_NAMES[metric]][DIFFICULTIES[diff]] = e
+                    if metric == IMAGE:
+                        res['aos'][DIFFICULTIES[diff]] = {'R11': ap_r11(r['aos']) if n else None,
+                                                          'R40': ap_r40(r['aos']) if n else None,
+                                                          'precision': suffix_max(r['aos']), 'n_gt': n}
+            out[cls][key] = res
+    return out
+
+
+# ---------------------------------------------------------------- the pass-2 choice, two ways
+
+def select_sequential(cands, min_overlap):
+    """The devkit's loop over one ground truth's candidates [(overlap, ignored_det)] (compute_fp = true): index or -1."""
+    det_idx, valid_detection, max_iou, assigned_ignored_det = -1, NO_DETECTION, 0.0, False
+    for j, (overlap, ign) in enumerate(cands):
+        if overlap > min_overlap and (overlap > max_iou or assigned_ignored_det) and ign == 0:
+            max_iou, det_idx, valid_detection, assigned_ignored_det = overlap, j, 1, False
+        elif overlap > min_overlap and valid_detection == NO_DETECTION and ign == 1:
+            det_idx, valid_detection, assigned_ignored_det = j, 1, True
+    return det_idx
+
+
+def select_reduced(cands, min_overlap):
+    """The same choice as the device makes it: the ignored_det == 0 candidate with the largest overlap (ties: first), else
+    the first ignored_det == 1 candidate -- two reductions over the candidates, no state carried from one to the next."""
+    best, best_j, first_ign = None, -1, -1
+    for j, (overlap, ign) in enumerate(cands):
+        if not overlap > min_overlap:
+            continue
+        if ign == 0 and (best is None or overlap > best):
+            best, best_j = overlap, j
+        elif ign == 1 and first_ign < 0:
+            first_ign = j
+    return best_j if best_j >= 0 else first_ign
