@@ -9,7 +9,8 @@
 //       pass 1 (compute_fp = 0): the candidate with the highest score, ties to the lowest index;
 //       pass 2 (compute_fp = 1): the non-ignored candidate with the largest overlap, ties to the lowest index, else the
 //         lowest-index ignored candidate -- what the devkit's sequential `(overlap > max_iou || assigned_ignored_det)`
-//         state machine reduces to (tests/kitti_eval_ref.py checks the reduction against the literal loop).
+//         state machine reduces to (tests/kitti_eval_ref.py checks the reduction against the literal loop; the reduction over several
+//         chunks per lane -- frames of more than 64 detections -- is checked on the device by tests/test_kitti_eval_crowded_gpu.py).
 //     A lane keeps the "assigned" flags of its detections as bits of one 64-bit word (bit c = chunk c), which is what
 //     bounds a frame to SRCNN_KITTI_MAX_DET = 64 x 64 detections.  Counts are integers, the similarity is summed in
 //     ground-truth order by every lane alike: no atomics, the same bits on every run.

@@ -5,8 +5,18 @@ getThresholds, eval_class) for small inputs.  The product never imports it.
 The BEV intersection here is computed by a different method than the device kernel's polygon clipping: the vertex set
 (corners of either box inside the other, plus every edge-edge crossing), sorted by angle about its centroid, shoelace area.
 Frames are lists of rows of kitti_eval.LABEL_DTYPE / RESULT_DTYPE arrays, the ground truth including its DontCare rows.
+
+Two intersection routines, and which is the authority for what:
+  * bev_intersection (float64, vertex set + angle sort, 1e-12 epsilons) is what evaluate() / frame_overlaps() use: the
+    yardstick of the *match* (tp / fp / fn, thresholds, AP), on splits that keep every overlap away from the minimum overlaps,
+    and of the device overlaps on boxes in general position (1e-12).  Its epsilons make it wrong by more than rounding for
+    edges that nearly touch or are nearly parallel, and its shoelace sum cancels like the device's.
+  * bev_intersection_exact (fractions.Fraction from the same float64 corners, convex clipping with exact sign tests, exact
+    shoelace, one rounding at the end) has no epsilons and no cancellation: the authority for the *value* of a BEV / 3-D overlap
+    wherever the two could differ -- touching, collinear, nearly parallel, nearly coincident, far from the origin.  Slow.
 """
 import math
+from fractions import Fraction
 
 CLASSES = ('Car', 'Pedestrian', 'Cyclist')
 DIFFICULTIES = ('easy', 'moderate', 'hard')
@@ -71,7 +81,12 @@ def _segment_crossing(p1, p2, q1, q2):
     t = (qp[0] * s[1] - qp[1] * s[0]) / den
     u = (qp[0] * r[1] - qp[1] * r[0]) / den
     if -1e-12 <= t <= 1 + 1e-12 and -1e-12 <= u <= 1 + 1e-12:
-        return (p1[0] + t * r[0], p1[1] + t * r[1])
+        x = (p1[0] + t * r[0], p1[1] + t * r[1])
+        # lines parallel but for rounding leave t and u without meaning (two edges end to end on one line would "cross" anywhere
+        # along it): the point, which lies on the first segment, counts only if its projection lies on the second as well
+        u = ((x[0] - q1[0]) * s[0] + (x[1] - q1[1]) * s[1]) / (s[0] * s[0] + s[1] * s[1])
+        if -1e-9 <= u <= 1 + 1e-9:
+            return x
     return None
 
 
@@ -102,14 +117,53 @@ def bev_intersection(a, b):
     return polygon_area(pts)
 
 
-def ground_overlap(d, g):
-    inter = bev_intersection(footprint(d), footprint(g))
+def _area2_exact(p):
+    return sum(p[k][0] * p[(k + 1) % len(p)][1] - p[(k + 1) % len(p)][0] * p[k][1] for k in range(len(p)))
+
+
+def bev_intersection_exact(a, b):
+    """Area of the intersection of two convex quadrilaterals given by float64 corners, in exact rational arithmetic: `a`
+    clipped by the four edge half-planes of `b` (closed: a vertex on an edge is inside), exact shoelace, rounded to float once.
+    Vertices repeated by touching edges add no area, so there is no degenerate case to treat."""
+    # a float64 is an integer over a power of two: on the common denominator `scale` the corners are integers, and only the
+    # crossing points are fractions
+    ratios = [float(v).as_integer_ratio() for p in list(a) + list(b) for v in p]
+    scale = max(d for _, d in ratios)
+    ints = [n * (scale // d) for n, d in ratios]
+    pa = [(ints[2 * k], ints[2 * k + 1]) for k in range(4)]
+    pb = [(ints[2 * k], ints[2 * k + 1]) for k in range(4, 8)]
+    ob = _area2_exact(pb)
+    if ob == 0 or _area2_exact(pa) == 0:
+        return 0.0
+    if ob < 0:
+        pb.reverse()                                # counter-clockwise: inside is left of every edge
+    poly = pa
+    for e in range(4):
+        p, q = pb[e], pb[(e + 1) % 4]
+        ex, ez = q[0] - p[0], q[1] - p[1]
+        side = [ex * (v[1] - p[1]) - ez * (v[0] - p[0]) for v in poly]
+        out = []
+        for k in range(len(poly)):
+            v, u, sv, su = poly[k], poly[k - 1], side[k], side[k - 1]
+            if (sv > 0 and su < 0) or (sv < 0 and su > 0):
+                t = Fraction(su) / (su - sv)
+                out.append((u[0] + t * (v[0] - u[0]), u[1] + t * (v[1] - u[1])))
+            if sv >= 0:
+                out.append(v)
+        poly = out
+        if len(poly) < 3:
+            return 0.0
+    return float(Fraction(abs(_area2_exact(poly))) / (2 * scale * scale))
+
+
+def ground_overlap(d, g, intersection=bev_intersection):
+    inter = intersection(footprint(d), footprint(g))
     den = d['l'] * d['w'] + g['l'] * g['w'] - inter
     return inter / den if den > 0 else 0.0
 
 
-def box3d_overlap(d, g):
-    inter = bev_intersection(footprint(d), footprint(g))
+def box3d_overlap(d, g, intersection=bev_intersection):
+    inter = intersection(footprint(d), footprint(g))
     ymax = min(d['y'], g['y'])
     ymin = max(d['y'] - d['h'], g['y'] - g['h'])
     inter_vol = inter * max(0.0, ymax - ymin)
@@ -117,6 +171,15 @@ def box3d_overlap(d, g):
     gt_vol = g['h'] * g['w'] * g['l']
     den = det_vol + gt_vol - inter_vol
     return inter_vol / den if den > 0 else 0.0
+
+
+def ground_and_box3d_overlap(d, g, intersection=bev_intersection):
+    """(ground_overlap, box3d_overlap) from one intersection: the same arithmetic as the two above."""
+    inter = intersection(footprint(d), footprint(g))
+    den = d['l'] * d['w'] + g['l'] * g['w'] - inter
+    inter_vol = inter * max(0.0, min(d['y'], g['y']) - max(d['y'] - d['h'], g['y'] - g['h']))
+    den3 = d['h'] * d['w'] * d['l'] + g['h'] * g['w'] * g['l'] - inter_vol
+    return (inter / den if den > 0 else 0.0), (inter_vol / den3 if den3 > 0 else 0.0)
 
 
 OVERLAP = {IMAGE: image_overlap, GROUND: ground_overlap, BOX3D: box3d_overlap}
@@ -329,11 +392,13 @@ def eval_class(gt_frames, det_frames, current_class, metric, difficulty, min_ove
             'fn': [p['fn'] for p in pr], 'precision': precision, 'aos': aos}
 
 
-def evaluate(gt_frames, det_frames, classes=CLASSES, overlap_sets=None):
-    """Same layout as stereo_rcnn_amd.kitti_eval.evaluate (class -> overlap key -> metric -> difficulty -> entry)."""
+def evaluate(gt_frames, det_frames, classes=CLASSES, overlap_sets=None, cache=None):
+    """Same layout as stereo_rcnn_amd.kitti_eval.evaluate (class -> overlap key -> metric -> difficulty -> entry).
+    cache: a dict that receives, and if already filled supplies, {metric: [frame_overlaps(g, d, metric) per frame]}, so that
+    a caller can look at the very overlaps the match used and need not pay for them twice."""
     sets = dict(DEFAULT_OVERLAPS)
     sets.update(overlap_sets or {})
-    cache = {}
+    cache = {} if cache is None else cache
     out = {}
     for cls in classes:
         if not any(str(d['type']).lower() == cls.lower() for det in det_frames for d in det):

@@ -13,42 +13,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kitti_eval_ref as ref                                    # noqa: E402
 from stereo_rcnn_amd import kitti_eval as ke                    # noqa: E402
+from kitti_synth import _jitter, _round, _row, assert_same_result   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIMS = {'Car': (1.5, 1.6, 3.9), 'Van': (2.2, 1.9, 5.0), 'Pedestrian': (1.75, 0.6, 0.8), 'Person_sitting': (1.2, 0.6, 0.9),
-        'Cyclist': (1.7, 0.6, 1.8)}
-
-
-def _row(rng, type_, height=None):
-    h2 = float(rng.choice([25.0, 40.0])) if height is None and rng.random() < 0.15 else (height or float(rng.uniform(15, 150)))
-    x1, y1 = float(rng.uniform(0, 1100)), float(rng.uniform(100, 220))
-    w2 = h2 * float(rng.uniform(0.4, 2.2))
-    h, w, l = (d * float(rng.uniform(0.9, 1.1)) for d in DIMS[type_])
-    return [type_, float(rng.choice([0.0, 0.1, 0.15, 0.2, 0.3, 0.45, 0.5, 0.7])), int(rng.integers(0, 4)),
-            float(rng.uniform(-math.pi, math.pi)), x1, y1, x1 + w2, y1 + h2, h, w, l,
-            float(rng.uniform(-15, 15)), float(rng.uniform(1.0, 2.5)), float(rng.uniform(5, 60)), float(rng.uniform(-math.pi, math.pi))]
-
-
-def _round(r, nd=2):
-    return [r[0], round(r[1], 2), r[2]] + [round(v, nd) for v in r[3:]]
-
-
-def _jitter(rng, r, s=1.0):
-    r = list(r)
-    for k in range(4, 8):
-        r[k] += float(rng.normal(0, 2.0 * s))
-    r[7] = max(r[7], r[5] + 1.0)
-    r[6] = max(r[6], r[4] + 1.0)
-    for k in (8, 9, 10):
-        r[k] *= float(rng.uniform(1 - 0.08 * s, 1 + 0.08 * s))
-    r[11] += float(rng.normal(0, 0.25 * s))
-    r[12] += float(rng.normal(0, 0.1 * s))
-    r[13] += float(rng.normal(0, 0.5 * s))
-    r[14] += float(rng.normal(0, 0.15 * s))
-    r[3] += float(rng.normal(0, 0.3))
-    return r
 
 
 def synthetic_split(seed, n_frames=200, max_obj=6):
@@ -292,7 +261,9 @@ def test_frame_over_the_detection_limit_is_an_error():
     g = np.array([tuple(_row(rng, 'Car'))], dtype=ke.LABEL_DTYPE)
     big = np.array([tuple(_row(rng, 'Car')) + (0.5,)] * (ke.MAX_DET_PER_FRAME + 1), dtype=ke.RESULT_DTYPE)
     ok = np.array([tuple(_row(rng, 'Car')) + (0.5,)] * ke.MAX_DET_PER_FRAME, dtype=ke.RESULT_DTYPE)
-    res = ke.evaluate([g, g], [ok[:3], ok])                              # exactly at the limit: evaluated
-    assert res['Car']['0.70, 0.70, 0.70']['bbox']['hard']['n_gt'] >= 0
+    res = ke.evaluate([g, g], [ok[:3], ok])                              # exactly at the limit: evaluated, and right
+    assert_same_result(res, ref.evaluate([g, g], [ok[:3], ok]))          # (no detection lies on g: no threshold anywhere)
+    on = np.array([tuple(g[0]) + (0.5,)] * ke.MAX_DET_PER_FRAME, dtype=ke.RESULT_DTYPE)      # ... and with every one on it
+    assert assert_same_result(ke.evaluate([g, g], [on[:3], on]), ref.evaluate([g, g], [on[:3], on])) > 0
     with pytest.raises(RuntimeError, match='4096'):
         ke.evaluate([g, g], [ok[:3], big])
