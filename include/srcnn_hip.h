@@ -15,7 +15,7 @@
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*;
  *     NULL = the null stream) and is hipGraph-capturable;
  *   - return value: 0 = SRCNN_OK, negative = error (srcnn_last_error() gives
- *     text).  The two legacy-named wrappers keep the reference's "1 = ok,
+ *     text).  The legacy-named wrappers keep the reference's "1 = ok,
  *     0 = bad roi shape" convention (roi_align_cuda.c:19-22,39; nms_cuda.c:18).
  *   - activations are NHWC float32 inside the library; NCHW only at the edge.
  */
@@ -95,6 +95,49 @@ SRCNN_API int srcnn_pyramid_roi_align(const float *const *maps_host, const int *
                             int channels, float im_height, const float *rois, int num_rois, int A,
                             float *out, int out_cstride, int out_coffset, int maps_format, int out_format,
                             const int *roi_limit, srcnn_stream_t stream);
+/* ------------------------------------------------- ROIAlign backward (training: the gradient with respect to the maps)
+ * Replaces  int roi_align_backward_cuda(int aligned_height, int aligned_width, float spatial_scale,
+ *                 THCudaTensor *top_grad, THCudaTensor *rois, THCudaTensor *bottom_grad)
+ *           lib/model/roi_align/src/roi_align_cuda.h:4-5, roi_align_cuda.c:42-76, kernel roi_align_kernel.cu:94-162.
+ * top_grad (n,C,ah,aw), rois (n, roi_cols), bottom_grad (B,C,H,W) NCHW.  Returns 1 on success, 0 when roi_cols != 5
+ * (bottom_grad untouched; checked before any launch) -- reference convention.
+ * DEFINED SUMMATION ORDER.  The reference scatters with float atomicAdd, so its result depends on arrival order; here every
+ * map element is gathered: the float32 sum, starting from 0, of its contributions in ascending (roi index, ph, pw) order
+ * (the four taps of one lattice point always fall on four different elements), each element written exactly once, no
+ * atomics: results are run-to-run bit-equal.  One contribution of lattice point (n, c, ph, pw) with gradient g is the
+ * reference's expression with C++'s promotions (roi_align_kernel.cu:137-140: `1.` is a double, `1 - w_ratio` a float):
+ *   up-left    (float)((double)g * (1. - (double)h_ratio) * (double)(1.f - w_ratio))
+ *   up-right   (float)((double)g * (1. - (double)h_ratio) * (double)w_ratio)
+ *   down-left  (g * h_ratio) * (1.f - w_ratio)            down-right  (g * h_ratio) * w_ratio          (float products)
+ * with the forward's geometry, outside-the-map test and hstart / wstart clamps.
+ * OVERWRITE, NOT ACCUMULATE: on success bottom_grad is overwritten with the gradient (zeros where no roi reaches; no
+ * zero fill is needed before the call).  The reference accumulates into bottom_grad, and its only caller passes a tensor
+ * it has just zeroed (functions/roi_align.py:38-39): for that caller the two are the same.  A roi whose truncated batch
+ * index (int)rois[n][0] lies outside [0, batch) contributes nothing (the reference would write outside the tensor). */
+SRCNN_API int roi_align_backward_cuda(int aligned_height, int aligned_width, float spatial_scale,
+                            const float *top_grad, const float *rois, int num_rois, int roi_cols,
+                            float *bottom_grad, int batch, int channels, int height, int width,
+                            srcnn_stream_t stream);
+/* Adjoint of srcnn_pool2x2_s1: grad_y (planes, h-1, w-1) -> grad_x (planes, h, w), every element written.
+ * take_max 0: a lattice point receives ((g00 + g01) + g10) + g11 over the (up to four) outputs that read it, taken in
+ * row-major order of the outputs starting with the first that exists, x 0.25f; x may be NULL.
+ * take_max 1: each output's gradient goes to the one lattice point torch.nn.functional.max_pool2d picks on the CPU
+ * (first maximum in row-major window order; a NaN wins, the last one of several); a point picked by several outputs
+ * adds them in the same row-major order; x is the forward's input (planes, h, w). */
+SRCNN_API int srcnn_pool2x2_s1_backward(const float *grad_y, const float *x, long long planes, int h, int w, float *grad_x,
+                              int take_max, srcnn_stream_t stream);
+/* Adjoint of srcnn_pyramid_roi_align with respect to the four maps.  grad_out is (n, A, A, out_cstride) NHWC and channels
+ * [out_coffset, out_coffset+C) are read (both multiples of 4); rois, A, im_height, roi_limit and the level routing as in
+ * the forward.  grad_maps[l] is (batch, mh[l], mw[l], C) NHWC, maps_format must be SRCNN_FMT_F32 (anything else is an
+ * error), and every element of every level is written (zeros where no roi reaches): one launch over the tiles of all
+ * four levels.  The 2x2 average is folded in -- the lattice gradient of a point is ((g00 + g01) + g10) + g11 over the
+ * outputs that exist, row-major, x 0.25f, formed in registers -- and the map sums follow roi_align_backward_cuda's
+ * order, so the result is bit-equal to srcnn_pool2x2_s1_backward (average) followed by roi_align_backward_cuda on each
+ * level's rois. */
+SRCNN_API int srcnn_pyramid_roi_align_backward(const float *grad_out, int out_cstride, int out_coffset, const float *rois,
+                                     int num_rois, int A, int channels, float im_height, float *const *grad_maps_host,
+                                     const int *mh_host, const int *mw_host, int batch, int maps_format,
+                                     const int *roi_limit, srcnn_stream_t stream);
 /* format conversion of an NHWC activation tensor (pixels x C): F32 <-> SPLIT16 (API edge / tests) */
 SRCNN_API int srcnn_act_convert(const void *x, int x_format, void *y, int y_format, long long pixels, int C,
                       srcnn_stream_t stream);

@@ -72,6 +72,12 @@ _SIGNATURES = {
                                         c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p]),
     "srcnn_pool2x2_s1": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "roi_align_backward_cuda": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_void_p]),
+    "srcnn_pool2x2_s1_backward": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "srcnn_pyramid_roi_align_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
+                                                 ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                                                 c_int, c_void_p, c_void_p]),
     "srcnn_act_convert": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
     "srcnn_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "srcnn_decode_kept_kpts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,

@@ -15,39 +15,20 @@
 // The float/double promotion pattern of the reference kernel (its `1.` literals) is
 // reproduced operation by operation; the library is built with -ffp-contract=off.
 #include "conv_common.h"
+#include "roi_align_geom.h"
 #include <cstdlib>
 
 namespace srcnn {
-
-struct RoiGeom {
-    float start_w, start_h, bin_w, bin_h;
-    int batch;
-};
-
-__device__ __forceinline__ RoiGeom roi_geom(const float *r, float scale, int ah, int aw)
-{
-    RoiGeom g;
-    g.batch = (int)r[0];
-    g.start_w = r[1] * scale;
-    g.start_h = r[2] * scale;
-    float end_w = r[3] * scale;
-    float end_h = r[4] * scale;
-    float roi_w = fmaxf((float)((double)(end_w - g.start_w) + 1.), 0.0f);   // roi_align_kernel.cu:40
-    float roi_h = fmaxf((float)((double)(end_h - g.start_h) + 1.), 0.0f);   // :41
-    g.bin_h = (float)((double)roi_h / ((double)ah - 1.));                   // :42
-    g.bin_w = (float)((double)roi_w / ((double)aw - 1.));                   // :43
-    return g;
-}
 
 // value of one lattice point; `at(y, x)` fetches the feature value
 template <typename Fetch>
 __device__ __forceinline__ float lattice_point(float h, float w, int height, int width, Fetch at)
 {
-    if (h < 0 || h >= height || w < 0 || w >= width) return 0.0f;           // :54-55
-    int hstart = (int)fminf(floorf(h), (float)(height - 2));                 // :48
-    int wstart = (int)fminf(floorf(w), (float)(width - 2));                  // :49
-    float h_ratio = h - (float)hstart;
-    float w_ratio = w - (float)wstart;
+    int hstart, wstart;
+    float h_ratio, w_ratio;
+    const bool h_ok = lattice_axis(h, height, hstart, h_ratio);
+    const bool w_ok = lattice_axis(w, width, wstart, w_ratio);
+    if (!h_ok || !w_ok) return 0.0f;                                         // :54-55
     // :64-67 with C++'s usual arithmetic conversions, left to right: `1.` is a double, so the first two terms are double
     // products; `down * h_ratio` is float x float (rounded to float) before it meets a double, and the last term is a
     // float product throughout.  (Checked against the reference's own kernel built for gfx950: tests/test_ref_kernels_gpu.py.)
@@ -97,13 +78,7 @@ __global__ void pyramid_roi_align_kernel(PyramidArgs pa, int channels, const flo
     const int n = blockIdx.y, py = blockIdx.x, c = threadIdx.x;
     if (pa.roi_limit && n >= *pa.roi_limit) return;
     const float *r = rois + (size_t)n * 5;
-    // level routing, stereo_rcnn.py:113-119 (natural log; round half away from zero; clamp 2..5)
-    float bh = r[4] - r[2] + 1.0f;
-    float bw = r[3] - r[1] + 1.0f;
-    float lv = logf(sqrtf(bh * bw) / 224.0f) + 4.0f;
-    lv = copysignf(floorf(fabsf(lv) + 0.5f), lv);
-    lv = fminf(fmaxf(lv, 2.0f), 5.0f);
-    const int l = __builtin_amdgcn_readfirstlane((int)lv - 2);   // same roi for the whole block
+    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
     const int height = pa.mh[l], width = pa.mw[l];
     RoiGeom g = roi_geom(r, pa.scale[l], A + 1, A + 1);
     const float *base = pa.maps[l];
@@ -167,13 +142,7 @@ __global__ void pyramid_roi_align8_kernel(PyramidArgs pa, int channels, const fl
     const int n = blockIdx.y, py = blockIdx.x * blockDim.y + threadIdx.y, g = threadIdx.x;
     if (py >= A || (pa.roi_limit && n >= *pa.roi_limit)) return;
     const float *r = rois + (size_t)n * 5;
-    // level routing, stereo_rcnn.py:113-119 (natural log; round half away from zero; clamp 2..5)
-    float bh = r[4] - r[2] + 1.0f;
-    float bw = r[3] - r[1] + 1.0f;
-    float lv = logf(sqrtf(bh * bw) / 224.0f) + 4.0f;
-    lv = copysignf(floorf(fabsf(lv) + 0.5f), lv);
-    lv = fminf(fmaxf(lv, 2.0f), 5.0f);
-    const int l = __builtin_amdgcn_readfirstlane((int)lv - 2);   // same roi for the whole block
+    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
     const int height = pa.mh[l], width = pa.mw[l];
     const RoiGeom geo = roi_geom(r, pa.scale[l], A + 1, A + 1);
     const float *base = pa.maps[l];
@@ -225,13 +194,7 @@ __global__ __launch_bounds__(32 * (A + 1)) void pyramid_roi_align8_roi_kernel(Py
     const int n = blockIdx.x, ry = threadIdx.y, g = threadIdx.x;
     if (pa.roi_limit && n >= *pa.roi_limit) return;             // (uniform: the whole workgroup leaves)
     const float *r = rois + (size_t)n * 5;
-    // level routing, stereo_rcnn.py:113-119 (natural log; round half away from zero; clamp 2..5)
-    float bh = r[4] - r[2] + 1.0f;
-    float bw = r[3] - r[1] + 1.0f;
-    float lv = logf(sqrtf(bh * bw) / 224.0f) + 4.0f;
-    lv = copysignf(floorf(fabsf(lv) + 0.5f), lv);
-    lv = fminf(fmaxf(lv, 2.0f), 5.0f);
-    const int l = __builtin_amdgcn_readfirstlane((int)lv - 2);   // same roi for the whole block
+    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
     const int height = pa.mh[l], width = pa.mw[l];
     const RoiGeom geo = roi_geom(r, pa.scale[l], A + 1, A + 1);
     const float *base = pa.maps[l];

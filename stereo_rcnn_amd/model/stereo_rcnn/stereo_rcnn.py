@@ -17,6 +17,45 @@ from ..utils.config import cfg
 from .plan import Plan, Weights
 
 
+def _pyramid_roi_feat(feat_maps, rois, im_height, A):
+    maps = [engine.nchw_to_nhwc(m.contiguous().float()) for m in feat_maps]
+    C = int(feat_maps[0].shape[1])
+    n = int(rois.shape[0])
+    out = torch.empty((n, A, A, C), device=rois.device)
+    ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
+    mh = (ctypes.c_int * 4)(*[int(m.shape[1]) for m in maps])
+    mw = (ctypes.c_int * 4)(*[int(m.shape[2]) for m in maps])
+    _lib.check(_lib.lib().srcnn_pyramid_roi_align(ptrs, mh, mw, C, im_height, rois.data_ptr(), n, A,
+                                                  out.data_ptr(), C, 0, _lib.FMT_F32, _lib.FMT_F32, None,
+                                                  _lib.stream()), "srcnn_pyramid_roi_align")
+    return engine.nhwc_to_nchw(out)
+
+
+class _PyramidRoIFeat(torch.autograd.Function):
+    """PyramidRoI_Feat with its adjoint with respect to the four maps (NCHW at the edge, NHWC inside)."""
+
+    @staticmethod
+    def forward(ctx, rois, im_height, A, *feat_maps):
+        ctx.save_for_backward(rois)
+        ctx.geometry = (im_height, A, [tuple(m.shape) for m in feat_maps])
+        return _pyramid_roi_feat(feat_maps, rois, im_height, A)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rois, = ctx.saved_tensors
+        im_height, A, shapes = ctx.geometry
+        C = shapes[0][1]
+        g = engine.nchw_to_nhwc(grad_out.contiguous().float())            # (n, A, A, C)
+        grads = [torch.empty((b, h, w, c), dtype=torch.float32, device=g.device) for b, c, h, w in shapes]
+        ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in grads])
+        mh = (ctypes.c_int * 4)(*[s[2] for s in shapes])
+        mw = (ctypes.c_int * 4)(*[s[3] for s in shapes])
+        _lib.check(_lib.lib().srcnn_pyramid_roi_align_backward(g.data_ptr(), C, 0, rois.data_ptr(), int(rois.shape[0]), A, C,
+                                                               im_height, ptrs, mh, mw, shapes[0][0], _lib.FMT_F32, None,
+                                                               _lib.stream()), "srcnn_pyramid_roi_align_backward")
+        return (None, None, None) + tuple(engine.nhwc_to_nchw(t) for t in grads)
+
+
 class _StereoRCNN(nn.Module):
     """ FPN-based Stereo R-CNN, eval mode only (the training branch of the reference,
     stereo_rcnn.py:198-230,273-311, is out of scope). """
@@ -122,25 +161,21 @@ class _StereoRCNN(nn.Module):
     def PyramidRoI_Feat(self, feat_maps, rois, im_info, kpts=False, single_level=None):
         """stereo_rcnn.py:110-139 with the reference's NCHW in / NCHW out contract.
         feat_maps: 4 NCHW maps (P2..P5); rois (n,5).  One fused native call (level routing,
-        lattice sampling, 2x2 average) instead of the per-level Python loop."""
-        maps = [engine.nchw_to_nhwc(m.contiguous().float()) for m in feat_maps]
-        C = int(feat_maps[0].shape[1])
+        lattice sampling, 2x2 average) instead of the per-level Python loop.  Differentiable with respect to the four
+        maps (srcnn_pyramid_roi_align_backward) when grad mode is on and one of them requires grad."""
         A = cfg.POOLING_SIZE * 2 if kpts else cfg.POOLING_SIZE
-        n = int(rois.shape[0])
-        rois = rois.contiguous().float()
-        out = torch.empty((n, A, A, C), device=rois.device)
-        ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
-        mh = (ctypes.c_int * 4)(*[int(m.shape[1]) for m in maps])
-        mw = (ctypes.c_int * 4)(*[int(m.shape[2]) for m in maps])
-        _lib.check(_lib.lib().srcnn_pyramid_roi_align(ptrs, mh, mw, C, float(im_info[0][0]), rois.data_ptr(), n, A,
-                                                      out.data_ptr(), C, 0, _lib.FMT_F32, _lib.FMT_F32, None,
-                                                      _lib.stream()), "srcnn_pyramid_roi_align")
-        return engine.nhwc_to_nchw(out)
+        im_height = float(im_info[0][0])
+        rois = rois.detach().contiguous().float()
+        if torch.is_grad_enabled() and any(m.requires_grad for m in feat_maps):
+            return _PyramidRoIFeat.apply(rois, im_height, A, *feat_maps)
+        return _pyramid_roi_feat(feat_maps, rois, im_height, A)
 
     def forward(self, im_left_data, im_right_data, im_info, gt_boxes_left=None, gt_boxes_right=None,
                 gt_boxes_merge=None, gt_dim_orien=None, gt_kpts=None, num_boxes=None, slot=0, kpts=True, alias_outputs=None):
         """Reference signature and 15-tuple return (stereo_rcnn.py:141-142,322-324).
-        The gt_* / num_boxes arguments are accepted and ignored exactly as in eval mode.
+        The gt_* / num_boxes arguments are accepted and ignored exactly as in eval mode: this forward (plans, SPLIT16, launch
+        programs) is inference-only and returns tensors without a grad_fn.  The differentiable pieces for fine-tuning heads on
+        top of the library are the ROIAlign modules and `PyramidRoI_Feat`.
         `slot` (extension): independent buffer set, so that several pairs can be in flight on different HIP
         streams (each stream uses its own slot).
         `kpts=False` (extension, stereo_rcnn_amd.pipeline): leave the keypoint branch out of the forward -- the three keypoint
