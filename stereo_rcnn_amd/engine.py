@@ -5,6 +5,7 @@ at load time, and one function per native op that fills the C descriptor and lau
 torch's current stream.  No arithmetic happens here.
 """
 import ctypes
+import os as _os
 
 import torch
 
@@ -177,7 +178,6 @@ _CANDIDATES_F16S = [(4, 4, 8, 2), (4, 2, 8, 3), (2, 2, 8, 4), (2, 2, 8, 2), (2, 
 # Largest LDS footprint (KB per workgroup) a tuned plan may have.  Isolated-launch timing always favours the deepest ring /
 # biggest tile (up to 144 KB: one workgroup per CU, nothing else fits beside it); with several pairs in flight a smaller
 # footprint lets workgroups of OTHER launches share the CU and fill the matrix pipe's idle slots (profiles/lds_cap_r03.txt).
-import os as _os
 MAX_LDS_KB = int(_os.environ.get('SRCNN_MAX_LDS_KB', '160'))
 
 
@@ -207,6 +207,19 @@ RPN_GROUP_TILE = tuple(int(c) for c in _os.environ.get('SRCNN_RPN_GROUP_TILE', '
 # bandwidth, and the four bilinear taps lengthen the epilogue of a launch whose workgroups hold the matrix pipe's LDS.
 UPSAMPLE_FUSION = _os.environ.get('SRCNN_UPSAMPLE_FUSION', '0') != '0'
 
+# ---- chained bottleneck launches (csrc/conv_chain.hip: srcnn_conv2d_chain): [conv2 -> conv3 -> conv1 of the next block] as ONE launch
+# whose workgroups keep their rows through the three convolutions.  BOTTLENECK_CHAIN: '0' (default) = off, '1' = on, 'auto' = on while
+# several forwards are in flight.  Built, bit-identical (tests/test_conv_chain_gpu.py), measured, and NOT the default: the headline
+# step is the same with and without it (profiles/chain_ab_r06.txt: 6.35-6.39 ms off, 6.35-6.41 ms with layer1 / layer2 / layer3
+# chained on their best tiles, at 3, 4, 6 and 8 forwards in flight) -- the intermediates come back through the fabric all the
+# same (a layer3 block's weights alone are 4.4 MB, the XCD's whole L2), and the package power limit prices the step by its
+# MFMA work, which a chain does not change (DESIGN 8).  It removes 46 launches per forward.
+BOTTLENECK_CHAIN = _os.environ.get('SRCNN_BOTTLENECK_CHAIN', '0')
+# planes of the bottleneck (64, 128, 256, 512) -> (tile_mr, waves, stages, narrow nr, wide nr) or None = that layer keeps its
+# separate launches.  layer4 (M = 2394: 10 workgroups of 256 rows) stays unchained.
+CHAIN_TILES = {64: (2, 4, 2, 1, 1), 128: (4, 8, 3, 2, 2), 256: (4, 8, 3, 2, 2), 512: None}
+CHAIN_MIN_WGS = 32        # a chain launch with fewer workgroups than this is not worth its latency
+
 
 # ---- what the tuner minimises.  'isolated': the latency of the launch alone on the chip (the right objective for one pair at a
 # time).  'concurrent': the time per launch while TUNE_STREAMS copies of the launch run on as many HIP streams -- the regime of
@@ -217,21 +230,7 @@ UPSAMPLE_FUSION = _os.environ.get('SRCNN_UPSAMPLE_FUSION', '0') != '0'
 TUNE_MODE = _os.environ.get('SRCNN_TUNE_MODE', 'isolated')
 TUNE_STREAMS = int(_os.environ.get('SRCNN_TUNE_STREAMS', '3'))
 _tune_side_streams = {}
-
-
-def set_tune_mode(mode, streams=None):
-    """'isolated' or 'concurrent' (see above).  Plans recorded into launch programs under the other mode are dropped by
-    Plan.run (the mode is part of its epoch)."""
-    global TUNE_MODE, TUNE_STREAMS
-    assert mode in ('isolated', 'concurrent')
-    TUNE_MODE = mode
-    if streams is not None:
-        TUNE_STREAMS = int(streams)
-
-
-def tune_mode_key():
-    return ('conc', TUNE_STREAMS) if TUNE_MODE == 'concurrent' and TUNE_STREAMS > 1 else ()
-
+_tune_flag = None          # scratch word that takes the range-guard reports of the tuner's trial launches (_tune)
 
 # Measurement hook (mix_table.py): [(compiled regex, n)] -- a conv launch whose layer name matches is issued n MORE times right
 # behind itself (same arguments: the output is simply rewritten).  The step-time increase per extra launch is that layer's
@@ -248,6 +247,20 @@ DEBUG_SKIP = frozenset()
 # every Plan compares it in run() and re-records.  KEY_HITS: while a dict, conv2d counts the launches per plan key.
 PLAN_EPOCH = 0
 KEY_HITS = None
+
+
+def set_tune_mode(mode, streams=None):
+    """'isolated' or 'concurrent' (see above).  Plans recorded into launch programs under the other mode are dropped by
+    Plan.run (the mode is part of its epoch)."""
+    global TUNE_MODE, TUNE_STREAMS
+    assert mode in ('isolated', 'concurrent')
+    TUNE_MODE = mode
+    if streams is not None:
+        TUNE_STREAMS = int(streams)
+
+
+def tune_mode_key():
+    return ('conc', TUNE_STREAMS) if TUNE_MODE == 'concurrent' and TUNE_STREAMS > 1 else ()
 
 
 def set_plan(key, plan):
@@ -288,37 +301,44 @@ def _set_plan(d, plan):
     d.tile_mr, d.tile_nr, d.tile_waves, d.tile_stages, d.splits = plan
 
 
-def _tune(d, key, device, only=None):
-    """Times each candidate plan with HIP events on the current stream: three interleaved passes, then a play-off.
-    only: the (mr, nr, waves, stages) tiles to choose from, unsplit (launches with an MFMA-form fused head)."""
-    L = _lib.lib()
+def _candidate_plans(d, only=None):
+    """The plans (mr, nr, waves, stages, splits) _tune times for the launch d describes, in trial order.
+    only: the (mr, nr, waves, stages) tiles to choose from, unsplit (launches with an MFMA-form fused head).  Of the shape rules
+    below they obey their own alone -- no 256-row tile for fewer than four of them, but never an empty choice -- and the LDS cap."""
     M = d.B * d.OH * d.OW
+    if only is not None:
+        tiles = [t for t in only if not (t[0] >= 4 and M < 256 * 4)] or list(only)[-1:]
+        return [tuple(t) + (1,) for t in tiles if plan_lds_kb(*t) <= MAX_LDS_KB]
     nkt = (d.KH * d.KW * d.Cin + d.Cin2) // 32
-    cands = []
+    fused_in = d.x2 or d.up_top            # a second input / the top-down addition: never split-K, never the 256x256 tile
     tiles = list(_CANDIDATES)
     if d.precision == 1 and d.x_format == 1:
         tiles = _CANDIDATES_F16S + tiles
-    if only is not None:
-        tiles = [t for t in only if not (t[0] >= 4 and M < 256 * 4)]or list(only)[-1:]
+    cands = []
     for mr, nr, waves, stages in tiles:
         if plan_lds_kb(mr, nr, waves, stages) > MAX_LDS_KB:
             continue
-        if nr == 2 and d.Cout <= 64 and only is None:
+        if nr == 2 and d.Cout <= 64:
             continue
         # the 256x256 tile: not with a second input (register budget); few fat workgroups lose the latency contest of this tuner on the
         # small-M layers but can win the several-in-flight step (tune.tune_throughput takes its candidates from this log)
-        if nr == 4 and only is None and (d.Cout <= 128 or M < 256 * 8 or d.x2 or d.up_top):
+        if nr == 4 and (d.Cout <= 128 or M < 256 * 8 or fused_in):
             continue
-        if mr >= 2 and M <= 64 * (mr // 2) and only is None:
+        if mr >= 2 and M <= 64 * (mr // 2):
             continue
         blocks = -(-M // (64 * mr)) * -(-d.Cout // (64 * nr))
-        splits = [1]
-        if d.mode != 1 and not d.x2 and not d.up_top and only is None:
-            for s in (2, 3, 4, 6, 8, 12, 16):
-                if blocks * s <= 4096 and nkt // s >= 4 and blocks < 1024:
-                    splits.append(s)
-        for s in splits:
-            cands.append((mr, nr, waves, stages, s))
+        cands.append((mr, nr, waves, stages, 1))
+        if d.mode != 1 and not fused_in:
+            cands += [(mr, nr, waves, stages, s) for s in (2, 3, 4, 6, 8, 12, 16)
+                      if blocks * s <= 4096 and nkt // s >= 4 and blocks < 1024]
+    return cands
+
+
+def _tune(d, key, device, only=None):
+    """Times each candidate plan with HIP events on the current stream: three interleaved passes, then a play-off.
+    only: see _candidate_plans."""
+    L = _lib.lib()
+    cands = _candidate_plans(d, only)
     log = _TUNE_LOG.setdefault(key, [])
     del log[:]
     st = _lib.stream()
@@ -333,9 +353,6 @@ def _tune(d, key, device, only=None):
         return _tune_candidates(d, key, device, cands, log, L, st)
     finally:
         L.srcnn_range_flag_bind(bound)
-
-
-_tune_flag = None
 
 
 def _tune_candidates(d, key, device, cands, log, L, st):
@@ -401,6 +418,105 @@ def _tune_candidates(d, key, device, cands, log, L, st):
     best = min(finalists, key=best_of.get)
     _TUNED[key] = best
     return best
+
+
+def conv_cost(cw, B, H, W, OH, OW, residual=False, up=None, head=False, head2=None, first_in_chain=True, grouped=False):
+    """What FlopCounter books for one convolution: (flops, bytes, M, N, K).  A pure function of the shape and the options conv2d
+    takes (residual / head: whether there is one; up, head2: conv2d's tuples).  Algorithmic flops 2 M N K with the true K, and
+    compulsory bytes at 4 per element (see FlopCounter), by these rules:
+    - a 1x1 convolution reads only the pixels it samples (M of them, whatever its stride); any other kernel reads the whole input;
+    - a later phase of a chain (first_in_chain=False) reads what its workgroup has just written: its input is not counted.  Its
+      weights, second input, residual and output are;
+    - a fused head adds its own flops, and its output replaces y (not written): 6 channels per tap for the fp32-FMA head; for the
+      MFMA head its channels per tap, once (final) or once per 256 conv channels (partial sums);
+    - a deconvolution (mode 1) is 4 taps of Cout / 4 channels each;
+    - a problem of a grouped launch is counted as the plain convolution the RPN levels are: one input, one tap per pixel, no
+      top-down addition."""
+    M = B * OH * OW
+    taps = 4 if cw.mode == 1 and not grouped else 1
+    px_in = M if (cw.kh == 1 and cw.kw == 1) else B * H * W
+    flops = 2.0 * M * cw.cout * cw.alg_k
+    nbytes = 4.0 * ((px_in * cw.cin if first_in_chain else 0) + (0 if grouped else M * cw.cin2) + cw.cout * cw.alg_k
+                    + M * cw.cout * (2 if residual else 1) + (B * up[1] * up[2] * cw.cout if up is not None and not grouped else 0))
+    if head2 is not None:
+        hn = head2[0].cout
+        flops += 2.0 * M * hn * cw.cout
+        nbytes += 4.0 * M * (taps * hn * (max(1, cw.cout // 256) if head2[2] else 1) - cw.cout)
+    if head:
+        flops += 2.0 * M * taps * 6 * (cw.cout // taps)
+        nbytes += 4.0 * M * (taps * 6 - cw.cout)
+    return flops, nbytes, M, cw.cout, cw.alg_k
+
+
+def _book(name, flops, nbytes, M, N, K, plan, **extra):
+    """Books one launch into FlopCounter: the totals, and its row (extra: the 'chain' / 'group' key of a fused launch)."""
+    if FlopCounter.enabled:
+        FlopCounter.flops += flops
+        FlopCounter.bytes += nbytes
+        FlopCounter.launches += 1
+        if FlopCounter.rows is not None:
+            FlopCounter.rows.append(dict({'name': name, 'M': M, 'N': N, 'K': K, 'flops': flops, 'bytes': nbytes, 'plan': plan}, **extra))
+
+
+def _plan_key(cw, d, precision, lim):
+    """The _TUNED key of the launch d describes (lim: m_limit_mul of a row-limited launch, else None).  A launch with an MFMA-form
+    head is keyed by the head's rows alone."""
+    if d.head_wf:
+        opts = ('head2', d.head_rows)
+    else:
+        opts = ((('lim', lim) if lim is not None else ()) + (('x2', cw.cin2, cw.stride2, d.H2, d.W2) if d.x2 else ())
+                + (('up',) if d.up_top else ()))
+    return _shape_key(cw, d.B, d.H, d.W, d.OH, d.OW, d.x_cstride, precision, (d.x_format, d.y_format, d.res_format) + opts + tune_mode_key())
+
+
+def _choose_plan(d, cw, precision, device, plan=None, lim=None):
+    """The plan (tile_mr, tile_nr, waves, stages, splits) for the launch the filled descriptor d describes; (0, 0, 0, 0, 0) leaves the
+    choice to the library's heuristic.  plan: the caller's explicit plan, if any (tests, tools, fused launches).  lim: m_limit_mul of
+    a row-limited launch -- the limit itself is not in d yet, the tuner puts its own there."""
+    if d.up_top and plan is not None and tuple(plan) != (0, 0, 0, 0, 0):
+        # the addition lives in the conv kernel's epilogue of every tile but 256x256, never in the split-K reduction: an explicit
+        # plan is rewritten here (not silently replaced by the library's heuristic), so that the returned plan is the one that ran
+        plan = ((4, 2, 8, 3) if tuple(plan[:2]) == (4, 4) else tuple(plan[:4])) + (1,)
+    if d.head_w:                          # the fp32-FMA fused head lives in the 256x256 tile, whatever was asked for
+        return (4, 4, 8, 2, 1)
+    if plan is not None:                  # explicit
+        return tuple(plan)
+    if not AUTOTUNE:
+        return (0, 0, 0, 0, 0)
+    if d.head_wf and not d.head_parts:    # final MFMA head: the 256x256 tile owns the pixel's channels -- nothing to tune
+        return (4, 4, 8, 2, 1)
+    key = _plan_key(cw, d, precision, lim)
+    if KEY_HITS is not None:
+        KEY_HITS[key] = KEY_HITS.get(key, 0) + 1
+    plan = _TUNED.get(key)
+    if plan is not None:
+        return plan
+    # never time inside a graph capture / program recording; warm-up runs tune first
+    recording = torch.cuda.is_current_stream_capturing() or _lib.lib().srcnn_program_recording()
+    if d.head_wf:                         # partial MFMA head: the 256x256 or the 128x128 8-wave tile
+        if recording:
+            return (4, 4, 8, 2, 1) if d.B * d.OH * d.OW >= 2048 else (2, 2, 8, 2, 1)
+        return _tune(d, key, device, only=[(4, 4, 8, 2), (2, 2, 8, 2)])
+    if recording:
+        return (0, 0, 0, 0, 0)
+    if lim is not None:
+        # a launch with a device-side row limit is tuned WITH a typical limit (LIMIT_TUNE_ROIS of its units): what is fastest for
+        # the whole shape (the biggest tile, one round of CUs) is not what is fastest for a fifth of it
+        typical = torch.tensor([LIMIT_TUNE_ROIS], dtype=torch.int32, device=device)
+        d.m_limit, d.m_limit_mul = typical.data_ptr(), int(lim)
+    plan = _tune(d, key, device)
+    d.m_limit, d.m_limit_mul = None, 0
+    return plan
+
+
+def _issue(launch, what, name):
+    """Issues a launch -- launch() calls the library and returns its status -- and the extra copies REPEAT asks for."""
+    _lib.check(launch(), what)
+    if REPEAT and name:
+        for rx, n in REPEAT:
+            if rx.match(name):
+                for _ in range(n):
+                    _lib.check(launch(), what + "(repeat)")
 
 
 def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=0, residual=None,
@@ -482,105 +598,20 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
         top, th, tw, top_fmt = up
         assert precision == 'f16x3' and x_fmt == _lib.FMT_SPLIT16 and residual is None and head is None and head2 is None and cw.mode == 0
         d.up_top, d.up_format, d.up_H, d.up_W = top.data_ptr(), int(top_fmt), int(th), int(tw)
-        if plan is not None and tuple(plan) != (0, 0, 0, 0, 0):
-            # the addition lives in the conv kernel's epilogue of every tile but 256x256, never in the split-K reduction: an explicit
-            # plan is rewritten here (not silently replaced by the library's heuristic), so that the returned plan is the one that ran
-            plan = ((4, 2, 8, 3) if tuple(plan[:2]) == (4, 4) else tuple(plan[:4])) + (1,)
     if desc_only:
         assert plan is not None and head is None and m_limit is None
-        _set_plan(d, plan)
+    _set_plan(d, _choose_plan(d, cw, precision, x.device, plan, m_limit_mul if m_limit is not None else None))
+    if desc_only:
         return d
-    if FlopCounter.enabled:
-        FlopCounter.flops += 2.0 * B * OH * OW * cw.cout * cw.alg_k
-        FlopCounter.launches += 1
-        px_in = B * OH * OW if (cw.kh == 1 and cw.kw == 1) else B * H * W
-        nbytes = 4.0 * (px_in * cw.cin + B * OH * OW * cw.cin2 + cw.cout * cw.alg_k + B * OH * OW * cw.cout * (2 if residual is not None else 1)
-                        + (B * up[1] * up[2] * cw.cout if up is not None else 0))
-        FlopCounter.bytes += nbytes
-        if FlopCounter.rows is not None:
-            FlopCounter.rows.append({'name': name or 'conv %dx%d %d->%d' % (cw.kh, cw.kw, cw.cin, cw.cout), 'M': B * OH * OW,
-                                     'N': cw.cout, 'K': cw.alg_k, 'flops': 2.0 * B * OH * OW * cw.cout * cw.alg_k, 'bytes': nbytes})
-    if head2 is not None and FlopCounter.enabled:
-        # the head's own flops; its output (final: hn floats per pixel; partial: one plane per 256 conv channels) instead of y
-        hn, taps = head2[0].cout, (4 if cw.mode == 1 else 1)
-        fl = 2.0 * B * OH * OW * hn * cw.cout                       # (mode 1: 4 taps x Cout / 4 channels each)
-        out_b = 4.0 * B * OH * OW * (taps * hn * (max(1, cw.cout // 256) if head2[2] else 1) - cw.cout)
-        FlopCounter.flops += fl
-        FlopCounter.bytes += out_b
-        if FlopCounter.rows is not None:
-            FlopCounter.rows[-1]['flops'] += fl
-            FlopCounter.rows[-1]['bytes'] = nbytes + out_b
-    if head2 is not None and plan is None and AUTOTUNE:
-        # final form: the 256x256 tile owns the pixel's channels -- nothing to tune; partial form: that or the 128x128 8-wave tile
-        if not head2[2]:
-            plan = (4, 4, 8, 2, 1)
-        else:
-            key = _shape_key(cw, B, H, W, OH, OW, d.x_cstride, precision, (x_fmt, y_fmt, res_fmt) + ('head2', d.head_rows) + tune_mode_key())
-            plan = _TUNED.get(key)
-            if KEY_HITS is not None:
-                KEY_HITS[key] = KEY_HITS.get(key, 0) + 1
-            if plan is None:
-                if torch.cuda.is_current_stream_capturing() or _lib.lib().srcnn_program_recording():
-                    plan = (4, 4, 8, 2, 1) if B * OH * OW >= 2048 else (2, 2, 8, 2, 1)
-                else:
-                    plan = _tune(d, key, x.device, only=[(4, 4, 8, 2), (2, 2, 8, 2)])
-    if head is not None:                   # the fused head lives in the 256x256 tile
-        _set_plan(d, (4, 4, 8, 2, 1))
-        if FlopCounter.enabled:            # the head's own (VALU) flops and its output instead of y
-            FlopCounter.flops += 2.0 * B * OH * OW * (4 if cw.mode == 1 else 1) * 6 * (cw.cout // (4 if cw.mode == 1 else 1))
-            FlopCounter.bytes += 4.0 * B * OH * OW * ((4 if cw.mode == 1 else 1) * 6 - cw.cout)
-            if FlopCounter.rows is not None:
-                FlopCounter.rows[-1]['flops'] = 2.0 * B * OH * OW * (cw.cout * cw.alg_k + 6 * cw.cout)
-                FlopCounter.rows[-1]['bytes'] = nbytes + 4.0 * B * OH * OW * ((4 if cw.mode == 1 else 1) * 6 - cw.cout)
-    elif plan is not None:                   # explicit (tile_mr, tile_nr, waves, stages, splits): tests and tools
-        _set_plan(d, plan)
-    elif AUTOTUNE:
-        # a launch with a device-side row limit is tuned WITH a typical limit (LIMIT_TUNE_ROIS of its units): what is fastest for
-        # the whole shape (the biggest tile, one round of CUs) is not what is fastest for a fifth of it
-        key = _shape_key(cw, B, H, W, OH, OW, d.x_cstride, precision, (x_fmt, y_fmt, res_fmt) + (('lim', m_limit_mul) if m_limit is not None else ())
-                         + (('x2', cw.cin2, cw.stride2, H2, W2) if x2 is not None else ()) + (('up',) if up is not None else ()) + tune_mode_key())
-        plan = _TUNED.get(key)
-        if KEY_HITS is not None:
-            KEY_HITS[key] = KEY_HITS.get(key, 0) + 1
-        if plan is None:
-            if torch.cuda.is_current_stream_capturing() or _lib.lib().srcnn_program_recording():
-                plan = (0, 0, 0, 0, 0)    # never time inside a graph capture / program recording; warm-up runs tune first
-            else:
-                if m_limit is not None:
-                    typical = torch.tensor([LIMIT_TUNE_ROIS], dtype=torch.int32, device=x.device)
-                    d.m_limit, d.m_limit_mul = typical.data_ptr(), int(m_limit_mul)
-                plan = _tune(d, key, x.device)
-                d.m_limit, d.m_limit_mul = None, 0
-        _set_plan(d, plan)
-    if FlopCounter.enabled and FlopCounter.rows is not None:
-        FlopCounter.rows[-1]['plan'] = (d.tile_mr, d.tile_nr, d.tile_waves, d.tile_stages, d.splits)
-    if m_limit is not None:
+    if m_limit is not None:               # after the plan: the tuner times the launch with a typical limit (_choose_plan)
         assert m_limit.is_cuda and m_limit.dtype == torch.int32 and m_limit_mul > 0
         d.m_limit, d.m_limit_mul = m_limit.data_ptr(), int(m_limit_mul)
-    need = L.srcnn_conv2d_workspace_bytes(ctypes.byref(d))
-    ws = _lib.workspace(need, x.device, "conv")
-    _lib.check(L.srcnn_conv2d(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d")
     used = (d.tile_mr, d.tile_nr, d.tile_waves, d.tile_stages, d.splits)
-    if REPEAT and name:
-        for rx, n in REPEAT:
-            if rx.match(name):
-                for _ in range(n):
-                    _lib.check(L.srcnn_conv2d(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d(repeat)")
+    _book(name or 'conv %dx%d %d->%d' % (cw.kh, cw.kw, cw.cin, cw.cout),
+          *conv_cost(cw, B, H, W, OH, OW, residual is not None, up, head is not None, head2), plan=used)
+    ws = _lib.workspace(L.srcnn_conv2d_workspace_bytes(ctypes.byref(d)), x.device, "conv")
+    _issue(lambda: L.srcnn_conv2d(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d", name)
     return used
-
-
-# ---- chained bottleneck launches (csrc/conv_chain.hip: srcnn_conv2d_chain): [conv2 -> conv3 -> conv1 of the next block] as ONE launch
-# whose workgroups keep their rows through the three convolutions.  BOTTLENECK_CHAIN: '0' (default) = off, '1' = on, 'auto' = on while
-# several forwards are in flight.  Built, bit-identical (tests/test_conv_chain_gpu.py), measured, and NOT the default: the headline
-# step is the same with and without it (profiles/chain_ab_r06.txt: 6.35-6.39 ms off, 6.35-6.41 ms with layer1 / layer2 / layer3
-# chained on their best tiles, at 3, 4, 6 and 8 forwards in flight) -- the intermediates come back through the fabric all the
-# same (a layer3 block's weights alone are 4.4 MB, the XCD's whole L2), and the package power limit prices the step by its
-# MFMA work, which a chain does not change (DESIGN 8).  It removes 46 launches per forward.
-BOTTLENECK_CHAIN = _os.environ.get('SRCNN_BOTTLENECK_CHAIN', '0')
-# planes of the bottleneck (64, 128, 256, 512) -> (tile_mr, waves, stages, narrow nr, wide nr) or None = that layer keeps its
-# separate launches.  layer4 (M = 2394: 10 workgroups of 256 rows) stays unchained.
-CHAIN_TILES = {64: (2, 4, 2, 1, 1), 128: (4, 8, 3, 2, 2), 256: (4, 8, 3, 2, 2), 512: None}
-CHAIN_MIN_WGS = 32        # a chain launch with fewer workgroups than this is not worth its latency
 
 
 def chain_enabled():
@@ -598,6 +629,26 @@ def chain_tile(planes, M):
     return t
 
 
+def _fused_descs(problems, plan_of, chained):
+    """The descriptors of a chained / grouped launch of problems = [(args, kwargs)] as for conv2d, each on the tile plan_of(its ConvW),
+    with what FlopCounter books for it: (descs, default name, flops, bytes, [(name, M, N, K) per problem])."""
+    descs = (_lib.ConvDesc * len(problems))()
+    flops = nbytes = 0.0
+    rows = []
+    for i, (args, kw) in enumerate(problems):
+        cw, B, H, W, OH, OW = args[0], args[2], args[3], args[4], args[6], args[7]
+        kw = dict(kw)
+        pname = kw.pop('name', None)
+        d = conv2d(*args, plan=plan_of(cw), desc_only=True, name=pname, **kw)
+        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(d), ctypes.sizeof(d))
+        fl, by, M, N, K = conv_cost(cw, B, H, W, OH, OW, kw.get('residual') is not None, head2=kw.get('head2'),
+                                    first_in_chain=not (chained and i), grouped=not chained)
+        flops += fl
+        nbytes += by
+        rows.append((pname, M, N, K))
+    return descs, '+'.join(str(r[0]) for r in rows), flops, nbytes, rows
+
+
 def conv_chain(phases, tile, name=None):
     """ONE launch for up to three convolutions over the same rows (srcnn_conv2d_chain): phases = [(args, kwargs)] exactly as they
     would be passed to conv2d, in order; phase i > 0 must be a 1x1 / stride 1 convolution of phase i-1's output.  tile = (tile_mr,
@@ -605,41 +656,9 @@ def conv_chain(phases, tile, name=None):
     narrow one.  Results are bit-identical to the separate launches with the same tiles."""
     L = _lib.lib()
     mr, waves, stages, na, nb = tile
-    descs = (_lib.ConvDesc * len(phases))()
-    flops = nbytes = 0.0
-    rows = []
-    for i, (args, kw) in enumerate(phases):
-        cw = args[0]
-        nr = nb if cw.cout >= 64 * nb else na
-        kw = dict(kw)
-        pname = kw.pop('name', None)
-        d = conv2d(*args, plan=(mr, nr, waves, stages, 1), desc_only=True, name=pname, **kw)
-        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(d), ctypes.sizeof(d))
-        B, OH, OW = args[2], args[6], args[7]
-        M = B * OH * OW
-        fl = 2.0 * M * cw.cout * cw.alg_k
-        # compulsory bytes of the chain: the first phase's input, every weight, residuals / second inputs, every output once --
-        # what a later phase reads is what the workgroup has just written (L2)
-        px_in = M if (cw.kh == 1 and cw.kw == 1) else B * args[3] * args[4]
-        by = 4.0 * ((px_in * cw.cin if i == 0 else 0) + M * cw.cin2 + cw.cout * cw.alg_k
-                    + M * cw.cout * (2 if kw.get('residual') is not None else 1))
-        flops += fl
-        nbytes += by
-        rows.append((pname, M, cw.cout, cw.alg_k))
-    if FlopCounter.enabled:
-        FlopCounter.flops += flops
-        FlopCounter.bytes += nbytes
-        FlopCounter.launches += 1
-        if FlopCounter.rows is not None:
-            FlopCounter.rows.append({'name': name or '+'.join(str(r[0]) for r in rows), 'M': rows[0][1], 'N': max(r[2] for r in rows),
-                                     'K': sum(r[3] for r in rows), 'flops': flops, 'bytes': nbytes, 'plan': (mr, nb, waves, stages, 1),
-                                     'chain': rows})
-    _lib.check(L.srcnn_conv2d_chain(descs, len(phases), _lib.stream()), "srcnn_conv2d_chain")
-    if REPEAT and name:
-        for rx, n in REPEAT:
-            if rx.match(name):
-                for _ in range(n):
-                    _lib.check(L.srcnn_conv2d_chain(descs, len(phases), _lib.stream()), "srcnn_conv2d_chain(repeat)")
+    descs, joined, flops, nbytes, rows = _fused_descs(phases, lambda cw: (mr, nb if cw.cout >= 64 * nb else na, waves, stages, 1), True)
+    _book(name or joined, flops, nbytes, rows[0][1], max(r[2] for r in rows), sum(r[3] for r in rows), (mr, nb, waves, stages, 1), chain=rows)
+    _issue(lambda: L.srcnn_conv2d_chain(descs, len(phases), _lib.stream()), "srcnn_conv2d_chain", name)
     return tile
 
 
@@ -647,42 +666,11 @@ def conv_group(problems, tile, name=None):
     """ONE launch for up to five independent convolutions that share a tile (srcnn_conv2d_group): problems = [(args, kwargs)] as
     for conv2d; tile = (tile_mr, tile_nr, waves, stages).  Each result is bit-identical to its own launch with that tile."""
     L = _lib.lib()
-    descs = (_lib.ConvDesc * len(problems))()
-    flops = nbytes = 0.0
-    rows = []
-    for i, (args, kw) in enumerate(problems):
-        cw = args[0]
-        kw = dict(kw)
-        pname = kw.pop('name', None)
-        d = conv2d(*args, plan=tuple(tile) + (1,), desc_only=True, name=pname, **kw)
-        ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(d), ctypes.sizeof(d))
-        B, H, W, OH, OW = args[2], args[3], args[4], args[6], args[7]
-        M = B * OH * OW
-        fl = 2.0 * M * cw.cout * cw.alg_k
-        px_in = M if (cw.kh == 1 and cw.kw == 1) else B * H * W
-        by = 4.0 * (px_in * cw.cin + cw.cout * cw.alg_k + M * cw.cout * (2 if kw.get('residual') is not None else 1))
-        h2 = kw.get('head2')
-        if h2 is not None:                  # the head's own flops; its planes instead of y (as conv2d counts them)
-            hn = h2[0].cout
-            fl += 2.0 * M * hn * cw.cout
-            by += 4.0 * M * (hn * (max(1, cw.cout // 256) if h2[2] else 1) - cw.cout)
-        flops += fl
-        nbytes += by
-        rows.append((pname, M, cw.cout, cw.alg_k))
-    if FlopCounter.enabled:
-        FlopCounter.flops += flops
-        FlopCounter.bytes += nbytes
-        FlopCounter.launches += 1
-        if FlopCounter.rows is not None:
-            FlopCounter.rows.append({'name': name or '+'.join(str(r[0]) for r in rows), 'M': sum(r[1] for r in rows), 'N': rows[0][2],
-                                     'K': rows[0][3], 'flops': flops, 'bytes': nbytes, 'plan': tuple(tile) + (1,), 'group': rows})
-    _lib.check(L.srcnn_conv2d_group(descs, len(problems), _lib.stream()), "srcnn_conv2d_group")
-    if REPEAT and name:
-        for rx, n in REPEAT:
-            if rx.match(name):
-                for _ in range(n):
-                    _lib.check(L.srcnn_conv2d_group(descs, len(problems), _lib.stream()), "srcnn_conv2d_group(repeat)")
-    return tuple(tile) + (1,)
+    plan = tuple(tile) + (1,)
+    descs, joined, flops, nbytes, rows = _fused_descs(problems, lambda cw: plan, False)
+    _book(name or joined, flops, nbytes, sum(r[1] for r in rows), rows[0][2], rows[0][3], plan, group=rows)
+    _issue(lambda: L.srcnn_conv2d_group(descs, len(problems), _lib.stream()), "srcnn_conv2d_group", name)
+    return plan
 
 
 def preprocess_size(H, W, target_short=600):
