@@ -82,7 +82,7 @@ __global__ void stem_pack_split16_kernel(const float *__restrict__ im, const flo
 
 // works on 8-channel groups; input F32, output F32 or SPLIT16
 __global__ void maxpool3x3s2_kernel(const float *__restrict__ x, int B, int H, int W, int C, float *__restrict__ y,
-                                    int OH, int OW, int yfmt)
+                                    int OH, int OW, int yfmt, unsigned *__restrict__ range_flag)
 {
     const int G = C / 8;
     const size_t total = (size_t)B * OH * OW * G;
@@ -105,6 +105,7 @@ __global__ void maxpool3x3s2_kernel(const float *__restrict__ x, int B, int H, i
 #pragma unroll
                 for (int e = 0; e < 8; ++e) m.v[e] = fmaxf(m.v[e], v.v[e]);
             }
+        if (yfmt == 1) split16_guard(m, range_flag, 9002);       // an F32 input beyond the f16 range: flag 9003 = max-pool
         act_store8(y, yfmt, ((size_t)b * OH + oh) * OW + ow, C, g, m);
     }
 }
@@ -352,7 +353,7 @@ int srcnn_maxpool3x3s2_ceil(const float *x, int B, int H, int W, int C, float *y
     SRCNN_REQUIRE((unsigned)y_format <= 1, "bad format");
     const size_t total = (size_t)B * OH * OW * (C / 8);
     SRCNN_LAUNCH(maxpool3x3s2_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, B, H, W, C,
-                       y, OH, OW, y_format);
+                       y, OH, OW, y_format, range_flag_word());
     return check_launch("srcnn_maxpool3x3s2_ceil");
 }
 

@@ -134,7 +134,8 @@ class FlopCounter(object):
 
 # ---- SPLIT16 range guard (include/srcnn_hip.h: srcnn_range_flag_read): layers are tagged by name so that a tripped flag
 # can be reported as the layer that produced the out-of-range activation
-TAG_NAMES = {9001: 'upsample_add', 9002: 'input conversion to SPLIT16 (stem_pack / act_convert)'}
+TAG_NAMES = {9001: 'upsample_add', 9002: 'input conversion to SPLIT16 (stem_pack / act_convert)',
+             9003: 'maxpool3x3s2_ceil (an F32 input beyond the SPLIT16 range)'}
 _TAG_IDS = {}
 
 
