@@ -16,18 +16,53 @@ Newton-CG restated in double precision (csrc/box_solver.h), one source built for
   solver='scipy'           the reference's own arrangement (host numpy `infer_boundary`, scipy solves, optionally fanned
                            out to a process pool) as the comparison path: model/utils/box_estimator.py, kitti_utils.py."""
 import collections
+import concurrent.futures
+import logging
 import math as m
+import multiprocessing
+import os
+import threading
+import time
 
 import numpy as np
 import torch
 
-from . import _lib, postprocess
+from . import _lib, engine, postprocess, serving
+from . import distributed as sdist
 from . import streams as _streams
 from .model.dense_align.dense_align import MAX_PIXELS, align_parallel, check_status
 from .model.utils import box_estimator, kitti_utils
 from .model.utils.config import cfg
 
 REC_COLS = _lib.REC_COLS
+
+# ------------------------------------------------------------------------------------------------ module switches
+# Keypoint branch on the detections that survive class NMS only (Plan.kpts_for_kept) instead of on all 300 rois inside the
+# forward: the flows below read no other row (nor do the reference's scripts, demo.py:196-257), every roi's keypoints are
+# computed independently of the other rois, and the device-side keep count bounds the tower's launches without a host
+# read-back.  The kept detections get the full head's values up to the engine's plan-to-plan rounding (~1e-5 relative on
+# the probabilities: the row-limited launches are tuned to their own tile / split-K plans).  Off: the forward computes the
+# branch for every roi, as `_StereoRCNN.forward` does by default.
+LAZY_KPTS = os.environ.get('SRCNN_LAZY_KPTS', '1') != '0'
+HOST_SOLVER_THREADS = 0          # srcnn_solve_*_records_host: <= 0 = one thread per 8 detections, at most 16
+# Streamed flow, solver='host' (default; SRCNN_ASYNC_HOST=0 = on the loop thread between launches): the host phases of a pair (wait for
+# its device stage, 4-DoF solves, record back + dense alignment launch, wait, 3-DoF solves) on a WORKER thread per pair in flight.
+# Same calls on the same streams in the same order per pair either way.  History of the switch (round 6): built for VERDICT r5 item
+# 8 and first measured with the KITTI loop's 16 PNG decoders as threads of this interpreter -- the loop thread's busy time per pair
+# fell 3.55 -> 2.14 ms and the throughput did not move (configs[3] 138.1 -> 136.7 pairs/s, 123 at six in flight: workers, decoders
+# and loop on one GIL; profiles/flow3d_async_host_r06.txt), so it stayed off.  With the decoders in processes of their own
+# (test_net._DecodeWorkers) the same switch gives configs[3] 155.6-163.4 -> 169.7-170.0 pairs/s on one box and leaves the
+# tensor-fed flow where it was (GPU-bound at 5.7 ms per pair: 175.2 vs 175.5) -- profiles/config3_host_side_r06.txt.
+ASYNC_HOST_PHASES = os.environ.get('SRCNN_ASYNC_HOST', '1') != '0'
+# host-side accounting of the record flow (bench.py --config 3): a dict {'solve_s', 'gpu_wait_s'} that step_3d / collect_3d add
+# to -- wall seconds of the host Newton-CG calls, and seconds the host sat in event.synchronize() waiting for the device
+TIMERS = None
+RECALIBRATE_AFTER_TRIPS = 2      # range-guard trips (pairs re-run on the fp32 engine) after which the scales are widened
+# Widening the scales changes the low-order bits of EVERY later frame (one glitched frame would cost them for good), so it can be
+# switched off: SRCNN_AUTO_RECALIBRATE=0 (or pipeline.AUTO_RECALIBRATE = False) keeps counting trips -- guard_trips(model) -- and
+# leaves the decision to the caller (model.calibrate_activation_scales(frames) is the controlled way; reset_guard_trips(model)).
+AUTO_RECALIBRATE = os.environ.get('SRCNN_AUTO_RECALIBRATE', '1') != '0'
+MAX_SHIFT_WIDENING = 10          # automatic re-calibration never lowers a tensor group's shift by more than this many bits in total (x1000)
 
 
 class _PlainCalib(object):
@@ -73,7 +108,6 @@ def _noop(_):
 
 
 def _worker_init():
-    import os
     os.environ.setdefault('OMP_NUM_THREADS', '1')
     torch.set_num_threads(1)
 
@@ -85,8 +119,6 @@ class SolverPool(object):
     (profiles/full_pipeline_solver_pool_r01.txt)."""
 
     def __init__(self, workers=None):
-        import multiprocessing as mp
-        import os
         if workers is None:
             world = int(os.environ.get('LOCAL_WORLD_SIZE', os.environ.get('WORLD_SIZE', '1')) or 1)
             workers = max(1, min(32, (os.cpu_count() or 1) // max(world, 1)))
@@ -95,7 +127,7 @@ class SolverPool(object):
         saved = {k: os.environ.get(k) for k in keys}
         os.environ.update({k: '1' for k in keys})
         try:
-            self._pool = mp.get_context('spawn').Pool(self.workers, initializer=_worker_init)
+            self._pool = multiprocessing.get_context('spawn').Pool(self.workers, initializer=_worker_init)
             self._pool.map(_noop, range(self.workers))          # workers are up (and have imported) before the first pair
         finally:
             for k, v in saved.items():
@@ -145,6 +177,9 @@ class _Stage3D(object):
         self.phase = 0               # solver='host': 1 = waiting for the 4-DoF solve, 2 = for the 3-DoF solve, 0 = complete
         self.ctx = None
         self.worker, self.error, self.done = False, None, None     # streamed flow: a worker thread runs the host phases
+        # image b > 0 of a batch: image 0's stage, whose record carries the shared forward's range flag (collect_3d).  Never
+        # cleared: batch stages live under slot keys (slot, b) that no other flow uses
+        self.batch_head = None
 
 
 _stages = {}
@@ -157,18 +192,28 @@ def _stage(n, dev, slot):
     return _stages[key]
 
 
-# Keypoint branch on the detections that survive class NMS only (Plan.kpts_for_kept) instead of on all 300 rois inside the
-# forward: the flows below read no other row (nor do the reference's scripts, demo.py:196-257), every roi's keypoints are
-# computed independently of the other rois, and the device-side keep count bounds the tower's launches without a host
-# read-back.  The kept detections get the full head's values up to the engine's plan-to-plan rounding (~1e-5 relative on
-# the probabilities: the row-limited launches are tuned to their own tile / split-K plans).  Off: the forward computes the
-# branch for every roi, as `_StereoRCNN.forward` does by default.
-import os as _os
-LAZY_KPTS = _os.environ.get('SRCNN_LAZY_KPTS', '1') != '0'
-
-
 def _lazy(model):
     return LAZY_KPTS and model.precision == 'f16x3' and not model.use_graph
+
+
+def _plan_of(model, im_left_data, slot):
+    B, _, H, W = im_left_data.shape
+    return model._get_plan(int(B), int(H), int(W), slot), model.precision
+
+
+def _launch_dense_align(st, iml, imr, scale, cal, stream):
+    """Dense alignment of the stage's record on `stream` (the library's handle): boxes, borders, poses and valid mask out of the
+    record, then the masked fixed-batch alignment into st.align_status / st.best_dis.  For launch_3d and step_3d phase 1."""
+    L = _lib.lib()
+    n = st.n
+    _lib.check(L.srcnn_align_inputs(st.rec.data_ptr(), n, REC_COLS, st.boxes.data_ptr(), st.borders.data_ptr(),
+                                    st.poses.data_ptr(), st.valid.data_ptr(), stream), "srcnn_align_inputs")
+    _, _, H, W = iml.shape
+    ws = _lib.workspace(L.srcnn_dense_align_workspace_bytes(H, W, n, MAX_PIXELS), iml.device, "dense_align")
+    _lib.check(L.srcnn_dense_align(_lib.ptr(iml), _lib.ptr(imr), H, W, float(scale), cal[0], cal[1], cal[2], cal[3],
+                                   st.boxes.data_ptr(), st.borders.data_ptr(), st.poses.data_ptr(), st.valid.data_ptr(),
+                                   n, MAX_PIXELS, st.align_status.data_ptr(), st.best_dis.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), stream), "srcnn_dense_align")
 
 
 def launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape, eval_thresh=0.05, class_index=1,
@@ -187,7 +232,6 @@ def launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape,
         lazy[0].kpts_for_kept(out[0][0].contiguous(), keep_idx, num, im_info.view(-1, 3)[0:1].contiguous().float(), det['kpts'], lazy[1])
     assert int(im_shape[1]) <= 4095, "image wider than the 3-D stage's column buffer"
     st = _stage(n, keep_idx.device, slot)
-    from . import distributed as sdist
     sdist.pack_records_device(det, keep_idx, num, class_index, out=st.rec)
     s = _lib.stream()
     cal = (float(calib.p2[0, 0]), float(calib.p2[0, 2]), float(calib.p2[1, 2]), float(calib.p2[0, 3] - calib.p3[0, 3]))
@@ -203,7 +247,7 @@ def launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape,
                   bool(dense_align))
         st.worker, st.error = False, None
         if async_host and ASYNC_HOST_PHASES:
-            st.done = _threading.Event()
+            st.done = threading.Event()
             st.worker = True
             _host_executor().submit(_host_phases, st, keep_idx.device.index if keep_idx.device.index is not None else torch.cuda.current_device())
         return st
@@ -211,14 +255,7 @@ def launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape,
     _lib.check(L.srcnn_solve_4dof(st.rec.data_ptr(), n, REC_COLS, im_h, im_w, cal[0], cal[1], cal[2], cal[3],
                                   float(eval_thresh), st.state[0].data_ptr(), s), "srcnn_solve_4dof")
     if dense_align:
-        _lib.check(L.srcnn_align_inputs(st.rec.data_ptr(), n, REC_COLS, st.boxes.data_ptr(), st.borders.data_ptr(),
-                                        st.poses.data_ptr(), st.valid.data_ptr(), s), "srcnn_align_inputs")
-        _, _, H, W = im_left_data.shape
-        ws = _lib.workspace(L.srcnn_dense_align_workspace_bytes(H, W, n, MAX_PIXELS), im_left_data.device, "dense_align")
-        _lib.check(L.srcnn_dense_align(_lib.ptr(im_left_data), _lib.ptr(im_right_data), H, W, float(scale), cal[0], cal[1],
-                                       cal[2], cal[3], st.boxes.data_ptr(), st.borders.data_ptr(), st.poses.data_ptr(),
-                                       st.valid.data_ptr(), n, MAX_PIXELS, st.align_status.data_ptr(),
-                                       st.best_dis.data_ptr(), ws.data_ptr(), ws.numel(), s), "srcnn_dense_align")
+        _launch_dense_align(st, im_left_data, im_right_data, scale, cal, s)
         _lib.check(L.srcnn_solve_3dof(st.rec.data_ptr(), n, REC_COLS, im_h, im_w, cal[0], cal[1], cal[2], cal[3],
                                       st.align_status.data_ptr(), st.best_dis.data_ptr(), st.state[1].data_ptr(), s),
                    "srcnn_solve_3dof")
@@ -228,26 +265,14 @@ def launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape,
     return st
 
 
-HOST_SOLVER_THREADS = 0          # srcnn_solve_*_records_host: <= 0 = one thread per 8 detections, at most 16
-# Streamed flow, solver='host' (default; SRCNN_ASYNC_HOST=0 = on the loop thread between launches): the host phases of a pair (wait for
-# its device stage, 4-DoF solves, record back + dense alignment launch, wait, 3-DoF solves) on a WORKER thread per pair in flight.
-# Same calls on the same streams in the same order per pair either way.  History of the switch (round 6): built for VERDICT r5 item
-# 8 and first measured with the KITTI loop's 16 PNG decoders as threads of this interpreter -- the loop thread's busy time per pair
-# fell 3.55 -> 2.14 ms and the throughput did not move (configs[3] 138.1 -> 136.7 pairs/s, 123 at six in flight: workers, decoders
-# and loop on one GIL; profiles/flow3d_async_host_r06.txt), so it stayed off.  With the decoders in processes of their own
-# (test_net._DecodeWorkers) the same switch gives configs[3] 155.6-163.4 -> 169.7-170.0 pairs/s on one box and leaves the
-# tensor-fed flow where it was (GPU-bound at 5.7 ms per pair: 175.2 vs 175.5) -- profiles/config3_host_side_r06.txt.
-ASYNC_HOST_PHASES = _os.environ.get('SRCNN_ASYNC_HOST', '1') != '0'
 _host_pool = None
-import threading as _threading
-_timers_lock = _threading.Lock()
+_timers_lock = threading.Lock()
 
 
 def _host_executor():
     global _host_pool
     if _host_pool is None:
-        import concurrent.futures as cf
-        _host_pool = cf.ThreadPoolExecutor(max_workers=8, thread_name_prefix='srcnn-host3d')
+        _host_pool = concurrent.futures.ThreadPoolExecutor(max_workers=8, thread_name_prefix='srcnn-host3d')
     return _host_pool
 
 
@@ -261,14 +286,10 @@ def _host_phases(st, dev_index):
         st.error = e
     finally:
         st.done.set()
-# host-side accounting of the record flow (bench.py --config 3): a dict {'solve_s', 'gpu_wait_s'} that step_3d / collect_3d add
-# to -- wall seconds of the host Newton-CG calls, and seconds the host sat in event.synchronize() waiting for the device
-TIMERS = None
 
 
 def _timed(key, t0):
     if TIMERS is not None:
-        import time
         dt = time.perf_counter() - t0
         with _timers_lock:
             if TIMERS is not None:
@@ -276,7 +297,6 @@ def _timed(key, t0):
 
 
 def _now():
-    import time
     return time.perf_counter() if TIMERS is not None else 0.0
 
 
@@ -288,7 +308,7 @@ def step_3d(st, block=True, _worker=False):
     at the latest, when the pair's slot is needed (collect_3d blocks)."""
     if st.phase == 0:
         return
-    if getattr(st, 'worker', False) and not _worker:
+    if st.worker and not _worker:
         return                                       # a worker thread owns this pair's host phases (collect_3d waits for it)
     if not block and not st.event.query():
         return
@@ -312,16 +332,8 @@ def step_3d(st, block=True, _worker=False):
             st.phase = 0
             return
         with torch.no_grad(), torch.cuda.stream(stream):
-            s = _lib.stream()
             st.rec.copy_(st.rec_host, non_blocking=True)
-            _lib.check(L.srcnn_align_inputs(st.rec.data_ptr(), n, REC_COLS, st.boxes.data_ptr(), st.borders.data_ptr(),
-                                            st.poses.data_ptr(), st.valid.data_ptr(), s), "srcnn_align_inputs")
-            _, _, H, W = iml.shape
-            ws = _lib.workspace(L.srcnn_dense_align_workspace_bytes(H, W, n, MAX_PIXELS), iml.device, "dense_align")
-            _lib.check(L.srcnn_dense_align(_lib.ptr(iml), _lib.ptr(imr), H, W, scale, cal[0], cal[1], cal[2], cal[3],
-                                           st.boxes.data_ptr(), st.borders.data_ptr(), st.poses.data_ptr(), st.valid.data_ptr(),
-                                           n, MAX_PIXELS, st.align_status.data_ptr(), st.best_dis.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), s), "srcnn_dense_align")
+            _launch_dense_align(st, iml, imr, scale, cal, _lib.stream())
             st.align_host[0].copy_(st.align_status, non_blocking=True)
             st.align_host[1].copy_(st.best_dis, non_blocking=True)
             st.event.record()
@@ -336,9 +348,16 @@ def step_3d(st, block=True, _worker=False):
     st.phase = 0
 
 
+def _range_error(flag, shared=False):
+    """The error for a record whose row 0, column 1 holds `flag` > 0: the range guard of the forward behind it tripped."""
+    return engine.Split16RangeError('SPLIT16 range exceeded in %s%s' % (
+        engine.TAG_NAMES.get(flag, 'layer tag %d' % (flag - 1)),
+        ' (flag of the batch\'s shared forward, carried by its first image)' if shared else ''))
+
+
 def collect_3d(st):
     """Wait for a launch_3d() handle and turn its record into the object list detect_3d returns."""
-    if getattr(st, 'worker', False):
+    if st.worker:
         t0 = _now()
         st.done.wait()
         _timed('main_wait_s', t0)
@@ -354,22 +373,22 @@ def collect_3d(st):
     _timed('gpu_wait_s', t0)
     rec, state = st.rec_host.numpy(), st.state_host.numpy()
     if rec[0, 1] > 0:           # SPLIT16 range guard of THIS pair's forward (its plan's own word, copied and cleared by the pack)
-        from . import engine
-        raise engine.Split16RangeError('SPLIT16 range exceeded in %s'
-                                       % engine.TAG_NAMES.get(int(rec[0, 1]), 'layer tag %d' % (int(rec[0, 1]) - 1)))
-    head = getattr(st, 'batch_head', None)
-    if head is not None:
+        raise _range_error(int(rec[0, 1]))
+    if st.batch_head is not None:
         # image b > 0 of a batched forward: the ONE forward's flag word was copied (and cleared) by the pack of image 0 only, so
         # this record alone would look clean whatever the shared forward did -- in whatever order the handles are collected
-        head.event.synchronize()
-        hflag = int(head.rec_host[0, 1])
+        st.batch_head.event.synchronize()
+        hflag = int(st.batch_head.rec_host[0, 1])
         if hflag > 0:
-            from . import engine
-            raise engine.Split16RangeError('SPLIT16 range exceeded in %s (flag of the batch\'s shared forward, carried by its first image)'
-                                           % engine.TAG_NAMES.get(hflag, 'layer tag %d' % (hflag - 1)))
-    k = int(rec[0, 0])
+            raise _range_error(hflag, shared=True)
+    return _objects_from_record(rec, state)
+
+
+def _objects_from_record(rec, state):
+    """A finished record (n + 1, REC_COLS) and its solver states (2, n, 4: [0] 4-DoF, [1] final) as numpy arrays -> detect_3d's
+    object list; no GPU, no waiting.  distributed.objects_to_record is the way back."""
     objs = []
-    for i in range(k):
+    for i in range(int(rec[0, 0])):
         row = rec[1 + i]
         if not row[20] > 0:                                    # 4-DoF status (demo.py:293)
             continue
@@ -379,7 +398,7 @@ def collect_3d(st):
         xyz4 = state[0, i, 0:3].copy()
         o = {'box_left': row[1:5].copy(), 'box_right': row[5:9].copy(), 'score': float(row[0]),
              'dim': row[9:12].astype(np.float64), 'alpha': m.atan2(float(row[12]), float(row[13])),
-             'xyz': state[1, i, 0:3].copy() if aligned else xyz4, 'theta': float(state[1, i, 3] if aligned else state[0, i, 3]),
+             'xyz': state[1, i, 0:3].copy() if aligned else xyz4.copy(), 'theta': float(state[1, i, 3] if aligned else state[0, i, 3]),
              'kpts': row[14:19].copy(), 'aligned': aligned, 'xyz_init': xyz4, 'theta_init': float(state[0, i, 3]),
              'roi_index': int(row[19])}
         if aligned:
@@ -388,17 +407,124 @@ def collect_3d(st):
     return objs
 
 
+# ------------------------------------------------------------------------------------------------ forward, fp32 fallback
+def _forward(model, left, right, im_info, slot):
+    """ONE forward on the current stream -> (out, left, right, im_info, lazy), what launch_3d takes.  left / right: the network
+    inputs with their im_info, or -- im_info None -- uint8 RGB images (model.forward_images: preprocessing fused in front of
+    the forward).  lazy: (plan, precision) when the forward left the keypoint branch to the kept detections (_lazy(model),
+    see LAZY_KPTS), else None."""
+    lazy = _lazy(model)
+    if im_info is None:
+        out, left, right, im_info = model.forward_images(left, right, slot=slot, kpts=not lazy, alias_outputs=True)
+    else:
+        out = model(left, right, im_info, slot=slot, kpts=not lazy, alias_outputs=True)
+    return out, left, right, im_info, _plan_of(model, left, slot) if lazy else None
+
+
+def _forward_and_launch(model, left, right, im_info, scale, calib, im_shape, eval_thresh, class_index, dense_align, slot, solver,
+                        async_host=False):
+    """One pair: _forward and the 3-D stage behind it (launch_3d, whose arguments these are) -> the handle.  scale is a Python
+    float the caller had BEFORE this call: a device read in here would block behind the forward (launch_3d_batch)."""
+    with torch.no_grad():
+        out, left, right, im_info, lazy = _forward(model, left, right, im_info, slot)
+        return launch_3d(out, left, right, im_info, scale, calib, im_shape, eval_thresh, class_index, dense_align, slot, solver,
+                         lazy=lazy, async_host=async_host)
+
+
+def _with_fp32_fallback(model, run, rerun, note):
+    """run(); when the SPLIT16 range guard trips in it (engine.Split16RangeError: an activation left the f16 range), rerun() --
+    the same work on the exact fp32 engine (F32 activations), never garbage -- with model.precision switched to 'f32' and
+    restored whatever happens.  A model already on 'f32' has nothing to fall back to: the error propagates, as does a second
+    trip inside rerun().  note() (_note_guard_trip) is called only after a re-run that succeeded: its own error is not masked
+    and does not count as a trip.  What the callers do differently, kept as it was when each had its own copy:
+      detect_3d, detect_3d_batch  rerun = the function itself on its own slot; noted for that slot -- slot 0 for solver
+                                  'scipy' / 'host_py', whose forward always runs there
+      detect_3d_stream            rerun = detect_3d / detect_3d_images on `retry_slot`, buffers no pair in flight owns; noted
+                                  with may_recalibrate=False.  Frames given as uint8 images are NOT noted (note=None): that is
+                                  the present behaviour, not a decision anyone has recorded."""
+    try:
+        return run()
+    except engine.Split16RangeError:
+        if model.precision == 'f32':
+            raise
+        prev, model.precision = model.precision, 'f32'
+        try:
+            objs = rerun()
+        finally:
+            model.precision = prev
+        if note is not None:
+            note()
+        return objs
+
+
 # ------------------------------------------------------------------------------------------------ scipy comparison flow
+# The reference's host arrangement as pure numpy functions: its one-shot form (_detect_3d_scipy) and its staged form
+# (_detect_3d_stream_scipy) differ in how the arrays reach the host and the tensors the device, not in these.
+# dets = (dets_left (k, 5), dets_right (k, 5), dim_orien (k, 5), kpts (k, 5)): float32 rows of the class's kept detections.
+def _tasks_4dof(kind, im_shape, calib, dets, eval_thresh):
+    """-> (cand, alphas, tasks): the detections above the threshold (demo.py:282-283), their observation angles (float64
+    atan2) and the _solve_task tuples of their 4-DoF solves (kind 4: scipy, 14: native) on the float32 rows as they are
+    (demo.py:288-293).  First, in place on kpts, demo.py:259-265: the regressed borders are replaced when they are narrower
+    than half the inferred ones."""
+    dl, dr, do, kpts = dets
+    inferred = kitti_utils.infer_boundary(im_shape, dl)
+    for i in range(dl.shape[0]):
+        if kpts[i, 4] - kpts[i, 3] < 0.5 * (inferred[i, 1] - inferred[i, 0]):
+            kpts[i, 3:5] = inferred[i]
+    cand = [i for i in range(dl.shape[0]) if dl[i, -1] > eval_thresh]
+    alphas = [m.atan2(do[i, 3], do[i, 4]) for i in cand]
+    return cand, alphas, [(kind, tuple(im_shape), calib.p2, calib.p3, (a, do[i, 0:3], dl[i, 0:4], dr[i, 0:4], kpts[i]))
+                          for i, a in zip(cand, alphas)]
+
+
+def _solved_objects(dets, cand, alphas, res4):
+    """demo.py:291-302: one object per candidate whose 4-DoF solve succeeded."""
+    dl, dr, do, kpts = dets
+    solved = []
+    for i, alpha, (status, state) in zip(cand, alphas, res4):
+        if status > 0:
+            solved.append({'box_left': dl[i, 0:4].copy(), 'box_right': dr[i, 0:4].copy(), 'score': float(dl[i, 4]),
+                           'dim': do[i, 0:3].astype(np.float64), 'alpha': alpha,
+                           'xyz': np.array(state[0:3], dtype=np.float64), 'theta': float(state[3]),
+                           'kpts': kpts[i].copy(), 'aligned': False,
+                           'xyz_init': np.array(state[0:3], dtype=np.float64), 'theta_init': float(state[3])})
+    return solved
+
+
+def _align_rows(solved):
+    """align_parallel's per-object inputs (demo.py:306-308) as arrays: left boxes, keypoints, poses [x y z w h l theta]."""
+    return (np.asarray([o['box_left'] for o in solved]), np.asarray([o['kpts'] for o in solved]),
+            np.asarray([[o['xyz'][0], o['xyz'][1], o['xyz'][2], o['dim'][0], o['dim'][1], o['dim'][2], o['theta']]
+                        for o in solved]))
+
+
+def _tasks_3dof(kind, im_shape, calib, solved, succ, dis):
+    """demo.py:311-319: the aligned objects (indices into `solved`) and their 3-DoF tasks (kind 3 / 13); see _alpha32, _f64."""
+    todo = [i for i in range(len(solved)) if succ[i] > 0]
+    return todo, [(kind, tuple(im_shape), calib.p2, calib.p3,
+                   (_alpha32(solved[i]['alpha']), solved[i]['dim'], _f64(solved[i]['box_left']), float(dis[i]),
+                    _f64(solved[i]['kpts']))) for i in todo]
+
+
+def _apply_3dof(solved, todo, res3, dis):
+    """The rectified poses written back into the aligned objects."""
+    for i, (state, z) in zip(todo, res3):
+        o = solved[i]
+        o['xyz'] = np.array([state[0], state[1], z], dtype=np.float64)
+        o['theta'] = float(state[2])
+        o['aligned'] = True
+        o['disparity'] = float(dis[i])
+
+
 def _detect_3d_scipy(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh, class_index, dense_align, pool,
                      native=False):
     k4, k3 = (14, 13) if native else (4, 3)
     with torch.no_grad():
-        lazy = _lazy(model)                   # the same form of the keypoint branch as the record flows (see LAZY_KPTS)
-        out = model(im_left_data, im_right_data, im_info, kpts=not lazy, alias_outputs=True)
+        out, _, _, _, lazy = _forward(model, im_left_data, im_right_data, im_info, 0)      # the record flows' forward, on slot 0
         det = postprocess.decode_detections(*out[:8], im_info)
         if lazy:
             keep_idx, num = postprocess.class_nms_device(det, class_index, eval_thresh, cfg.TEST.NMS)
-            plan, precision = _plan_of(model, im_left_data, 0)
+            plan, precision = lazy
             plan.kpts_for_kept(out[0][0].contiguous(), keep_idx, num, im_info.view(-1, 3)[0:1].contiguous(), det['kpts'], precision)
         cls = postprocess.class_detections(det, class_index, eval_thresh, cfg.TEST.NMS)
         # this flow packs no record, so nothing else would read (and clear) the forward's range word: a tripped flag would be
@@ -408,48 +534,18 @@ def _detect_3d_scipy(model, im_left_data, im_right_data, im_info, calib, im_shap
     dets_left = cls['dets_left'].cpu().numpy()
     if dets_left.shape[0] == 0:
         return []
-    dets_right = cls['dets_right'].cpu().numpy()
-    dim_orien = cls['dim_orien'].cpu().numpy()
-    kpts = cls['kpts'].cpu().numpy().copy()
-    # demo.py:259-265: replace the regressed borders when they are narrower than half the inferred ones
-    inferred = kitti_utils.infer_boundary(im_shape, dets_left)
-    for i in range(dets_left.shape[0]):
-        if kpts[i, 4] - kpts[i, 3] < 0.5 * (inferred[i, 1] - inferred[i, 0]):
-            kpts[i, 3:5] = inferred[i]
+    dets = (dets_left, cls['dets_right'].cpu().numpy(), cls['dim_orien'].cpu().numpy(), cls['kpts'].cpu().numpy().copy())
     run = pool.map if pool is not None else (lambda tasks: [_solve_task(t) for t in tasks])
-    cand = [i for i in range(dets_left.shape[0]) if dets_left[i, -1] > eval_thresh]            # demo.py:282-283
-    alphas = [m.atan2(dim_orien[i, 3], dim_orien[i, 4]) for i in cand]
-    res4 = run([(k4, tuple(im_shape), calib.p2, calib.p3,
-                 (a, dim_orien[i, 0:3], dets_left[i, 0:4], dets_right[i, 0:4], kpts[i])) for i, a in zip(cand, alphas)])
-    solved = []
-    for i, alpha, (status, state) in zip(cand, alphas, res4):                                    # demo.py:291-302
-        if status > 0:
-            solved.append({'box_left': dets_left[i, 0:4].copy(), 'box_right': dets_right[i, 0:4].copy(),
-                           'score': float(dets_left[i, 4]), 'dim': dim_orien[i, 0:3].astype(np.float64), 'alpha': alpha,
-                           'xyz': np.array(state[0:3], dtype=np.float64), 'theta': float(state[3]),
-                           'kpts': kpts[i].copy(), 'aligned': False,
-                           'xyz_init': np.array(state[0:3], dtype=np.float64), 'theta_init': float(state[3])})
+    cand, alphas, tasks = _tasks_4dof(k4, im_shape, calib, dets, eval_thresh)
+    solved = _solved_objects(dets, cand, alphas, run(tasks))
     if not solved or not dense_align:
         return solved
     dev = im_left_data.device
-    f32 = lambda rows: torch.tensor(np.asarray(rows), dtype=torch.float32, device=dev)
-    boxes = f32([o['box_left'] for o in solved])
-    kp = f32([o['kpts'] for o in solved])
-    poses = f32([[o['xyz'][0], o['xyz'][1], o['xyz'][2], o['dim'][0], o['dim'][1], o['dim'][2], o['theta']]
-                 for o in solved])
+    boxes, kp, poses = (torch.tensor(rows, dtype=torch.float32, device=dev) for rows in _align_rows(solved))
     succ, dis_final = align_parallel(calib, _scale32(im_info), im_left_data, im_right_data, boxes, kp, poses)   # demo.py:306-308
     succ, dis_final = check_status(succ.cpu().numpy()), dis_final.cpu().numpy()
-    todo = [i for i in range(len(solved)) if succ[i] > 0]                                      # demo.py:311-319
-    res3 = run([(k3, tuple(im_shape), calib.p2, calib.p3,
-                 (_alpha32(solved[i]['alpha']), solved[i]['dim'], _f64(solved[i]['box_left']), float(dis_final[i]),
-                  _f64(solved[i]['kpts'])))
-                for i in todo])
-    for i, (state, z) in zip(todo, res3):
-        o = solved[i]
-        o['xyz'] = np.array([state[0], state[1], z], dtype=np.float64)
-        o['theta'] = float(state[2])
-        o['aligned'] = True
-        o['disparity'] = float(dis_final[i])
+    todo, tasks = _tasks_3dof(k3, im_shape, calib, solved, succ, dis_final)
+    _apply_3dof(solved, todo, run(tasks), dis_final)
     return solved
 
 
@@ -463,62 +559,31 @@ def detect_3d(model, im_left_data, im_right_data, im_info, calib, im_shape, eval
     the reference's scipy path, same throughput as 'device' when streamed); 'device' (Newton-CG kernels, no host bounce at
     all, one D2H copy; its libm differs from glibc in last bits, so chaotic end points differ); 'scipy' (the
     reference's own arrangement: host numpy + scipy per object, optional `pool`); 'host_py' (that arrangement with the native
-    solver called per object)."""
-    from . import engine
+    solver called per object).  Out-of-range SPLIT16 activations re-run the pair on the exact fp32 engine."""
     if solver in ('scipy', 'host_py'):
-        try:
-            return _detect_3d_scipy(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh, class_index,
-                                    dense_align, pool if solver == 'scipy' else None, native=(solver == 'host_py'))
-        except engine.Split16RangeError:
-            if model.precision == 'f32':
-                raise
-            prev, model.precision = model.precision, 'f32'       # same fallback as the record flows below
-            try:
-                objs = _detect_3d_scipy(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh, class_index,
-                                        dense_align, pool if solver == 'scipy' else None, native=(solver == 'host_py'))
-            finally:
-                model.precision = prev
-            _note_guard_trip(model, im_left_data, 0)             # only after a re-run that succeeded (its own error is not masked)
-            return objs
-    with torch.no_grad():
-        lazy = _lazy(model)
+        run = lambda: _detect_3d_scipy(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh, class_index,
+                                       dense_align, pool if solver == 'scipy' else None, native=(solver == 'host_py'))
+        note_slot = 0
+    else:
         scale = _scale32(im_info)            # a blocking device read: before the forward is enqueued, not behind it
-        out = model(im_left_data, im_right_data, im_info, slot=slot, kpts=not lazy, alias_outputs=True)
-        st = launch_3d(out, im_left_data, im_right_data, im_info, scale, calib, im_shape, eval_thresh,
-                       class_index, dense_align, slot, solver, lazy=_plan_of(model, im_left_data, slot) if lazy else None)
-    try:
-        return collect_3d(st)
-    except engine.Split16RangeError:
-        if model.precision == 'f32':
-            raise
-        # an activation left the f16 range: this pair again on the exact fp32 engine (F32 activations), never garbage
-        prev, model.precision = model.precision, 'f32'
-        try:
-            objs = detect_3d(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh, class_index,
-                             dense_align, pool, solver, slot)
-        finally:
-            model.precision = prev
-        _note_guard_trip(model, im_left_data, slot)
-        return objs
-
-
-def _plan_of(model, im_left_data, slot):
-    B, _, H, W = im_left_data.shape
-    return model._get_plan(int(B), int(H), int(W), slot), model.precision
+        st = _forward_and_launch(model, im_left_data, im_right_data, im_info, scale, calib, im_shape, eval_thresh,
+                                 class_index, dense_align, slot, solver)
+        run = lambda: collect_3d(st)
+        note_slot = slot
+    return _with_fp32_fallback(model, run,
+                               lambda: detect_3d(model, im_left_data, im_right_data, im_info, calib, im_shape, eval_thresh,
+                                                 class_index, dense_align, pool, solver, slot),
+                               lambda: _note_guard_trip(model, im_left_data, note_slot))
 
 
 def detect_3d_images(model, img_left_u8, img_right_u8, calib, eval_thresh=0.05, class_index=1, dense_align=True, slot=0,
                      wait=True, solver='host', async_host=False):
     """The same from the decoded uint8 RGB images on the device: preprocessing fused in front of the forward
     (model.forward_images), then the device 3-D flow.  wait=False returns the handle for collect_3d()."""
-    with torch.no_grad():
-        lazy = _lazy(model)
-        out, iml, imr, info = model.forward_images(img_left_u8, img_right_u8, slot=slot, kpts=not lazy, alias_outputs=True)
-        from . import engine
-        scale = float(np.float32(engine.preprocess_size(int(img_left_u8.shape[0]), int(img_left_u8.shape[1]),
-                                                        cfg.TEST.SCALES[0])[2]))
-        st = launch_3d(out, iml, imr, info, scale, calib, tuple(img_left_u8.shape), eval_thresh, class_index, dense_align, slot,
-                       solver, lazy=_plan_of(model, iml, slot) if lazy else None, async_host=async_host and not wait)
+    scale = float(np.float32(engine.preprocess_size(int(img_left_u8.shape[0]), int(img_left_u8.shape[1]),
+                                                    cfg.TEST.SCALES[0])[2]))
+    st = _forward_and_launch(model, img_left_u8, img_right_u8, None, scale, calib, tuple(img_left_u8.shape), eval_thresh,
+                             class_index, dense_align, slot, solver, async_host=async_host and not wait)
     return collect_3d(st) if wait else st
 
 
@@ -546,17 +611,13 @@ def launch_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shap
     if scales is None:
         scales = [float(v) for v in im_info.view(-1, 3)[:, 2].cpu()]        # float32 elements -> Python floats, as _scale32
     with torch.no_grad():
-        lazy = _lazy(model)
-        out = model(im_left_data, im_right_data, im_info, slot=slot, kpts=not lazy, alias_outputs=True)
-        pl = _plan_of(model, im_left_data, slot) if lazy else None
-        handles = []
-        for b in range(B):
-            info_b = im_info.view(-1, 3)[b:b + 1]
-            handles.append(launch_3d(image_outputs(out, b), im_left_data[b:b + 1], im_right_data[b:b + 1], info_b,
-                                     scales[b], calibs[b], im_shapes[b], eval_thresh, class_index, dense_align,
-                                     (slot, b), solver, lazy=pl))
-        for h in handles[1:]:
-            h.batch_head = handles[0]        # see collect_3d: the shared forward's range flag lives in image 0's record
+        out, _, _, _, lazy = _forward(model, im_left_data, im_right_data, im_info, slot)
+        info = im_info.view(-1, 3)
+        handles = [launch_3d(image_outputs(out, b), im_left_data[b:b + 1], im_right_data[b:b + 1], info[b:b + 1], scales[b],
+                             calibs[b], im_shapes[b], eval_thresh, class_index, dense_align, (slot, b), solver, lazy=lazy)
+                   for b in range(B)]
+    for h in handles[1:]:
+        h.batch_head = handles[0]        # see collect_3d: the shared forward's range flag lives in image 0's record
     return handles
 
 
@@ -579,29 +640,13 @@ def detect_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shap
                     dense_align=True, slot=0, solver='host'):
     """B pairs -> B object lists (detect_3d's dicts), one batched forward; out-of-range SPLIT16 activations re-run the batch on
     the exact fp32 engine."""
-    from . import engine
-    try:
-        return collect_3d_batch(launch_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shapes, eval_thresh,
-                                                class_index, dense_align, slot, solver))
-    except engine.Split16RangeError:
-        if model.precision == 'f32':
-            raise
-        prev, model.precision = model.precision, 'f32'
-        try:
-            objs = detect_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shapes, eval_thresh, class_index,
-                                   dense_align, slot, solver)
-        finally:
-            model.precision = prev
-        _note_guard_trip(model, im_left_data, slot)
-        return objs
-
-
-RECALIBRATE_AFTER_TRIPS = 2      # range-guard trips (pairs re-run on the fp32 engine) after which the scales are widened
-# Widening the scales changes the low-order bits of EVERY later frame (one glitched frame would cost them for good), so it can be
-# switched off: SRCNN_AUTO_RECALIBRATE=0 (or pipeline.AUTO_RECALIBRATE = False) keeps counting trips -- guard_trips(model) -- and
-# leaves the decision to the caller (model.calibrate_activation_scales(frames) is the controlled way; reset_guard_trips(model)).
-AUTO_RECALIBRATE = _os.environ.get('SRCNN_AUTO_RECALIBRATE', '1') != '0'
-MAX_SHIFT_WIDENING = 10          # automatic re-calibration never lowers a tensor group's shift by more than this many bits in total (x1000)
+    return _with_fp32_fallback(
+        model,
+        lambda: collect_3d_batch(launch_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shapes, eval_thresh,
+                                                 class_index, dense_align, slot, solver)),
+        lambda: detect_3d_batch(model, im_left_data, im_right_data, im_info, calibs, im_shapes, eval_thresh, class_index,
+                                dense_align, slot, solver),
+        lambda: _note_guard_trip(model, im_left_data, slot))
 
 
 def guard_trips(model):
@@ -621,7 +666,6 @@ def _note_guard_trip(model, im_left_data, slot, may_recalibrate=True):
     and the caller is not streaming -- the offending frame, still the input of this slot's plan, is merged into the calibration (one
     fp32 forward; plans re-record their launch programs), unless that would widen some group by more than MAX_SHIFT_WIDENING bits
     beyond its first calibration: then the frame is an outlier, the scales stay, and only the counter says so."""
-    import logging
     log = logging.getLogger('stereo_rcnn_amd')
     w = model._weights
     if w is None:
@@ -633,8 +677,7 @@ def _note_guard_trip(model, im_left_data, slot, may_recalibrate=True):
         if first is None:
             first = w.first_shifts = dict(w.shifts)
         before = (dict(w.shifts), list(w.fuse_shortcut), dict(w.calibration_max), w.calib_epoch)
-        B, _, H, W = im_left_data.shape
-        plan = model._get_plan(int(B), int(H), int(W), slot)
+        plan = _plan_of(model, im_left_data, slot)[0]
         with torch.no_grad():
             plan.calibrate(merge=True)
         if any(first.get(g, k) - k > MAX_SHIFT_WIDENING for g, k in w.shifts.items()):
@@ -660,7 +703,6 @@ def _slot_streams(n):
     without bound -- and fresh streams per CALLER would run out of hardware queues, see streams.main_streams)."""
     # the serving regime of bench.py's headline (serving.py): branches stay on the main streams with n > 1, the hardware-queue
     # supply is checked, and the shipped throughput-tuned conv plans are adopted (once; MI355X only; matching shapes only)
-    from . import serving
     serving.enter(n)
     return _streams.main_streams(n, kind=_streams.MAIN_KIND if _streams.MAIN_KIND in _streams.KINDS else 'dedicated')
 
@@ -676,47 +718,35 @@ def detect_3d_stream(model, frames, pool=None, eval_thresh=0.05, class_index=1, 
     host/scipy arrangement."""
     prev_n = _streams.pairs_in_flight()
     try:
-        for objs in _detect_3d_stream(model, frames, pool, eval_thresh, class_index, dense_align, slots, solver):
-            yield objs
+        yield from _detect_3d_stream(model, frames, pool, eval_thresh, class_index, dense_align, slots, solver)
     finally:
         _streams.set_pairs_in_flight(prev_n)      # the plans go back to the caller's regime (one at a time: branches on side streams)
 
 
 def _detect_3d_stream(model, frames, pool, eval_thresh, class_index, dense_align, slots, solver):
     if solver == 'scipy':
-        for objs in _detect_3d_stream_scipy(model, frames, pool, eval_thresh, class_index, dense_align, min(slots, 2)):
-            yield objs
+        yield from _detect_3d_stream_scipy(model, frames, pool, eval_thresh, class_index, dense_align, min(slots, 2))
         return
-    from . import engine
     streams = _slot_streams(max(1, slots))
     inflight = collections.deque()
 
     retry_slot = len(streams)        # a buffer set no pair in flight can own: the fp32 re-run must not touch slots 0..n-1
 
     def finish(entry):
+        # when the SPLIT16 range guard of THIS pair tripped: the pair again on the exact fp32 engine, on the caller's stream and
+        # in its own slot -- the pairs still in flight keep their plans, 3-D stage buffers and images untouched
         st, frame = entry
-        try:
-            return collect_3d(st)
-        except engine.Split16RangeError:
-            if model.precision == 'f32':
-                raise
-            # the SPLIT16 range guard of THIS pair tripped: the pair again on the exact fp32 engine, on the caller's stream and
-            # in its own slot -- the pairs still in flight keep their plans, 3-D stage buffers and images untouched
-            prev, model.precision = model.precision, 'f32'
-            try:
-                if len(frame) == 3:
-                    objs = detect_3d_images(model, frame[0], frame[1], frame[2], eval_thresh, class_index, dense_align,
-                                            retry_slot, solver=solver)
-                else:
-                    objs = detect_3d(model, frame[0], frame[1], frame[2], frame[3], frame[4], eval_thresh, class_index, dense_align,
-                                     solver=solver, slot=retry_slot)
-            finally:
-                model.precision = prev
-            if len(frame) != 3:
-                # streamed: other pairs are in flight -- count the trip, never re-calibrate here (that synchronises the device and
-                # changes the scales under the pairs in flight); the caller re-calibrates between streams if it wants to
-                _note_guard_trip(model, frame[0], retry_slot, may_recalibrate=False)
-            return objs
+        if len(frame) == 3:
+            rerun = lambda: detect_3d_images(model, frame[0], frame[1], frame[2], eval_thresh, class_index, dense_align,
+                                             retry_slot, solver=solver)
+            note = None
+        else:
+            rerun = lambda: detect_3d(model, frame[0], frame[1], frame[2], frame[3], frame[4], eval_thresh, class_index,
+                                      dense_align, solver=solver, slot=retry_slot)
+            # streamed: other pairs are in flight -- count the trip, never re-calibrate here (that synchronises the device and
+            # changes the scales under the pairs in flight); the caller re-calibrates between streams if it wants to
+            note = lambda: _note_guard_trip(model, frame[0], retry_slot, may_recalibrate=False)
+        return _with_fp32_fallback(model, lambda: collect_3d(st), rerun, note)
 
     for k, frame in enumerate(frames):
         slot = k % len(streams)
@@ -724,17 +754,15 @@ def _detect_3d_stream(model, frames, pool, eval_thresh, class_index, dense_align
             yield finish(inflight.popleft())
         s = streams[slot]
         s.wait_stream(torch.cuda.current_stream())
-        with torch.no_grad(), torch.cuda.stream(s):
+        with torch.cuda.stream(s):
             if len(frame) == 3:
                 st = detect_3d_images(model, frame[0], frame[1], frame[2], eval_thresh, class_index, dense_align, slot, wait=False,
                                       solver=solver, async_host=True)
             else:
                 l, r, info, calib, im_shape = frame[:5]
                 scale = float(np.float32(frame[5])) if len(frame) > 5 else _scale32(info)
-                lazy = _lazy(model)
-                out = model(l, r, info, slot=slot, kpts=not lazy, alias_outputs=True)
-                st = launch_3d(out, l, r, info, scale, calib, im_shape, eval_thresh, class_index, dense_align, slot, solver,
-                               lazy=_plan_of(model, l, slot) if lazy else None, async_host=True)
+                st = _forward_and_launch(model, l, r, info, scale, calib, im_shape, eval_thresh, class_index, dense_align,
+                                         slot, solver, async_host=True)
         for older, _ in inflight:                              # solver='host': a host phase of every pair in flight whose device
             step_3d(older, block=False)                        # work has finished -- never waiting for one that has not
         inflight.append((st, frame))
@@ -751,8 +779,8 @@ class _Pair(object):
 def _detect_3d_stream_scipy(model, frames, pool, eval_thresh, class_index, dense_align, slots):
     """The scipy arrangement, staged: forward + decode + class NMS + record (GPU, async) -> borders + 4-DoF tasks (host ->
     pool, async) -> dense alignment (GPU, async) -> 3-DoF tasks (pool, async) -> results; every loop iteration launches the
-    next pair's forward and moves each pair in flight one stage on."""
-    from . import distributed as sdist
+    next pair's forward and moves each pair in flight one stage on.  Unlike the one-shot form it takes the detections out of
+    the packed record, computes the keypoint branch inside the forward and does not call check_range."""
     streams = _slot_streams(max(1, slots))
     inflight = collections.deque()
 
@@ -779,43 +807,24 @@ def _detect_3d_stream_scipy(model, frames, pool, eval_thresh, class_index, dense
             rec = p.rec_host.numpy()
             k = int(rec[0, 0])
             body = rec[1:k + 1]
-            dl = np.concatenate((body[:, 1:5], body[:, 0:1]), 1)
-            dr = np.concatenate((body[:, 5:9], body[:, 0:1]), 1)
-            do, kpts = body[:, 9:14].copy(), body[:, 14:19].copy()
-            p.dets = (dl, dr, do, kpts)
+            p.dets = (np.concatenate((body[:, 1:5], body[:, 0:1]), 1), np.concatenate((body[:, 5:9], body[:, 0:1]), 1),
+                      body[:, 9:14].copy(), body[:, 14:19].copy())
             if k == 0:
                 p.objs, p.stage = [], 9
                 return
-            inferred = kitti_utils.infer_boundary(im_shape, dl)
-            for i in range(k):
-                if kpts[i, 4] - kpts[i, 3] < 0.5 * (inferred[i, 1] - inferred[i, 0]):
-                    kpts[i, 3:5] = inferred[i]
-            p.cand = [i for i in range(k) if dl[i, -1] > eval_thresh]
-            p.alphas = [m.atan2(do[i, 3], do[i, 4]) for i in p.cand]
-            p.pending = pool.submit([(4, tuple(im_shape), calib.p2, calib.p3, (a, do[i, 0:3], dl[i, 0:4], dr[i, 0:4], kpts[i]))
-                                     for i, a in zip(p.cand, p.alphas)])
+            p.cand, p.alphas, tasks = _tasks_4dof(4, im_shape, calib, p.dets, eval_thresh)
+            p.pending = pool.submit(tasks)
             p.stage = 2
         elif p.stage == 2:                                     # 4-DoF results -> dense alignment on the GPU
-            dl, dr, do, kpts = p.dets
-            p.solved = []
-            for i, alpha, (status, state) in zip(p.cand, p.alphas, p.pending.get()):
-                if status > 0:
-                    p.solved.append({'box_left': dl[i, 0:4].copy(), 'box_right': dr[i, 0:4].copy(), 'score': float(dl[i, 4]),
-                                     'dim': do[i, 0:3].astype(np.float64), 'alpha': alpha,
-                                     'xyz': np.array(state[0:3], dtype=np.float64), 'theta': float(state[3]),
-                                     'kpts': kpts[i].copy(), 'aligned': False, 'xyz_init': np.array(state[0:3], dtype=np.float64),
-                                     'theta_init': float(state[3])})
+            p.solved = _solved_objects(p.dets, p.cand, p.alphas, p.pending.get())
             if not p.solved or not dense_align:
                 p.objs, p.stage = p.solved, 9
                 return
             l, r, info = p.frame[0], p.frame[1], p.frame[2]
-            dev = l.device
-            f32 = lambda rows: torch.tensor(np.asarray(rows), dtype=torch.float32).to(dev, non_blocking=True)
             with torch.no_grad(), torch.cuda.stream(p.stream):
-                succ, dis = align_parallel(calib, float(np.float32(p.frame[5])) if len(p.frame) > 5 else _scale32(info), l, r,
-                                           f32([o['box_left'] for o in p.solved]), f32([o['kpts'] for o in p.solved]),
-                                           f32([[o['xyz'][0], o['xyz'][1], o['xyz'][2], o['dim'][0], o['dim'][1], o['dim'][2],
-                                                 o['theta']] for o in p.solved]))
+                scale = float(np.float32(p.frame[5])) if len(p.frame) > 5 else _scale32(info)     # device read: before the copies
+                succ, dis = align_parallel(calib, scale, l, r, *(torch.tensor(rows, dtype=torch.float32).to(l.device, non_blocking=True)
+                                                                 for rows in _align_rows(p.solved)))
                 p.succ_host = torch.empty(succ.shape, dtype=succ.dtype, pin_memory=True)
                 p.dis_host = torch.empty(dis.shape, dtype=dis.dtype, pin_memory=True)
                 p.succ_host.copy_(succ, non_blocking=True)
@@ -825,40 +834,27 @@ def _detect_3d_stream_scipy(model, frames, pool, eval_thresh, class_index, dense
             p.stage = 3
         elif p.stage == 3:                                     # aligned disparities -> 3-DoF tasks
             p.event.synchronize()
-            succ, dis = check_status(p.succ_host.numpy()), p.dis_host.numpy()
-            p.todo = [i for i in range(len(p.solved)) if succ[i] > 0]
-            p.pending = pool.submit([(3, tuple(im_shape), calib.p2, calib.p3,
-                                      (_alpha32(p.solved[i]['alpha']), p.solved[i]['dim'], _f64(p.solved[i]['box_left']),
-                                       float(dis[i]), _f64(p.solved[i]['kpts']))) for i in p.todo])
+            succ = check_status(p.succ_host.numpy())
+            p.todo, tasks = _tasks_3dof(3, im_shape, calib, p.solved, succ, p.dis_host.numpy())
+            p.pending = pool.submit(tasks)
             p.stage = 4
         elif p.stage == 4:                                     # rectified poses
-            dis = p.dis_host.numpy()
-            for i, (state, z) in zip(p.todo, p.pending.get()):
-                o = p.solved[i]
-                o['xyz'] = np.array([state[0], state[1], z], dtype=np.float64)
-                o['theta'] = float(state[2])
-                o['aligned'] = True
-                o['disparity'] = float(dis[i])
+            _apply_3dof(p.solved, p.todo, p.pending.get(), p.dis_host.numpy())
             p.objs, p.stage = p.solved, 9
 
-    def drain_ready():
+    def advance_all(new=None):
+        for q in list(inflight):
+            if q.stage != 9:
+                advance(q)
+        if new is not None:
+            inflight.append(new)
         while inflight and inflight[0].stage == 9:
             yield inflight.popleft().objs
 
     for k, frame in enumerate(frames):
-        new = launch(k, frame)
-        for q in list(inflight):
-            if q.stage != 9:
-                advance(q)
-        inflight.append(new)
-        for objs in drain_ready():
-            yield objs
+        yield from advance_all(launch(k, frame))
     while inflight:
-        for q in list(inflight):
-            if q.stage != 9:
-                advance(q)
-        for objs in drain_ready():
-            yield objs
+        yield from advance_all()
 
 
 def write_kitti_results(result_dir, file_number, calib, objects):

@@ -369,6 +369,83 @@ def test_pipeline_falls_back_to_fp32_when_the_split16_range_is_exceeded(dev):
         assert np.array_equal(a['box_left'], b['box_left']) and np.array_equal(a['xyz'], b['xyz'])
 
 
+HOT = 64.0          # see _hot_frames
+HOT_SEEDS = (5, 6)
+
+
+def _hot_frames(dev, seeds):
+    """The fixture's 120 x 400 frames of `seeds` as one batch, as they are and with the images x HOT, on the device.  The
+    neighbouring fallback tests use x2000; their frames cannot serve a test that wants objects to compare: on the exact fp32
+    network (oracle.pipeline.detect_3d on the CPU) none of the seeds 3..12 keeps a solved object at x2000, nor at x200 -- the
+    saturated scores and boxes leave the 4-DoF solver nothing -- while these seeds keep two each at x64.  The scales chosen
+    from a frame leave its largest activation between 23x and 45x below the f16 overflow threshold (Plan.calibrate: a rounded
+    power of two around 32x), so x64 of the very frame the model was calibrated on is out of range."""
+    from stereo_rcnn_amd import fixture
+    parts = [fixture.make_inputs(seed, 120, 400, target_short=192) for seed in seeds]
+    l, r, info = (torch.cat([p[k] for p in parts], 0).to(dev) for k in range(3))
+    return (l, r, info), (l * HOT, r * HOT, info)
+
+
+def _calibrate_and_trip(mdl, cool, hot):
+    """The model's first forward (which chooses the scales) on the frames as they are; then: does `hot` trip the range guard?"""
+    from stereo_rcnn_amd import engine
+    with torch.no_grad():
+        mdl(*cool)
+        mdl.check_range()
+        mdl(*hot)
+    return engine.range_flag(reset=True)[0] > 0
+
+
+def _assert_same_objects(got, want):
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert np.array_equal(a['box_left'], b['box_left']) and np.array_equal(a['xyz'], b['xyz'])
+
+
+@pytest.mark.parametrize("solver", ['scipy', 'host_py'])
+def test_host_arrangement_falls_back_to_fp32_when_the_split16_range_is_exceeded(dev, solver):
+    """The reference's host arrangement packs no record: _detect_3d_scipy reads the range word itself (check_range) and detect_3d
+    redoes the pair on the exact fp32 engine -- the objects of asking for precision 'f32' directly.  Precondition, asserted
+    first: the frame trips the guard and the fp32 engine still finds an object in it."""
+    from oracle.dense_align import KITTI_DEMO_CALIB as calib
+    from stereo_rcnn_amd import engine, fixture, pipeline
+    mdl = _model(dev, fixture.make_state_dict(3))
+    cool, hot = _hot_frames(dev, HOT_SEEDS[:1])
+    tripped = _calibrate_and_trip(mdl, cool, hot)
+    args = (mdl,) + hot + (calib, (120, 400, 3))
+    mdl.precision = 'f32'
+    want = pipeline.detect_3d(*args, solver=solver)
+    mdl.precision = 'f16x3'
+    print('guard tripped: %s; objects on the fp32 engine: %d' % (tripped, len(want)))
+    assert tripped and len(want) > 0
+    got = pipeline.detect_3d(*args, solver=solver)        # default engine -> guard -> fp32 re-run
+    assert mdl.precision == 'f16x3' and engine.range_flag()[0] == 0
+    assert pipeline.guard_trips(mdl) == 1
+    _assert_same_objects(got, want)
+
+
+def test_batched_pipeline_falls_back_to_fp32_when_the_split16_range_is_exceeded(dev):
+    """detect_3d_batch, B = 2, both frames out of the f16 range: the shared forward's flag condemns the batch, which is redone
+    on the exact fp32 engine -- the object lists of asking for precision 'f32' directly.  Precondition, asserted first: the
+    batch trips the guard and the fp32 engine still finds an object in it."""
+    from oracle.dense_align import KITTI_DEMO_CALIB as calib
+    from stereo_rcnn_amd import engine, fixture, pipeline
+    mdl = _model(dev, fixture.make_state_dict(3))
+    cool, hot = _hot_frames(dev, HOT_SEEDS)
+    tripped = _calibrate_and_trip(mdl, cool, hot)
+    args = (mdl,) + hot + ([calib] * 2, [(120, 400, 3)] * 2)
+    mdl.precision = 'f32'
+    want = pipeline.detect_3d_batch(*args)
+    mdl.precision = 'f16x3'
+    print('guard tripped: %s; objects on the fp32 engine: %s' % (tripped, [len(o) for o in want]))
+    assert tripped and len(want) == 2 and sum(len(o) for o in want) > 0
+    got = pipeline.detect_3d_batch(*args)                 # default engine -> guard -> fp32 re-run of the batch
+    assert mdl.precision == 'f16x3' and engine.range_flag()[0] == 0
+    assert pipeline.guard_trips(mdl) == 1 and len(got) == 2
+    for g, w in zip(got, want):
+        _assert_same_objects(g, w)
+
+
 def test_repeated_range_trips_widen_the_activation_scales(dev):
     """the SPLIT16 scales come from the first forward's frame.  A stream of frames unlike it would trip the range guard
     on every pair and run at fp32-engine speed for good, silently.  pipeline._note_guard_trip: every trip is logged, and after
