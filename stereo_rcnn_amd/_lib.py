@@ -204,6 +204,18 @@ def ptr(t):
     return t.data_ptr()
 
 
+def int_array(values, ctype=c_int):
+    """C array of integers for a library call."""
+    values = [int(v) for v in values]
+    return (ctype * len(values))(*values)
+
+
+def ptr_array(tensors_or_ints):
+    """C array of device pointers for a library call: tensors (their data_ptr) or addresses."""
+    ptrs = [t if isinstance(t, int) else t.data_ptr() for t in tensors_or_ints]
+    return (c_void_p * len(ptrs))(*ptrs)
+
+
 def stream():
     """Handle of torch's current HIP stream: every launch goes where torch's allocator expects it."""
     return torch.cuda.current_stream().cuda_stream

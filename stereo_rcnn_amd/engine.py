@@ -740,6 +740,15 @@ def act_convert(x, x_fmt, y_fmt):
     return y
 
 
+def pyramid_roi_align(maps, hw, C, im_height, rois, n_rois, A, out, cstride, coffset, x_fmt=0, y_fmt=0, limit=None):
+    """ROIAlign over the four pyramid levels P2..P5 (level routing, lattice sampling, 2x2 average; srcnn_pyramid_roi_align): maps =
+    the levels' NHWC maps (tensors or device addresses) of sizes hw = [(h, w)] and C channels, rois (n_rois, 5) -> A x A x C per roi
+    into channels [coffset, coffset + C) of `out` rows of cstride channels.  limit: device int32 row limit, or None."""
+    _lib.check(_lib.lib().srcnn_pyramid_roi_align(_lib.ptr_array(maps), _lib.int_array(h for h, _ in hw), _lib.int_array(w for _, w in hw), C,
+                                                  im_height, rois.data_ptr(), n_rois, A, out.data_ptr(), cstride, coffset, x_fmt, y_fmt,
+                                                  None if limit is None else limit.data_ptr(), _lib.stream()), "srcnn_pyramid_roi_align")
+
+
 def subsample2(x, B, H, W, C, y, OH, OW):
     _lib.check(_lib.lib().srcnn_subsample2(x.data_ptr(), B, H, W, C, y.data_ptr(), OH, OW, _lib.stream()),
                "srcnn_subsample2")

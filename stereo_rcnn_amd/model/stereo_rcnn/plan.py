@@ -10,6 +10,7 @@ MI355X-first structure (not the reference's eager module tree):
   * concatenations (RPN left|right, ROI left|right) are channel-offset writes, never copies.
 Every arithmetic step is a call into libsrcnn_hip.so (see include/srcnn_hip.h).
 """
+import contextlib
 import ctypes
 import logging
 
@@ -19,6 +20,15 @@ from ... import _lib, engine, streams
 
 _log = logging.getLogger('stereo_rcnn_amd')
 from ..utils.config import cfg
+
+
+KPTS_RESULTS = ('kpts_prob', 'left_prob', 'right_prob')      # what the keypoint branch writes (absent from a kpts=False forward)
+
+
+def _fmt_of(precision):
+    """Activation format of the internal buffers under an engine: the f16x3 engine keeps activations in the SPLIT16 format between
+    convolutions so that both GEMM operands are DMA'd into LDS (csrc/conv_f16s.hip); the fp32 engine uses F32."""
+    return _lib.FMT_SPLIT16 if precision == 'f16x3' else _lib.FMT_F32
 
 
 def _bn_dict(sd, prefix):
@@ -143,7 +153,6 @@ class Plan(object):
         # fused RPN head (SPLIT16 engine): per level up to 8 planes of per-(eye, N tile) partial sums, (B * h * w, 24) floats each
         self.rpn_part = [torch.zeros((8, B * a * b, 24), dtype=torch.float32, device=dev) for a, b in self.rpn_shapes]   # zeroed: a plane count mismatch adds zeros, not garbage
         self.rpn_nparts = [0] * len(self.rpn_shapes)
-        self._rpn_fused = False
         self.probs = e(B, self.A, 2)
         self.deltas = e(B, self.A, 6)
         self.post = cfg.TEST.RPN_POST_NMS_TOP_N
@@ -185,7 +194,7 @@ class Plan(object):
         self.graphs = {}
         self.programs = {}      # (precision, kpts, branches on side streams) -> (native launch program handle, buffers it keeps alive)
         self._rec = None        # program being recorded right now
-        self.packed_fmt = -1    # format `packed` currently holds for the inputs of the NEXT run (-1: none, pack in trunk())
+        self.packed_fmt = -1    # format `packed` currently holds for the inputs of the NEXT run (-1: none, pack in trunk()): _ensure_packed
         self._src = (self.im_left, self.im_right)    # where trunk() packs the stem input from: this plan's own planes, or the caller's tensors (set_inputs)
         self.fmt = 0            # activation format of the internal buffers for the current/last run
         # independent branches of the forward (FPN laterals, small RPN levels, box head vs keypoint head) are
@@ -207,6 +216,44 @@ class Plan(object):
         if self._side is None:
             self._side = streams.side_streams(2, self.dev) or [None, None]
         return self._side
+
+    # ------------------------------------------------------------------ engine mode, stem input, non-conv stages
+    @contextlib.contextmanager
+    def _engine(self, precision, bind=True):
+        """A stretch of launches on one engine: sets engine.PRECISION (restored on the way out) and this plan's activation format.
+        bind: every launch of the stretch -- and the decode / pack calls the caller makes right after it on this thread -- report
+        range violations to this plan's word (it stays bound until the next forward binds its own)."""
+        prev, engine.PRECISION = engine.PRECISION, precision
+        self.fmt = _fmt_of(precision)
+        try:
+            if bind:
+                _lib.check(_lib.lib().srcnn_range_flag_bind(self.range_flag.data_ptr()), "srcnn_range_flag_bind")
+            yield
+        finally:
+            engine.PRECISION = prev
+
+    def _ensure_packed(self, f):
+        """Packs the stem input of the current sources in format f unless set_images() / pack_inputs() already wrote it so.  A
+        launch program being recorded never holds the pack: run() issues it eagerly, its list starts at the stem conv."""
+        if self.packed_fmt != f and self._rec is None:
+            self.pack_inputs(f)
+
+    def _packed_stale(self):
+        """`packed` no longer holds the next run's input: a forward consumed it, or new inputs arrived."""
+        self.packed_fmt = -1
+
+    def _call(self, fn, *args):
+        """A library function whose last argument is the stream, on the current one."""
+        _lib.check(getattr(_lib.lib(), fn)(*(args + (_lib.stream(),))), fn)
+
+    def _stage(self, names, fn, *args, passes=None, **kw):
+        """A NON-conv stage of the forward: fn(*args, **kw), unless engine.DEBUG_SKIP lists its name (or one of its names).
+        passes=(buffer, group): the stage hands its input's values through unchanged, so `buffer` holds a tensor of that scale
+        group afterwards (skipped or not: it keeps an earlier frame's result then)."""
+        if not any(n in engine.DEBUG_SKIP for n in ((names,) if isinstance(names, str) else names)):
+            fn(*args, **kw)
+        if passes is not None:
+            self._buf_shift[passes[0].data_ptr()] = self._k(passes[1])
 
     # ------------------------------------------------------------------ activation scales (SPLIT16 engine)
     def _k(self, group):
@@ -256,15 +303,16 @@ class Plan(object):
         stream of a layer, and the whole feature pyramid (mixed per roi by ROIAlign), share one scale each."""
         import math
         w = self.w
-        saved = (self.fmt, engine.PRECISION, self.overlap)
-        self.fmt, engine.PRECISION, self.overlap = _lib.FMT_F32, 'f32', False
+        saved = (self.fmt, self.overlap)
         self._calib = {}
         try:
-            self.launch_all()
-            torch.cuda.synchronize()
+            with self._engine('f32', bind=False):           # the caller's forward keeps the range word
+                self.overlap = False
+                self.launch_all()                           # (its trunk consumes the packed input: the next forward packs again)
+                torch.cuda.synchronize()
         finally:
             calib, self._calib = self._calib, None
-            self.fmt, engine.PRECISION, self.overlap = saved
+            self.fmt, self.overlap = saved
         if merge:
             for g, mx in w.calibration_max.items():
                 calib[g] = max(calib.get(g, 0.0), mx)
@@ -273,7 +321,6 @@ class Plan(object):
             # frame trip the range guard and fall back to the fp32 engine.  Stay uncalibrated; the next forward tries again.
             _log.warning('SPLIT16 activation scales NOT calibrated: the frame produced no finite non-zero stem output '
                          '(blank warm-up input?); the next forward calibrates again')
-            self.packed_fmt = -1
             return
         shifts = {}
         for g, mx in calib.items():
@@ -296,7 +343,6 @@ class Plan(object):
         w.calibrated = True
         w.calibration_max = calib
         w.calibration_frames = (getattr(w, 'calibration_frames', 0) + 1) if merge else 1
-        self.packed_fmt = -1
         _log.info('SPLIT16 activation scales calibrated on %d frame(s) (last: %dx%dx%d, max |stem| %.3g): shifts %s; projection '
                   'shortcuts fused: %s', w.calibration_frames, self.B, self.H, self.W, calib.get('stem', 0.0),
                   ' '.join('%s:%+d' % kv for kv in sorted(shifts.items())), fuse)
@@ -306,15 +352,12 @@ class Plan(object):
         w, N = self.w, self.N
         H, W = self.H, self.W
         f = self.fmt                                  # SPLIT16 activations (f16x3 engine) or F32
-        if self.packed_fmt != f:                      # set_images() / pack_inputs() already wrote the stem input in this format otherwise
-            engine.stem_pack_pair(self._src[0], self._src[1], self.packed, out_fmt=f)
-        self.packed_fmt = -1                          # consumed: the next forward packs again unless set_images() / pack_inputs() ran
+        self._ensure_packed(f)
+        self._packed_stale()                          # consumed
         sh, sw = self.stem_hw
         self._conv(w.stem, self.packed, N, H + 6, W + 8, self.stem_out, sh, sw, None, 'stem', x_cstride=4, x_fmt=f, name='stem')   # F32 out
         ph, pw = self.c1_hw
-        if 'maxpool' not in engine.DEBUG_SKIP:
-            engine.maxpool3x3s2_ceil(self.stem_out, N, sh, sw, 64, self.c1, ph, pw, y_fmt=f)
-        self._buf_shift[self.c1.data_ptr()] = self._k('stem')
+        self._stage('maxpool', engine.maxpool3x3s2_ceil, self.stem_out, N, sh, sw, 64, self.c1, ph, pw, y_fmt=f, passes=(self.c1, 'stem'))
         x, xh, xw, xg = self.c1, ph, pw, 'stem'
         for li, blocks in enumerate(w.layers):
             h, w_ = self.layer_hw[li]
@@ -379,37 +422,83 @@ class Plan(object):
         else:
             stream.wait_event(token)
 
-    def _fork(self, side):
-        self._wait(side, self._signal(torch.cuda.current_stream()))
-
     def _join(self, side):
         self._wait(torch.cuda.current_stream(), self._signal(side))
+
+    @contextlib.contextmanager
+    def _on(self, side):
+        """Issue the body on the stream `side`, forked from the current stream here (the caller joins it where the branch's results
+        are needed) -- or, side None (branches do not overlap in this run), inline."""
+        if side is None:
+            yield
+        else:
+            self._wait(side, self._signal(torch.cuda.current_stream()))       # fork
+            with torch.cuda.stream(side):
+                yield
+
+    # ------------------------------------------------------------------ stereo RPN
+    @property
+    def _feats(self):
+        return [self.p2, self.p3, self.p4, self.p5, self.p6]
+
+    @property
+    def _rpn_fused(self):
+        """RPN_Conv on both eyes AND the 24-channel head in one launch (SPLIT16 engine, _rpn_level)?"""
+        return bool(self.fmt and engine.RPN_HEAD_FUSION and engine.RPN_PAIR_LAUNCH)
+
+    def _rpn_schedule(self):
+        """The RPN launches of a forward in issue order: [(levels of one launch, the level whose smoothing conv it waits for)],
+        level 0 = P2 .. 4 = P6; P5 and P6 exist once the top layer ran (level 3).  Grouped launches (engine.RPN_GROUP, fused head
+        only): the levels wait for the last one of their group."""
+        grp = engine.RPN_GROUP if self._rpn_fused else None
+        if grp == 'all':
+            return [([0, 1, 2, 3, 4], 0)]
+        if grp == 'small':                         # P3 exists: P3..P6 in one launch, P2 by itself
+            return [([1, 2, 3, 4], 1), ([0], 0)]
+        return [([4], 3), ([3], 3), ([2], 2), ([1], 1), ([0], 0)]
+
+    def _rpn_launch(self, levels):
+        self._rpn_group(levels) if len(levels) > 1 else self._rpn_level(levels[0])
+
+    def _rpn_after(self, level, side):
+        """The RPN launches that wait for pyramid level `level`, on `side` (one fork: the side stream also waits for this level's
+        smooth conv) -- except the big P2 level, which stays on the main stream."""
+        todo = [levels for levels, after in self._rpn_schedule() if after == level]
+        if todo:
+            with self._on(None if 0 in todo[-1] else side):
+                for levels in todo:
+                    self._rpn_launch(levels)
+
+    def _rpn_planes(self, l, used):
+        """Partial-sum planes the fused launch of level l wrote, `used` = the (tile_mr, tile_nr, ...) it was given / reports."""
+        h, w_ = self.rpn_shapes[l]
+        # planes the launch wrote = (eye, N tile) pairs of the tile that RAN: the library runs a head2 launch on the 128x128
+        # 8-wave tile when asked for exactly that (or, without a request, for small M), on the 256x256 tile otherwise
+        # (conv_mfma.hip: plan_for) -- whatever else the descriptor asked for (ADVICE r5)
+        ran_small = (used[0] == 2 and used[1] == 2) or (used[0] <= 0 and 2 * self.B * h * w_ < 256 * 8)
+        return 2 * (self.w.rpn_conv_pair.cout // (128 if ran_small else 256))
 
     def _rpn_level(self, l):
         """RPN_Conv on left and right maps of level l into [left 512 | right 512], fused 1x1 heads, scoring."""
         w, B, f = self.w, self.B, self.fmt
-        feats = [self.p2, self.p3, self.p4, self.p5, self.p6]
+        x = self._feats[l]
         h, w_ = self.rpn_shapes[l]
         cat, hd = self.rpn_cat[l], self.rpn_hd[l]
         if self._rpn_fused:
             # RPN_Conv on both eyes AND the 24-channel head (RPN_cls_score | RPN_bbox_pred_left_right over [left 512 | right 512],
             # stereo_rpn.py:77-91) in one launch: the head runs in the conv's epilogue as a second GEMM on each tile and leaves
             # partial sums per (eye, N tile); the (B, h, w, 1024) tensor is neither written nor read, five head launches are gone
-            used = self._conv(w.rpn_conv_pair, feats[l], 2 * B, h, w_, None, h, w_, 'P', 'rpn', x_fmt=f, name='rpn_conv+head.P%d' % (l + 2),
+            used = self._conv(w.rpn_conv_pair, x, 2 * B, h, w_, None, h, w_, 'P', 'rpn', x_fmt=f, name='rpn_conv+head.P%d' % (l + 2),
                               head2=(w.rpn_head, self.rpn_part[l], 8))
-            # planes the launch wrote = (eye, N tile) pairs of the tile that RAN: the library runs a head2 launch on the 128x128
-            # 8-wave tile when asked for exactly that (or, without a request, for small M), on the 256x256 tile otherwise
-            # (conv_mfma.hip: plan_for) -- whatever else the descriptor asked for (ADVICE r5)
-            ran_small = (used[0] == 2 and used[1] == 2) or (used[0] <= 0 and 2 * B * h * w_ < 256 * 8)
-            self.rpn_nparts[l] = 2 * (w.rpn_conv_pair.cout // (128 if ran_small else 256))
+            self.rpn_nparts[l] = self._rpn_planes(l, used)
             return
         if f and engine.RPN_PAIR_LAUNCH:       # SPLIT16 engine: both eyes in one launch (conv mode 2: the right half lands 512 channels further)
-            self._conv(w.rpn_conv_pair, feats[l], 2 * B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=0, x_fmt=f, y_fmt=f,
+            self._conv(w.rpn_conv_pair, x, 2 * B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=0, x_fmt=f, y_fmt=f,
                        name='rpn_conv.P%d' % (l + 2))
         else:
-            self._conv(w.rpn_conv, feats[l], B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=0, x_fmt=f, y_fmt=f,
+            self._conv(w.rpn_conv, x, B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=0, x_fmt=f, y_fmt=f,
                        name='rpn_conv.P%d' % (l + 2))
-            self._conv(w.rpn_conv, feats[l], B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=512,
+            self._conv(w.rpn_conv, x, B, h, w_, cat, h, w_, 'P', 'rpn', y_cstride=1024, y_coffset=512,
                        x_offset_elems=B * h * w_ * 256, x_fmt=f, y_fmt=f, name='rpn_conv.P%d' % (l + 2))
         self._conv(w.rpn_head, cat, B, h, w_, hd, h, w_, 'rpn', None, x_fmt=f, name='rpn_head.P%d' % (l + 2))
 
@@ -417,111 +506,77 @@ class Plan(object):
         """RPN_Conv + fused head of several pyramid levels in ONE grouped launch (shared weights; srcnn_conv2d_group): every level's
         partial planes are the bits its own launch would write."""
         w, B, f = self.w, self.B, self.fmt
-        feats = [self.p2, self.p3, self.p4, self.p5, self.p6]
         tile = engine.RPN_GROUP_TILE
         ki, ko = self._k('P'), self._k('rpn')
         probs = []
         for l in levels:
             h, w_ = self.rpn_shapes[l]
-            probs.append(((w.rpn_conv_pair, feats[l], 2 * B, h, w_, None, h, w_),
+            probs.append(((w.rpn_conv_pair, self._feats[l], 2 * B, h, w_, None, h, w_),
                           dict(x_fmt=f, head2=(w.rpn_head, self.rpn_part[l], 8), in_shift=ki, out_shift=ko, precision=engine.PRECISION,
                                name='rpn_conv+head.P%d' % (l + 2))))
-            self.rpn_nparts[l] = 2 * (w.rpn_conv_pair.cout // (64 * tile[1]))
+            self.rpn_nparts[l] = self._rpn_planes(l, tile)
         engine.conv_group(probs, tile, name='rpn_conv+head.P%s' % '+'.join(str(l + 2) for l in levels))
 
     def _rpn_scores(self):
         """Pair softmax + NHWC flatten of every level's head output into probs / deltas (stereo_rpn.py:81-91): one launch for all
         five levels, after the last of them (on whatever stream it ran) has been joined."""
         nl = len(self.rpn_shapes)
-        hw = (ctypes.c_int * nl)(*[a * b for a, b in self.rpn_shapes])
-        if 'rpn_scores' in engine.DEBUG_SKIP:
-            return
+        hw = _lib.int_array(a * b for a, b in self.rpn_shapes)
         if self._rpn_fused:
-            parts = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in self.rpn_part])
-            npl = (ctypes.c_int * nl)(*self.rpn_nparts)
-            planes = (ctypes.c_longlong * nl)(*[t.numel() // 8 for t in self.rpn_part])
-            _lib.check(_lib.lib().srcnn_rpn_score_parts(parts, npl, planes, hw, nl, self.B, self.w.rpn_head.bias.data_ptr(), self.probs.data_ptr(),
-                                                        self.deltas.data_ptr(), self.A, _lib.stream()), "srcnn_rpn_score_parts")
-            return
-        heads = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in self.rpn_hd])
-        _lib.check(_lib.lib().srcnn_rpn_score_levels(heads, hw, nl, self.B, 24, self.probs.data_ptr(), self.deltas.data_ptr(), self.A,
-                                                     _lib.stream()), "srcnn_rpn_score_levels")
+            self._stage('rpn_scores', self._call, 'srcnn_rpn_score_parts', _lib.ptr_array(self.rpn_part), _lib.int_array(self.rpn_nparts),
+                        _lib.int_array((t.numel() // 8 for t in self.rpn_part), ctypes.c_longlong), hw, nl, self.B,
+                        self.w.rpn_head.bias.data_ptr(), self.probs.data_ptr(), self.deltas.data_ptr(), self.A)
+        else:
+            self._stage('rpn_scores', self._call, 'srcnn_rpn_score_levels', _lib.ptr_array(self.rpn_hd), hw, nl, self.B, 24, self.probs.data_ptr(),
+                        self.deltas.data_ptr(), self.A)
+
+    def _lateral(self, i, out, up=None):
+        """Lateral 1x1 conv of top-down step i (0: c4, 1: c3, 2: c2) into `out`; up=(top, th, tw): with the top-down addition of
+        the coarser map `top` in its epilogue (`out` is then the SPLIT16 sum, not the lateral map)."""
+        f = self.fmt
+        h, w_ = self.layer_hw[2 - i]
+        kw = {} if up is None else dict(y_fmt=f, up=tuple(up) + (f,))
+        self._conv(self.w.lateral[i], self.c[2 - i], self.N, h, w_, out, h, w_, 'L%d' % (3 - i), 'P', x_fmt=f,
+                   name='fpn.lateral%d' % (i + 1), **kw)     # lateral stays F32 (at the pyramid's scale: it is added to `top`)
 
     def fpn_rpn(self):
         """FPN top-down path (stereo_rcnn.py:161-168) with the stereo RPN head (stereo_rpn.py:73-95) of every
-        level started as soon as that level exists: laterals on side stream 0, RPN levels 6..3 on side stream 1,
+        level started as soon as that level exists (_rpn_schedule): laterals on side stream 0, RPN levels 6..3 on side stream 1,
         the big P2 level on the main stream."""
         w, N, f = self.w, self.N, self.fmt
-        (h2, w2), (h3, w3), (h4, w4), (h5, w5) = self.layer_hw
-        c2, c3, c4, c5 = self.c
-        self._rpn_fused = bool(f and engine.RPN_HEAD_FUSION and engine.RPN_PAIR_LAUNCH)
+        h5, w5 = self.layer_hw[3]
         par = self._par()
         s_lat, s_rpn = self.side if par else (None, None)
         lat_done = []
         if par:
-            self._fork(s_lat)
-            with torch.cuda.stream(s_lat):
-                for i, (cin, (h, w_)) in enumerate(((c4, (h4, w4)), (c3, (h3, w3)), (c2, (h2, w2)))):
-                    self._conv(w.lateral[i], cin, N, h, w_, self.lat[i], h, w_, 'L%d' % (3 - i), 'P', x_fmt=f,
-                               name='fpn.lateral%d' % (i + 1))     # lateral stays F32 (at the pyramid's scale: it is added to `top`)
+            with self._on(s_lat):
+                for i in range(3):
+                    self._lateral(i, self.lat[i])
                     lat_done.append(self._signal(s_lat))
-        self._conv(w.toplayer, c5, N, h5, w5, self.p5, h5, w5, 'L4', 'P', x_fmt=f, y_fmt=f, name='fpn.toplayer')
+        self._conv(w.toplayer, self.c[3], N, h5, w5, self.p5, h5, w5, 'L4', 'P', x_fmt=f, y_fmt=f, name='fpn.toplayer')
         h6, w6 = self.rpn_shapes[4]
-        if 'subsample' not in engine.DEBUG_SKIP:
-            engine.subsample2(self.p5, N, h5, w5, 256, self.p6, h6, w6)                          # stereo_rcnn.py:168
-        self._buf_shift[self.p6.data_ptr()] = self._k('P')
-        # grouped RPN launches (engine.RPN_GROUP): the levels wait for the last one of their group
-        grp = engine.RPN_GROUP if (self._rpn_fused and engine.RPN_GROUP in ('all', 'small')) else None
-        if grp:
-            pass
-        elif par:
-            self._fork(s_rpn)
-            with torch.cuda.stream(s_rpn):
-                self._rpn_level(4)
-                self._rpn_level(3)
-        else:
-            self._rpn_level(4)
-            self._rpn_level(3)
-        tops = [(self.p5, h5, w5), None, None]
-        for i, (cin, (h, w_), out) in enumerate(((c4, (h4, w4), self.p4), (c3, (h3, w3), self.p3),
-                                                 (c2, (h2, w2), self.p2))):
-            top, th, tw = tops[i]
+        self._stage('subsample', engine.subsample2, self.p5, N, h5, w5, 256, self.p6, h6, w6, passes=(self.p6, 'P'))   # stereo_rcnn.py:168
+        self._rpn_after(3, s_rpn)
+        fused = bool(f and engine.UPSAMPLE_FUSION) and not par
+        top = (self.p5, h5, w5)
+        for i, out in enumerate((self.p4, self.p3, self.p2)):
+            h, w_ = self.layer_hw[2 - i]
             if par:
                 self._wait(torch.cuda.current_stream(), lat_done[i])
-            elif f and engine.UPSAMPLE_FUSION:
+            elif fused:
                 # lateral conv + top-down addition in one launch (srcnn_conv_desc.up_top): the float32 lateral map is neither written
                 # nor read back, three launches and 0.4 GB per pair go; bit-identical to the two-launch form below
-                self._conv(w.lateral[i], cin, N, h, w_, self.summed[i], h, w_, 'L%d' % (3 - i), 'P', x_fmt=f, y_fmt=f,
-                           up=(top, th, tw, f), name='fpn.lateral%d' % (i + 1))
+                self._lateral(i, self.summed[i], up=top)
             else:
-                self._conv(w.lateral[i], cin, N, h, w_, self.lat[i], h, w_, 'L%d' % (3 - i), 'P', x_fmt=f, name='fpn.lateral%d' % (i + 1))
-            if (par or not (f and engine.UPSAMPLE_FUSION)) and 'upsample_add' not in engine.DEBUG_SKIP:
-                engine.upsample_add(top, th, tw, self.lat[i], N, h, w_, 256, self.summed[i], top_fmt=f, y_fmt=f)   # stereo_rcnn.py:91-108
+                self._lateral(i, self.lat[i])
+            if not fused:
+                self._stage('upsample_add', engine.upsample_add, top[0], top[1], top[2], self.lat[i], N, h, w_, 256, self.summed[i],
+                            top_fmt=f, y_fmt=f)   # stereo_rcnn.py:91-108
             if self._calib is not None:
                 self._note('P', self.summed[i])
             self._conv(w.smooth[i], self.summed[i], N, h, w_, out, h, w_, 'P', 'P', x_fmt=f, y_fmt=f, name='fpn.smooth%d' % (i + 1))
-            if i + 1 < 3:
-                tops[i + 1] = (out, h, w_)
-            level = 2 - i                        # p4 -> RPN level 2, p3 -> 1, p2 -> 0
-            if grp:
-                if grp == 'small' and level == 1:               # P3 exists: P3..P6 in one launch (on the side stream when forked)
-                    if par:
-                        self._fork(s_rpn)
-                        with torch.cuda.stream(s_rpn):
-                            self._rpn_group([1, 2, 3, 4])
-                    else:
-                        self._rpn_group([1, 2, 3, 4])
-                elif level == 0:
-                    if grp == 'all':
-                        self._rpn_group([0, 1, 2, 3, 4])
-                    else:
-                        self._rpn_level(0)
-            elif par and level > 0:
-                self._fork(s_rpn)                # side stream also waits for this level's smooth conv
-                with torch.cuda.stream(s_rpn):
-                    self._rpn_level(level)
-            else:
-                self._rpn_level(level)
+            top = (out, h, w_)
+            self._rpn_after(2 - i, s_rpn)        # p4 -> RPN level 2, p3 -> 1, p2 -> 0
         if par:
             self._join(s_lat)
             self._join(s_rpn)
@@ -535,46 +590,28 @@ class Plan(object):
             self.overlap = prev
 
     def rpn(self):
-        """(kept for stage timing tools) the RPN head alone, serial."""
-        self._rpn_fused = bool(self.fmt and engine.RPN_HEAD_FUSION and engine.RPN_PAIR_LAUNCH)
-        if self._rpn_fused and engine.RPN_GROUP == 'all':
-            self._rpn_group([0, 1, 2, 3, 4])
-        elif self._rpn_fused and engine.RPN_GROUP == 'small':
-            self._rpn_group([1, 2, 3, 4])
-            self._rpn_level(0)
-        else:
-            for l in range(5):
-                self._rpn_level(l)
+        """(kept for stage timing tools) the RPN head alone, serial: the schedule's grouped launch first, then single levels from P2 up."""
+        for levels, _ in sorted(self._rpn_schedule(), key=lambda e: (len(e[0]) == 1, e[0])):
+            self._rpn_launch(levels)
         self._rpn_scores()
 
     def proposals(self):
-        if 'proposals' in engine.DEBUG_SKIP:
-            return
-        L = _lib.lib()
-        nl = len(self.rpn_shapes)
-        hw = (ctypes.c_int * (2 * nl))(*[int(v) for s in self.rpn_shapes for v in s])
+        self._stage('proposals', self._proposal_layer)
+
+    def _proposal_layer(self):
         pre = cfg.TEST.RPN_PRE_NMS_TOP_N
-        ws = _lib.workspace(L.srcnn_proposal_workspace_bytes(self.B, self.A, pre, self.post), self.dev, "proposal")
-        _lib.check(L.srcnn_proposal_layer(self.probs.data_ptr(), self.deltas.data_ptr(), self.B, self.A, hw, nl,
-                                          self.im_info.data_ptr(), pre, self.post, float(cfg.TEST.RPN_NMS_THRESH),
-                                          self.rois_left.data_ptr(), self.rois_right.data_ptr(),
-                                          self.num_valid.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
-                   "srcnn_proposal_layer")
+        ws = _lib.workspace(_lib.lib().srcnn_proposal_workspace_bytes(self.B, self.A, pre, self.post), self.dev, "proposal")
+        self._call('srcnn_proposal_layer', self.probs.data_ptr(), self.deltas.data_ptr(), self.B, self.A,
+                   _lib.int_array(int(v) for s in self.rpn_shapes for v in s), len(self.rpn_shapes), self.im_info.data_ptr(), pre, self.post,
+                   float(cfg.TEST.RPN_NMS_THRESH), self.rois_left.data_ptr(), self.rois_right.data_ptr(), self.num_valid.data_ptr(),
+                   ws.data_ptr(), ws.numel())
 
     def _pyramid(self, right, rois, A, out, cstride, coffset, n_rois=None, limit=None):
-        if 'roi_align' in engine.DEBUG_SKIP or ('roi_align%d' % A) in engine.DEBUG_SKIP:
-            return
-        maps = [self.p2, self.p3, self.p4, self.p5]
         hw = self.rpn_shapes[:4]
-        ptrs = (ctypes.c_void_p * 4)()
-        for l in range(4):
-            h, w_ = hw[l]
-            ptrs[l] = maps[l].data_ptr() + (4 * self.B * h * w_ * 256 if right else 0)
-        mh = (ctypes.c_int * 4)(*[h for h, _ in hw])
-        mw = (ctypes.c_int * 4)(*[w_ for _, w_ in hw])
-        _lib.check(_lib.lib().srcnn_pyramid_roi_align(ptrs, mh, mw, 256, float(self.H), rois.data_ptr(), self.R if n_rois is None else n_rois, A,
-                                                      out.data_ptr(), cstride, coffset, self.fmt, self.fmt,
-                                                      None if limit is None else limit.data_ptr(), _lib.stream()), "srcnn_pyramid_roi_align")
+        # the right eye's maps are the second half of the 2B-image batch
+        maps = [m.data_ptr() + (4 * self.B * h * w_ * 256 if right else 0) for m, (h, w_) in zip(self._feats, hw)]
+        self._stage(('roi_align', 'roi_align%d' % A), engine.pyramid_roi_align, maps, hw, 256, float(self.H), rois,
+                    self.R if n_rois is None else n_rois, A, out, cstride, coffset, self.fmt, self.fmt, limit)
 
     def box_head(self):
         w, R, f = self.w, self.R, self.fmt
@@ -584,9 +621,8 @@ class Plan(object):
         self._conv(w.top0, self.sem, R, 1, 1, self.h1, 1, 1, 'P', 'h1', x_fmt=f, y_fmt=f, name='box.top0')   # 7x7/7 conv == GEMM (resnet.py:257)
         self._conv(w.top3, self.h1, R, 1, 1, self.h2, 1, 1, 'h1', 'h2', x_fmt=f, y_fmt=f, name='box.top3')
         self._conv(w.fc, self.h2, R, 1, 1, self.fc, 1, 1, 'h2', None, x_fmt=f, name='box.fc')
-        if 'box_tail' not in engine.DEBUG_SKIP:
-            _lib.check(_lib.lib().srcnn_box_head_tail(self.fc.data_ptr(), R, w.n_bbox, w.n_dim, w.n_cls, w.fc.cout, self.bbox_pred.data_ptr(),
-                                                  self.dim_orien.data_ptr(), self.cls_prob.data_ptr(), _lib.stream()), "srcnn_box_head_tail")
+        self._stage('box_tail', self._call, 'srcnn_box_head_tail', self.fc.data_ptr(), R, w.n_bbox, w.n_dim, w.n_cls, w.fc.cout, self.bbox_pred.data_ptr(),
+                    self.dim_orien.data_ptr(), self.cls_prob.data_ptr())
 
     def kpts_head(self, rois=None, n_rois=None, limit=None, outs=None):
         """Keypoint branch (stereo_rcnn.py:260-271).  Default: all R rois of the forward.  rois / n_rois / limit: the lazy form
@@ -619,9 +655,8 @@ class Plan(object):
             self._conv(w.kpts_up, x, R, s, s, self.kp_up, s, s, g, 'kup', x_fmt=f, y_fmt=f, name='kpts.deconv', **lim(s * s))
             self._conv(w.kpts_class, self.kp_up, R, G, G, self.kp_logits, G, G, 'kup', None, x_fmt=f, name='kpts.class', **lim(G * G))
         kp, lp, rp = (self.kpts_prob, self.left_prob, self.right_prob) if outs is None else outs
-        if 'kpts_tail' not in engine.DEBUG_SKIP:
-            _lib.check(_lib.lib().srcnn_kpts_tail(self.kp_logits.data_ptr(), R, G, kp.data_ptr(), lp.data_ptr(), rp.data_ptr(),
-                                                  None if limit is None else limit.data_ptr(), _lib.stream()), "srcnn_kpts_tail")
+        self._stage('kpts_tail', self._call, 'srcnn_kpts_tail', self.kp_logits.data_ptr(), R, G, kp.data_ptr(), lp.data_ptr(), rp.data_ptr(),
+                    None if limit is None else limit.data_ptr())
 
     def kpts_for_kept(self, rois_left_b, keep_idx, num, im_info_b, det_kpts, precision):
         """The keypoint head for the detections of ONE image that survived class NMS (postprocess.class_nms_device: keep_idx
@@ -631,7 +666,6 @@ class Plan(object):
         values the full head gives them up to the engine's own plan-to-plan rounding (the row-limited launches are tuned to
         other tile / split-K plans, which add the K products in another order: probabilities within ~1e-5 relative, like any
         two tunings of one layer); rows of the 300 that the reference's scripts never read are skipped."""
-        L = _lib.lib()
         n = int(keep_idx.shape[0])
         assert n == self.post and rois_left_b.is_contiguous()
         # the decode kernel dereferences im_info: a host tensor (which forward(), decode_detections and set_inputs all accept)
@@ -639,21 +673,13 @@ class Plan(object):
         im_info_b = im_info_b.reshape(-1, 3)[0:1].to(device=self.dev, dtype=torch.float32).contiguous()
         for name, tns in (('rois_left_b', rois_left_b), ('keep_idx', keep_idx), ('num', num), ('det_kpts', det_kpts)):
             assert tns.is_cuda and tns.is_contiguous(), "kpts_for_kept: %s must be a contiguous device tensor" % name
-        prev, engine.PRECISION = engine.PRECISION, precision
-        self.fmt = _lib.FMT_SPLIT16 if precision == 'f16x3' else _lib.FMT_F32
         # the tower's range-guard reports belong to this plan's forward (the record packed after this call carries the word)
-        _lib.check(L.srcnn_range_flag_bind(self.range_flag.data_ptr()), "srcnn_range_flag_bind")
-        try:
-            _lib.check(L.srcnn_gather_rows(rois_left_b.data_ptr(), keep_idx.data_ptr(), n, 5, self.kp_rois.data_ptr(), _lib.stream()),
-                       "srcnn_gather_rows")
+        with self._engine(precision):
+            self._call('srcnn_gather_rows', rois_left_b.data_ptr(), keep_idx.data_ptr(), n, 5, self.kp_rois.data_ptr())
             self.kpts_head(rois=self.kp_rois, n_rois=n, limit=num if self.fmt else None, outs=(self.kp_prob, self.kp_left, self.kp_right))
-            G = cfg.KPTS_GRID
-            _lib.check(L.srcnn_decode_kept_kpts(rois_left_b.data_ptr(), self.kp_prob.data_ptr(), self.kp_left.data_ptr(),
-                                                self.kp_right.data_ptr(), keep_idx.data_ptr(), num.data_ptr(),
-                                                im_info_b.data_ptr(), n, G, det_kpts.data_ptr(), _lib.stream()),
-                       "srcnn_decode_kept_kpts")
-        finally:
-            engine.PRECISION = prev
+            self._call('srcnn_decode_kept_kpts', rois_left_b.data_ptr(), self.kp_prob.data_ptr(), self.kp_left.data_ptr(),
+                       self.kp_right.data_ptr(), keep_idx.data_ptr(), num.data_ptr(), im_info_b.data_ptr(), n, cfg.KPTS_GRID,
+                       det_kpts.data_ptr())
 
     def __del__(self):
         # run() / kpts_for_kept() leave this plan's range word bound on the thread (the decode / pack calls that follow a forward
@@ -668,18 +694,13 @@ class Plan(object):
     def heads(self, kpts=True):
         """Box head (M=300 GEMMs, poor chip fill on their own) runs beside the keypoint tower (kpts=False: box head only --
         the keypoints then come from kpts_for_kept after class NMS)."""
-        if not kpts:
+        side = self.side[0] if kpts and self._par() else None
+        with self._on(side):
             self.box_head()
-        elif self._par():
-            side = self.side[0]
-            self._fork(side)
-            with torch.cuda.stream(side):
-                self.box_head()
+        if kpts:
             self.kpts_head()
+        if side is not None:
             self._join(side)
-        else:
-            self.box_head()
-            self.kpts_head()
 
     def launch_all(self, kpts=True):
         self.trunk()
@@ -700,7 +721,7 @@ class Plan(object):
             self._src = (self.im_left, self.im_right)
         else:
             self._src = (im_left, im_right)
-        self.packed_fmt = -1
+        self._packed_stale()
         self.im_info.copy_(im_info.view(self.B, 3), non_blocking=True)
 
     def pack_inputs(self, fmt):
@@ -714,8 +735,7 @@ class Plan(object):
         them) AND its packed stem input, one pass per eye (srcnn_preprocess); trunk() then skips the stem_pack launches.
         Returns im_scale."""
         assert self.B == 1, "set_images feeds one stereo pair"
-        fmt = _lib.FMT_SPLIT16 if precision == 'f16x3' else _lib.FMT_F32
-        L = _lib.lib()
+        fmt = _fmt_of(precision)
         scale = None
         per_image = (self.H + 6) * (self.W + 8) * 4 * 4
         for i, (img, planar) in enumerate(((img_left_u8, self.im_left), (img_right_u8, self.im_right))):
@@ -727,8 +747,7 @@ class Plan(object):
             H0, W0 = int(img.shape[0]), int(img.shape[1])
             OH, OW, scale = engine.preprocess_size(H0, W0, target_short)
             assert (OH, OW) == (self.H, self.W), "plan was built for another input size"
-            _lib.check(L.srcnn_preprocess(img.data_ptr(), H0, W0, scale, planar.data_ptr(), OH, OW,
-                                          self.packed.data_ptr() + i * per_image, fmt, _lib.stream()), "srcnn_preprocess")
+            self._call('srcnn_preprocess', img.data_ptr(), H0, W0, scale, planar.data_ptr(), OH, OW, self.packed.data_ptr() + i * per_image, fmt)
         self.im_info.copy_(torch.tensor([[self.H, self.W, scale]], dtype=torch.float32), non_blocking=True)
         self.packed_fmt = fmt
         self._src = (self.im_left, self.im_right)      # the planes the preprocessing just wrote
@@ -740,8 +759,7 @@ class Plan(object):
         L = _lib.lib()
         self.launch_all(kpts)                 # warm-up: tunes the plans, sizes every workspace, splits the weights
         torch.cuda.synchronize()
-        self.packed_fmt = self.fmt            # `packed` holds this input in the run's format: the recorded list starts behind the pack
-        prog = L.srcnn_program_create()
+        prog = L.srcnn_program_create()           # (the recorded list starts behind the pack: _ensure_packed)
         refs = []
         _lib._recording_refs = refs
         _lib.check(L.srcnn_program_begin(prog, torch.cuda.current_stream().cuda_stream), "srcnn_program_begin")
@@ -764,50 +782,34 @@ class Plan(object):
         """precision: 'f32' (exact fp32 MFMA engine) or 'f16x3' (3-term split on the f16 MFMA).
         use_program: replay the forward from the native launch list (recorded on first use) instead of walking the Python
         launch code -- same launches, same streams, same results."""
-        prev = engine.PRECISION
-        engine.PRECISION = precision
-        # every launch of this forward -- and the decode / pack calls the caller makes right after it on this thread -- report
-        # range violations to this plan's word (it stays bound until the next forward binds its own)
-        _lib.check(_lib.lib().srcnn_range_flag_bind(self.range_flag.data_ptr()), "srcnn_range_flag_bind")
-        # the f16x3 engine keeps activations in the SPLIT16 format between convolutions so that
-        # both GEMM operands are DMA'd into LDS (csrc/conv_f16s.hip); the fp32 engine uses F32
-        self.fmt = _lib.FMT_SPLIT16 if precision == 'f16x3' else _lib.FMT_F32
-        if self.fmt and engine.ACT_SCALES and not self.w.calibrated:
-            self.calibrate()               # once per weights: the scales of every SPLIT16 tensor group, from this first input
-        epoch = (self.w.calib_epoch, engine.tune_mode_key(), engine.PLAN_EPOCH)
-        if self._epoch != epoch:      # the scales, or the tuner's objective (= the plan set), changed since this plan recorded its launch lists
-            for prog, _ in self.programs.values():
-                _lib.lib().srcnn_program_destroy(prog)
-            self.programs, self.graphs, self._epoch = {}, {}, epoch
-        try:
+        with self._engine(precision):
+            if self.fmt and engine.ACT_SCALES and not self.w.calibrated:
+                self.calibrate()               # once per weights: the scales of every SPLIT16 tensor group, from this first input
+            epoch = (self.w.calib_epoch, engine.tune_mode_key(), engine.PLAN_EPOCH)
+            if self._epoch != epoch:      # the scales, or the tuner's objective (= the plan set), changed since this plan recorded its launch lists
+                for prog, _ in self.programs.values():
+                    _lib.lib().srcnn_program_destroy(prog)
+                self.programs, self.graphs, self._epoch = {}, {}, epoch
             if use_program and not use_graph:
                 # the stem input is packed here, eagerly, from wherever the inputs are (set_inputs keeps references instead of
                 # copying; set_images wrote `packed` itself); the recorded list starts at the stem conv
                 ent = self.programs.get(self.program_key(precision, kpts))      # one list per (engine, branch, stream regime)
-                if ent is None:
-                    prog = self._record_program(precision, kpts)             # (its warm-up run packs and consumes the input)
-                    self.packed_fmt = -1
-                else:
-                    prog = ent[0]
-                if self.packed_fmt != self.fmt:
-                    self.pack_inputs(self.fmt)
-                self.packed_fmt = -1
+                prog = ent[0] if ent is not None else self._record_program(precision, kpts)   # (its warm-up run packs and consumes the input)
+                self._ensure_packed(self.fmt)
+                self._packed_stale()
                 _lib.check(_lib.lib().srcnn_program_run(prog, torch.cuda.current_stream().cuda_stream), "srcnn_program_run")
-                return
-            if not use_graph or not kpts:
+            elif not use_graph or not kpts:
                 self.launch_all(kpts)
-                return
-            self.packed_fmt = -1                  # a captured graph always contains the stem_pack launches
-            if precision not in self.graphs:
-                self.launch_all()                 # warm-up: sizes every workspace, splits weights, before capture
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self.launch_all()
-                self.graphs[precision] = g
-            self.graphs[precision].replay()
-        finally:
-            engine.PRECISION = prev
+            else:
+                self._packed_stale()                  # a captured graph always contains the stem_pack launches
+                if precision not in self.graphs:
+                    self.launch_all()                 # warm-up: sizes every workspace, splits weights, before capture
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self.launch_all()
+                    self.graphs[precision] = g
+                self.graphs[precision].replay()
 
     def as_f32(self, buf):
         """fp32 NHWC copy of an internal activation buffer (whatever format the last run used)."""
@@ -824,20 +826,17 @@ class Plan(object):
         alias=True (the streamed entry points: pipeline flows, bench.py's step): VIEWS of this plan's own buffers, valid until the
         next forward on this plan (slot) -- for callers that consume them in stream order right away (decode + class NMS write
         fresh tensors), which is what every serving flow does: no copy launches at all."""
-        w, B = self.w, self.B
-        names = ('rois_left', 'rois_right', 'cls_prob', 'bbox_pred', 'dim_orien', 'kpts_prob', 'left_prob', 'right_prob')
+        B = self.B
+        names = ('rois_left', 'rois_right', 'cls_prob', 'bbox_pred', 'dim_orien') + (KPTS_RESULTS if kpts else ())
         if alias:
             t = {n: getattr(self, n) for n in names}
         elif self.graphs or self.programs:
-            t = {n: (getattr(self, n).clone() if kpts or n not in ('kpts_prob', 'left_prob', 'right_prob') else None) for n in names}
+            t = {n: getattr(self, n).clone() for n in names}
         else:
             t = {n: getattr(self, n) for n in names}
             for n in names:
-                if kpts or n not in ('kpts_prob', 'left_prob', 'right_prob'):
-                    setattr(self, n, torch.empty_like(getattr(self, n)))
-        res = {'rois_left': t['rois_left'], 'rois_right': t['rois_right'], 'cls_prob': t['cls_prob'].view(B, self.post, -1),
+                setattr(self, n, torch.empty_like(t[n]))
+        return {'rois_left': t['rois_left'], 'rois_right': t['rois_right'], 'cls_prob': t['cls_prob'].view(B, self.post, -1),
                'bbox_pred': t['bbox_pred'].view(B, self.post, -1), 'dim_orien_pred': t['dim_orien'].view(B, self.post, -1),
-               'kpts_prob': t['kpts_prob'], 'left_border_prob': t['left_prob'], 'right_border_prob': t['right_prob']}
-        if not kpts:        # lazy keypoint head: the three keypoint outputs do not exist for this forward
-            res['kpts_prob'] = res['left_border_prob'] = res['right_border_prob'] = None
-        return res
+               # lazy keypoint head (kpts=False): the three keypoint outputs do not exist for this forward
+               'kpts_prob': t.get('kpts_prob'), 'left_border_prob': t.get('left_prob'), 'right_border_prob': t.get('right_prob')}

@@ -5,8 +5,6 @@ The class keeps the reference's surface: construction through a subclass that de
 schema, `PyramidRoI_Feat`, and `forward(9 args) -> 15-tuple`.  The nn.Module parameters are
 containers only; `forward` executes a static launch plan (plan.py) in the HIP library.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -22,12 +20,7 @@ def _pyramid_roi_feat(feat_maps, rois, im_height, A):
     C = int(feat_maps[0].shape[1])
     n = int(rois.shape[0])
     out = torch.empty((n, A, A, C), device=rois.device)
-    ptrs = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in maps])
-    mh = (ctypes.c_int * 4)(*[int(m.shape[1]) for m in maps])
-    mw = (ctypes.c_int * 4)(*[int(m.shape[2]) for m in maps])
-    _lib.check(_lib.lib().srcnn_pyramid_roi_align(ptrs, mh, mw, C, im_height, rois.data_ptr(), n, A,
-                                                  out.data_ptr(), C, 0, _lib.FMT_F32, _lib.FMT_F32, None,
-                                                  _lib.stream()), "srcnn_pyramid_roi_align")
+    engine.pyramid_roi_align(maps, [(int(m.shape[1]), int(m.shape[2])) for m in maps], C, im_height, rois, n, A, out, C, 0)
     return engine.nhwc_to_nchw(out)
 
 
@@ -47,11 +40,9 @@ class _PyramidRoIFeat(torch.autograd.Function):
         C = shapes[0][1]
         g = engine.nchw_to_nhwc(grad_out.contiguous().float())            # (n, A, A, C)
         grads = [torch.empty((b, h, w, c), dtype=torch.float32, device=g.device) for b, c, h, w in shapes]
-        ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in grads])
-        mh = (ctypes.c_int * 4)(*[s[2] for s in shapes])
-        mw = (ctypes.c_int * 4)(*[s[3] for s in shapes])
         _lib.check(_lib.lib().srcnn_pyramid_roi_align_backward(g.data_ptr(), C, 0, rois.data_ptr(), int(rois.shape[0]), A, C,
-                                                               im_height, ptrs, mh, mw, shapes[0][0], _lib.FMT_F32, None,
+                                                               im_height, _lib.ptr_array(grads), _lib.int_array(s[2] for s in shapes),
+                                                               _lib.int_array(s[3] for s in shapes), shapes[0][0], _lib.FMT_F32, None,
                                                                _lib.stream()), "srcnn_pyramid_roi_align_backward")
         return (None, None, None) + tuple(engine.nhwc_to_nchw(t) for t in grads)
 

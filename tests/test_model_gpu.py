@@ -957,3 +957,78 @@ def test_aliased_outputs_and_inputs_by_reference(dev, use_program):
         assert torch.equal(x, y)
     for x, y in zip(r2, own_b):
         assert torch.equal(x, y)
+
+
+# ---- the launch list of plan.Plan under its A/B switches: replay == eager, and as many program nodes as the parent commit recorded
+
+PLAN_SETTINGS = {'defaults': {},
+                 'rpn_group_0': {'RPN_GROUP': '0'},
+                 'rpn_group_all': {'RPN_GROUP': 'all'},
+                 'overlap_upsample_fusion': {'UPSAMPLE_FUSION': True, 'overlap': True}}
+
+
+@pytest.fixture(scope='module')
+def odd_f16x3(dev):
+    """One model and one 97x333 pair (short side 160: the smallest input of this module) for every PLAN_SETTINGS case, its SPLIT16
+    scales calibrated here so that no case depends on the one before it.  engine.AUTOTUNE is off wherever this model runs: every
+    launch takes the library's own plan, no choice depends on a timing."""
+    from stereo_rcnn_amd import engine, fixture
+    m, _ = _build_model(dev)
+    m.precision = 'f16x3'
+    inputs = [t.to(dev) for t in fixture.make_inputs(11, 97, 333, target_short=160)]
+    prev, engine.AUTOTUNE = engine.AUTOTUNE, False
+    try:
+        with torch.no_grad():
+            m(*inputs)
+        torch.cuda.synchronize()
+    finally:
+        engine.AUTOTUNE = prev
+    return m, inputs
+
+
+def plan_setting_case(m, inputs, setting):
+    """(eager outputs, first program run's outputs (records), second's (replays), srcnn_program_size) of one PLAN_SETTINGS entry on a
+    fresh plan."""
+    from stereo_rcnn_amd import _lib, engine
+    switches = dict(PLAN_SETTINGS[setting])
+    overlap = switches.pop('overlap', None)
+    saved = {k: getattr(engine, k) for k in list(switches) + ['AUTOTUNE']}
+    m._plans = {}                                     # programs are keyed without the switches: a fresh plan per setting
+    plan = m._get_plan(1, int(inputs[0].shape[2]), int(inputs[0].shape[3]))
+    plan.overlap = overlap
+    try:
+        engine.AUTOTUNE = False
+        for k, v in switches.items():
+            setattr(engine, k, v)
+        with torch.no_grad():
+            m.use_program = False
+            eager = [t.clone() for t in m(*inputs)[:8]]
+            m.use_program = True
+            recorded = [t.clone() for t in m(*inputs)[:8]]
+            replayed = [t.clone() for t in m(*inputs)[:8]]
+        torch.cuda.synchronize()
+        assert m._get_plan(1, int(inputs[0].shape[2]), int(inputs[0].shape[3])) is plan
+        size = _lib.lib().srcnn_program_size(plan.programs[plan.program_key('f16x3', True)][0])
+    finally:
+        m.use_program = False
+        for k, v in saved.items():
+            setattr(engine, k, v)
+        m._plans = {}
+    return eager, recorded, replayed, size
+
+
+@pytest.mark.parametrize('setting', sorted(PLAN_SETTINGS))
+def test_plan_switch_settings_replay_bit_identical_with_the_parent_program_size(odd_f16x3, setting):
+    """Per switch setting of plan.Plan (the defaults, per-level RPN launches, one grouped RPN launch, forced side streams with the
+    up-sampling fused where a lateral runs inline): the eager forward and the recorded launch program give bit-identical
+    outputs, and the program has exactly as many nodes as the commit before plan.py's rules were stated once each
+    (tests/golden/plan_program_sizes.json, measured there on an MI355X): no launch, fork or join appeared or went."""
+    import json
+    with open(os.path.join(GOLD, 'plan_program_sizes.json')) as f:
+        want = json.load(f)['program_size']
+    m, inputs = odd_f16x3
+    eager, recorded, replayed, size = plan_setting_case(m, inputs, setting)
+    print('srcnn_program_size[%s] = %d (parent: %d)' % (setting, size, want[setting]))
+    for a, b, c in zip(eager, recorded, replayed):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    assert size == want[setting], (setting, size, want[setting])
