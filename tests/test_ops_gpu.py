@@ -112,8 +112,9 @@ def test_roi_align_avg_module(dev):
 
 @pytest.mark.parametrize("A,pad_c", [(7, 0), (14, 0), (7, 4), (14, 4)])
 def test_pyramid_roi_align_fused(dev, A, pad_c):
-    """Fused NHWC kernel == per-level legacy op + avg-pool + level routing of the oracle.  pad_c = 0: 8-channel-group
-    kernel (output strides multiples of 8, what the forward uses); pad_c = 4: the per-channel kernel behind it."""
+    """Fused NHWC kernel == per-level legacy op + avg-pool + level routing of the oracle.  pad_c = 0: the roi form,
+    pyramid_roi_align8_roi_kernel, one workgroup per roi (output stride and offset multiples of 8 and C <= 256, what the forward
+    uses); pad_c = 4: the per-channel kernel behind it.  (Every form and shipped configuration: test_pyramid_roi_align_gpu.py.)"""
     import ctypes
     from stereo_rcnn_amd import _lib
     from oracle import net as onet
@@ -133,7 +134,8 @@ def test_pyramid_roi_align_fused(dev, A, pad_c):
     ref = onet.pyramid_roi_feat([torch.from_numpy(m) for m in maps], torch.from_numpy(rois), im_info, kpts=(A == 14))
     tm = [torch.from_numpy(m).to(dev).permute(0, 2, 3, 1).contiguous() for m in maps]
     CS, CO = 2 * C + pad_c, C + pad_c                        # output channel stride / offset
-    out = torch.zeros((n, A, A, CS), device=dev)
+    canary = lambda: torch.full((n, A, A, CS), 0x7FC0BEEF, dtype=torch.int32, device=dev).view(torch.float32)   # NaN, fixed bits
+    out = canary()
     ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in tm])
     mh = (ctypes.c_int * 4)(*[h for h, _ in hw]); mw = (ctypes.c_int * 4)(*[w for _, w in hw])
     tr = torch.from_numpy(rois).to(dev)
@@ -141,14 +143,14 @@ def test_pyramid_roi_align_fused(dev, A, pad_c):
                                                   0, 0, None, _lib.stream()))
     got = out[:, :, :, CO:].permute(0, 3, 1, 2).cpu().numpy()
     lv_dev = onet.roi_levels(torch.from_numpy(rois))
-    assert float(out[:, :, :, :CO].abs().sum()) == 0.0         # other channel slice untouched
+    assert bool((out[:, :, :, :CO].view(torch.int32) == 0x7FC0BEEF).all())      # other channel slice untouched: still the canary
     assert np.array_equal(got, ref.numpy()), float(np.abs(got - ref.numpy()).max())
     # device-side roi limit (the keypoint head on the kept detections): the first rois as before, later ones not touched
     lim = torch.tensor([37], dtype=torch.int32, device=dev)
-    out2 = torch.zeros((n, A, A, CS), device=dev)
+    out2 = canary()
     _lib.check(_lib.lib().srcnn_pyramid_roi_align(ptrs, mh, mw, C, 600.0, tr.data_ptr(), n, A, out2.data_ptr(), CS, CO,
                                                   0, 0, lim.data_ptr(), _lib.stream()))
-    assert torch.equal(out2[:37], out[:37]) and float(out2[37:].abs().sum()) == 0.0
+    assert torch.equal(out2[:37].view(torch.int32), out[:37].view(torch.int32)) and bool((out2[37:].view(torch.int32) == 0x7FC0BEEF).all())
 
 
 def _conv_case(dev, B, H, W, cin, cout, k, stride, pad, relu, res, bn, seed, precision='f32'):
