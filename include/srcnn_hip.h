@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -506,6 +506,71 @@ SRCNN_API int srcnn_solver_evaluate_host(int im_h, int im_w, double p2_00, doubl
                                double p2_03_minus_p3_03, double alpha, const double *dim3, const double *box_left4,
                                const double *box_right4_or_null, const double *kpts5, const double *xyzt, double *cost,
                                double *grad4);
+
+/* ------------------------------------------------------------------ training losses
+ * The six loss terms of Stereo R-CNN as two kernel families, each a forward and a backward:
+ *   srcnn_cross_entropy  rpn_loss_cls (stereo_rpn.py:113-119: nonzero + index_select + F.cross_entropy), RCNN_loss_cls
+ *                        (stereo_rcnn.py:287) and the keypoint / left-border / right-border terms (stereo_rcnn.py:292-310);
+ *   srcnn_smooth_l1      _smooth_l1_loss (net_utils.py:79-99) for rpn_loss_box_left_right, RCNN_loss_bbox and
+ *                        RCNN_loss_dim_orien, with the torch.gather by rois_label (stereo_rcnn.py:274-280) folded in.
+ * Nothing is read back to the host: the ignore rule, the `sum(w) < 1` rule and the slice selection run on the device, the
+ * backward takes the upstream gradient and the normaliser from device memory.  All tensors float32, labels / selectors int32.
+ *
+ * DEFINED SUMMATION ORDER (no atomics; results are run-to-run bit-equal).  Stage 1: workgroup b (256 threads) owns rows
+ * [b * SRCNN_LOSS_ROWS_PER_WG, (b + 1) * SRCNN_LOSS_ROWS_PER_WG) -- a compile-time constant, independent of the device.  A
+ * thread adds its terms in ascending row order starting from 0 (cross-entropy: at most 4 rows; smooth L1: local elements
+ * t, t + 256, .. of the workgroup's rows x D block, as 4 groups of D consecutive ones, each group added from 0 and the 4 group
+ * sums added from 0); a wavefront adds its 64 lanes by an xor butterfly (offsets 32, 16, 8, 4, 2, 1); thread 0 adds the four
+ * wavefront sums ((w0 + w1) + w2) + w3 and writes the pair {sum, normaliser sum} to workspace[b].  Stage 2: one workgroup;
+ * thread t adds workspace[t], workspace[t + 256], .. in that order from 0, then the same butterfly and four-term sum; thread 0
+ * divides and writes *loss_out and *norm_out.  Which cross-entropy row a lane adds: cols == 2, rows t, t + 256, t + 512, t + 768 of the
+ * workgroup; otherwise a row lies on lpr = min(64, max(2, cols rounded up to a power of two)) adjacent lanes, pass p of the
+ * workgroup takes rows p * (256 / lpr) + (t / lpr), and lane p mod lpr of the row's lanes adds it.
+ *
+ * srcnn_cross_entropy: logits (rows, cols) with row stride `row_stride` >= cols floats, 1 <= cols <= SRCNN_CE_MAX_COLS.  The loss
+ * of a row is log(sum_c exp(x_c - m)) + (m - x_label), m the row maximum (logits of magnitude 1e4 stay finite), the logarithm
+ * taken as log1p of the terms other than the first maximum's.  A row is KEPT when 0 <= label < cols; every other label (-1, the
+ * RPN's "don't care", or anything else out of range) is ignored and never used as an index: the row contributes to no sum.
+ * With w_i = weights[i] (1 where weights is NULL), S = sum over kept rows of loss_i w_i and N = sum over kept rows of w_i:
+ *   SRCNN_CE_MEAN_KEPT  loss = S / N   (weights NULL: the mean over the kept rows; *norm_out = N, the kept count)
+ *   SRCNN_CE_WEIGHTED   loss = S if N < 1, else S / N   (the comparison is made on the device; *norm_out = N)
+ * DELIBERATE DIFFERENCE from the reference: when no row is kept (or N = 0) the loss is 0 and the gradient all zeros, where
+ * F.cross_entropy over an empty selection gives NaN or raises.  rows == 0 succeeds and writes loss 0.
+ * srcnn_cross_entropy_backward: grad_logits (rows, cols) with row stride grad_stride >= cols; columns [0, cols) of EVERY row are
+ * written (zeros for ignored rows; the caller need not zero it, and floats between cols and the stride are left alone):
+ *   (softmax(x)_c - [c == label]) * w_i * (*grad_loss / n),  n = the forward's divisor rebuilt from *norm (1 where it did not divide).
+ *
+ * srcnn_smooth_l1: pred (rows, n_sel * D), target (rows, D), 1 <= D <= SRCNN_SMOOTH_L1_MAX_D, 1 <= n_sel <= SRCNN_SMOOTH_L1_MAX_SEL.
+ * selector NULL (then n_sel must be 1): row r uses pred[r, 0:D]; otherwise its slice [sel[r] * D, sel[r] * D + D), and a row
+ * whose selector lies outside [0, n_sel) contributes nothing and indexes nothing.  w_in / w_out: NULL (= 1), (rows, D), or with
+ * *_per_row != 0 one weight per row (rows) -- the RPN's per-anchor weight, never expanded to 6 columns.  With
+ * d = w_in * (pred - target) and t = (float)(1.0 / sigma^2) an element is   0.5 sigma^2 d^2  where |d| < t (strictly),
+ * |d| - 0.5 / sigma^2  otherwise, times w_out; loss = (sum over all elements) / divisor.  The divisor is the caller's: it carries the
+ * reference's sum-over-`dim`-then-.mean() rule ((B, A, 6) with dim=[1] gives B * 6, not B * A).  *norm_out = divisor.
+ * srcnn_smooth_l1_backward: every element of grad_pred (rows, n_sel * D) is written (zeros in the slices the selector does not
+ * pick):  sigma^2 d w_in w_out (*grad_loss / *norm)  on the quadratic branch,  sign(d) w_in w_out (*grad_loss / *norm)  on the linear one.
+ *
+ * Errors (SRCNN_ERR_ARG / SRCNN_ERR_WORKSPACE, before any launch): a null required pointer, rows < 0, cols / D / n_sel out of
+ * range, a stride smaller than cols, sigma <= 0, divisor <= 0, a workspace smaller than srcnn_loss_workspace_bytes(rows). */
+#define SRCNN_LOSS_ROWS_PER_WG 1024
+#define SRCNN_CE_MAX_COLS 256
+#define SRCNN_CE_MEAN_KEPT 0
+#define SRCNN_CE_WEIGHTED 1
+#define SRCNN_SMOOTH_L1_MAX_D 64
+#define SRCNN_SMOOTH_L1_MAX_SEL 1024
+SRCNN_API size_t srcnn_loss_workspace_bytes(long long rows);
+SRCNN_API int srcnn_cross_entropy(const float *logits, long long rows, int cols, long long row_stride, const int *labels,
+                        const float *weights, int mode, float *loss_out, float *norm_out, void *workspace,
+                        size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_cross_entropy_backward(const float *logits, long long rows, int cols, long long row_stride, const int *labels,
+                                 const float *weights, int mode, const float *norm, const float *grad_loss,
+                                 float *grad_logits, long long grad_stride, srcnn_stream_t stream);
+SRCNN_API int srcnn_smooth_l1(const float *pred, const int *selector, int n_sel, const float *target, const float *w_in,
+                    int w_in_per_row, const float *w_out, int w_out_per_row, long long rows, int D, float sigma, float divisor,
+                    float *loss_out, float *norm_out, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_smooth_l1_backward(const float *pred, const int *selector, int n_sel, const float *target, const float *w_in,
+                             int w_in_per_row, const float *w_out, int w_out_per_row, long long rows, int D, float sigma,
+                             const float *norm, const float *grad_loss, float *grad_pred, srcnn_stream_t stream);
 
 /* ------------------------------------------------------------------ recorded launch programs
  * The forward is a fixed list of ~230 asynchronous launches over fixed buffers (one list per input size and buffer set).

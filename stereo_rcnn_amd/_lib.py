@@ -15,6 +15,9 @@ LIB_PATH = os.environ.get("SRCNN_LIB_PATH") or os.path.join(_HERE, "libsrcnn_hip
 
 FMT_F32, FMT_SPLIT16 = 0, 1     # SRCNN_FMT_* (include/srcnn_hip.h)
 REC_COLS = 32                   # SRCNN_REC_COLS: detection record row (include/srcnn_hip.h lists the columns)
+LOSS_ROWS_PER_WG = 1024         # SRCNN_LOSS_ROWS_PER_WG: rows of one stage-1 workgroup of the loss kernels (one workspace partial each)
+CE_MAX_COLS = 256               # SRCNN_CE_MAX_COLS
+CE_MEAN_KEPT, CE_WEIGHTED = 0, 1    # SRCNN_CE_*
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
@@ -161,6 +164,15 @@ _SIGNATURES = {
                                 ctypes.POINTER(ctypes.c_longlong)]),
     "srcnn_kitti_overlaps": (c_int, [ctypes.POINTER(KittiSplit), c_void_p]),
     "srcnn_kitti_match": (c_int, [ctypes.POINTER(KittiSplit), ctypes.POINTER(KittiMatchDesc), c_void_p]),
+    "srcnn_loss_workspace_bytes": (c_size_t, [ctypes.c_longlong]),
+    "srcnn_cross_entropy": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "srcnn_cross_entropy_backward": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_void_p,
+                                             c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
+    "srcnn_smooth_l1": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_float,
+                                c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "srcnn_smooth_l1_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int,
+                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
