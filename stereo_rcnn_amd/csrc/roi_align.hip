@@ -12,34 +12,43 @@
 //     level routing on the device (no nonzero()/host sync), both lattice rows of an output
 //     row in registers, 2x2 average fused, result written straight into the (left|right)
 //     channel slice of the head's GEMM operand.
-// The float/double promotion pattern of the reference kernel (its `1.` literals) is
-// reproduced operation by operation; the library is built with -ffp-contract=off.
+// The float/double promotion pattern of the reference kernel (its `1.` literals) is reproduced operation by operation; every
+// piece of that arithmetic is stated once, in roi_align_geom.h (lattice_blend() explains the pattern).
 #include "conv_common.h"
 #include "roi_align_geom.h"
 #include <cstdlib>
 
 namespace srcnn {
 
-// value of one lattice point; `at(y, x)` fetches the feature value
+// lattice_blend() for 8 consecutive channels
+__device__ __forceinline__ float8 lattice_blend(const float8 &ul, const float8 &ur, const float8 &dl, const float8 &dr, float h_ratio,
+                                                float w_ratio)
+{
+    float8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v.v[e] = lattice_blend(ul.v[e], ur.v[e], dl.v[e], dr.v[e], h_ratio, w_ratio);
+    return v;
+}
+
+__device__ __forceinline__ float8 avg2x2(const float8 &a, const float8 &b, const float8 &c, const float8 &d)
+{
+    float8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.v[e] = avg2x2(a.v[e], b.v[e], c.v[e], d.v[e]);
+    return o;
+}
+
+// value of one lattice point; `at(y, x)` fetches the feature value: a float, or the float8 of 8 consecutive channels
 template <typename Fetch>
-__device__ __forceinline__ float lattice_point(float h, float w, int height, int width, Fetch at)
+__device__ __forceinline__ auto lattice_point(float h, float w, int height, int width, Fetch at) -> decltype(at(0, 0))
 {
     int hstart, wstart;
     float h_ratio, w_ratio;
     const bool h_ok = lattice_axis(h, height, hstart, h_ratio);
     const bool w_ok = lattice_axis(w, width, wstart, w_ratio);
-    if (!h_ok || !w_ok) return 0.0f;                                         // :54-55
-    // :64-67 with C++'s usual arithmetic conversions, left to right: `1.` is a double, so the first two terms are double
-    // products; `down * h_ratio` is float x float (rounded to float) before it meets a double, and the last term is a
-    // float product throughout.  (Checked against the reference's own kernel built for gfx950: tests/test_ref_kernels_gpu.py.)
-    const double hr1 = 1. - (double)h_ratio, wr1 = 1. - (double)w_ratio;
-    const float dl_h = at(hstart + 1, wstart) * h_ratio;
-    const float dr_hw = at(hstart + 1, wstart + 1) * h_ratio * w_ratio;
-    double v = (double)at(hstart, wstart) * hr1 * wr1
-             + (double)at(hstart, wstart + 1) * hr1 * (double)w_ratio
-             + (double)dl_h * wr1
-             + (double)dr_hw;
-    return (float)v;
+    if (!h_ok || !w_ok) return {};                                           // :54-55
+    return lattice_blend(at(hstart, wstart), at(hstart, wstart + 1), at(hstart + 1, wstart), at(hstart + 1, wstart + 1), h_ratio,
+                         w_ratio);
 }
 
 __global__ void roi_align_nchw_kernel(int total, const float *__restrict__ feat, float scale, int height,
@@ -65,9 +74,7 @@ __global__ void roi_align_nchw_kernel(int total, const float *__restrict__ feat,
 
 struct PyramidArgs {
     const float *maps[4];
-    int mh[4], mw[4];
-    float scale[4];
-    const int *roi_limit;        // device-side count of the rois that matter (blocks of later rois exit) or nullptr
+    RoiLevels lv;
 };
 
 // grid (A, n); block = C threads (C multiple of 64, <= 1024). One output row per block.
@@ -76,62 +83,26 @@ __global__ void pyramid_roi_align_kernel(PyramidArgs pa, int channels, const flo
                                          float *__restrict__ out, int out_cstride, int out_coffset, int mfmt, int ofmt)
 {
     const int n = blockIdx.y, py = blockIdx.x, c = threadIdx.x;
-    if (pa.roi_limit && n >= *pa.roi_limit) return;
-    const float *r = rois + (size_t)n * 5;
-    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
-    const int height = pa.mh[l], width = pa.mw[l];
-    RoiGeom g = roi_geom(r, pa.scale[l], A + 1, A + 1);
-    const float *base = pa.maps[l];
-    const size_t img = (size_t)g.batch * height * width;
-    auto at = [&](int y, int x) { return act_load(base, mfmt, img + (size_t)y * width + x, channels, c); };
+    if (pa.lv.roi_limit && n >= *pa.lv.roi_limit) return;
+    const RoiView v = roi_view(pa.lv, pa.maps, rois, n, A);
+    auto at = [&](int y, int x) { return act_load(v.base, mfmt, v.img + (size_t)y * v.width + x, channels, c); };
     float top[A + 1], bot[A + 1];
-    const float h0 = (float)py * g.bin_h + g.start_h;
-    const float h1 = (float)(py + 1) * g.bin_h + g.start_h;
+    const float h0 = (float)py * v.geo.bin_h + v.geo.start_h;
+    const float h1 = (float)(py + 1) * v.geo.bin_h + v.geo.start_h;
 #pragma unroll
     for (int px = 0; px <= A; ++px) {
-        float w = (float)px * g.bin_w + g.start_w;
-        top[px] = lattice_point(h0, w, height, width, at);
-        bot[px] = lattice_point(h1, w, height, width, at);
+        float w = (float)px * v.geo.bin_w + v.geo.start_w;
+        top[px] = lattice_point(h0, w, v.height, v.width, at);
+        bot[px] = lattice_point(h1, w, v.height, v.width, at);
     }
 #pragma unroll
-    for (int px = 0; px < A; ++px) {
-        float s = top[px];
-        s = s + top[px + 1];
-        s = s + bot[px];
-        s = s + bot[px + 1];
-        act_store(out, ofmt, (size_t)(n * A + py) * A + px, out_cstride, out_coffset + c, s * 0.25f);
-    }
+    for (int px = 0; px < A; ++px)
+        act_store(out, ofmt, (size_t)(n * A + py) * A + px, out_cstride, out_coffset + c,
+                  avg2x2(top[px], top[px + 1], bot[px], bot[px + 1]));
 }
 
-// value of one lattice point for 8 consecutive channels; `at8(y, x)` fetches the 8-channel group.  Same arithmetic per
-// channel as lattice_point() above.
-template <typename Fetch8>
-__device__ __forceinline__ float8 lattice_point8(float h, float w, int height, int width, Fetch8 at8)
-{
-    float8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r.v[e] = 0.0f;
-    if (h < 0 || h >= height || w < 0 || w >= width) return r;
-    const int hstart = (int)fminf(floorf(h), (float)(height - 2));
-    const int wstart = (int)fminf(floorf(w), (float)(width - 2));
-    const float h_ratio = h - (float)hstart;
-    const float w_ratio = w - (float)wstart;
-    const double hr1 = 1. - (double)h_ratio, wr1 = 1. - (double)w_ratio;
-    const float8 ul = at8(hstart, wstart), ur = at8(hstart, wstart + 1);
-    const float8 dl = at8(hstart + 1, wstart), dr = at8(hstart + 1, wstart + 1);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float dl_h = dl.v[e] * h_ratio;
-        const float dr_hw = dr.v[e] * h_ratio * w_ratio;
-        const double v = (double)ul.v[e] * hr1 * wr1 + (double)ur.v[e] * hr1 * (double)w_ratio + (double)dl_h * wr1 +
-                         (double)dr_hw;
-        r.v[e] = (float)v;
-    }
-    return r;
-}
-
-// The form the forward uses: one thread per (roi, output row, 8-channel group), block (C/8, rows) of one or two wavefronts,
-// grid (ceil(A/rows), n).
+// The row-pair form (behind SRCNN_ROI_ALIGN_FORM=0): one thread per (roi, output row, 8-channel group), block (C/8, rows) of one
+// or two wavefronts, grid (ceil(A/rows), n).
 // A thread walks the A+1 lattice columns of its two lattice rows, keeps the previous column, and emits one 32-byte output
 // group per step: every tap is a 32-byte load (both activation formats), every store 2 x 16 bytes, and the 32 groups of a
 // row read 1 KB contiguous per tap.  (The per-channel kernel above issued 2-byte accesses: 8x the memory instructions.)
@@ -140,41 +111,27 @@ __global__ void pyramid_roi_align8_kernel(PyramidArgs pa, int channels, const fl
                                           float *__restrict__ out, int out_cstride, int out_coffset, int mfmt, int ofmt)
 {
     const int n = blockIdx.y, py = blockIdx.x * blockDim.y + threadIdx.y, g = threadIdx.x;
-    if (py >= A || (pa.roi_limit && n >= *pa.roi_limit)) return;
-    const float *r = rois + (size_t)n * 5;
-    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
-    const int height = pa.mh[l], width = pa.mw[l];
-    const RoiGeom geo = roi_geom(r, pa.scale[l], A + 1, A + 1);
-    const float *base = pa.maps[l];
-    const size_t img = (size_t)geo.batch * height * width;
-    auto at8 = [&](int y, int x) { return act_load8(base, mfmt, img + (size_t)y * width + x, channels, g); };
-    const float h0 = (float)py * geo.bin_h + geo.start_h;
-    const float h1 = (float)(py + 1) * geo.bin_h + geo.start_h;
-    const float w0 = (float)0 * geo.bin_w + geo.start_w;                         // the reference's expression at px = 0
-    float8 top_prev = lattice_point8(h0, w0, height, width, at8);
-    float8 bot_prev = lattice_point8(h1, w0, height, width, at8);
+    if (py >= A || (pa.lv.roi_limit && n >= *pa.lv.roi_limit)) return;
+    const RoiView v = roi_view(pa.lv, pa.maps, rois, n, A);
+    auto at8 = [&](int y, int x) { return act_load8(v.base, mfmt, v.img + (size_t)y * v.width + x, channels, g); };
+    const float h0 = (float)py * v.geo.bin_h + v.geo.start_h;
+    const float h1 = (float)(py + 1) * v.geo.bin_h + v.geo.start_h;
+    const float w0 = (float)0 * v.geo.bin_w + v.geo.start_w;                     // the reference's expression at px = 0
+    float8 top_prev = lattice_point(h0, w0, v.height, v.width, at8);
+    float8 bot_prev = lattice_point(h1, w0, v.height, v.width, at8);
 #pragma unroll 2
     for (int px = 1; px <= A; ++px) {
-        const float w = (float)px * geo.bin_w + geo.start_w;
-        const float8 top = lattice_point8(h0, w, height, width, at8);
-        const float8 bot = lattice_point8(h1, w, height, width, at8);
-        float8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float s = top_prev.v[e];
-            s = s + top.v[e];
-            s = s + bot_prev.v[e];
-            s = s + bot.v[e];
-            o.v[e] = s * 0.25f;
-        }
-        act_store8(out, ofmt, (size_t)(n * A + py) * A + (px - 1), out_cstride, (out_coffset >> 3) + g, o);
+        const float w = (float)px * v.geo.bin_w + v.geo.start_w;
+        const float8 top = lattice_point(h0, w, v.height, v.width, at8);
+        const float8 bot = lattice_point(h1, w, v.height, v.width, at8);
+        act_store8(out, ofmt, (size_t)(n * A + py) * A + (px - 1), out_cstride, (out_coffset >> 3) + g,
+                   avg2x2(top_prev, top, bot_prev, bot));
         top_prev = top;
         bot_prev = bot;
     }
 }
 
-
-// The form the forward uses since round 5: ONE workgroup per roi, thread (g, ry) = 8-channel group g of LATTICE row ry (A+1 rows).
+// The form the forward uses: ONE workgroup per roi, thread (g, ry) = 8-channel group g of LATTICE row ry (A+1 rows).
 // Every lattice point is computed once (the row-pair form above computes each lattice row twice, for the output rows above and
 // below it: twice the tap loads and twice the double-precision blends); neighbouring rows meet through a double-buffered LDS
 // slot per lattice column, behind a barrier that leaves global loads in flight, and the taps of column px + 1 are requested
@@ -192,49 +149,39 @@ __global__ __launch_bounds__(32 * (A + 1)) void pyramid_roi_align8_roi_kernel(Py
 {
     __shared__ float4 lat[2][A + 1][32][2];                     // [column parity][lattice row][group][8 floats]
     const int n = blockIdx.x, ry = threadIdx.y, g = threadIdx.x;
-    if (pa.roi_limit && n >= *pa.roi_limit) return;             // (uniform: the whole workgroup leaves)
-    const float *r = rois + (size_t)n * 5;
-    const int l = __builtin_amdgcn_readfirstlane(pyramid_level(r));   // same roi for the whole block
-    const int height = pa.mh[l], width = pa.mw[l];
-    const RoiGeom geo = roi_geom(r, pa.scale[l], A + 1, A + 1);
-    const float *base = pa.maps[l];
-    const size_t img = (size_t)geo.batch * height * width;
+    if (pa.lv.roi_limit && n >= *pa.lv.roi_limit) return;       // (uniform: the whole workgroup leaves)
+    const RoiView v = roi_view(pa.lv, pa.maps, rois, n, A);
     const bool live = g * 8 < channels;                          // (channels < 256: the upper groups only keep the barriers company)
-    const float h = (float)ry * geo.bin_h + geo.start_h;
-    const bool h_ok = !(h < 0 || h >= height);
-    const int hstart = h_ok ? (int)fminf(floorf(h), (float)(height - 2)) : 0;
-    const float h_ratio = h - (float)hstart;
-    const double hr1 = 1. - (double)h_ratio;
+    // a point outside the map reads the map's first pixels and drops them: its taps start at 0, its blend is not used
+    int hs;
+    float h_ratio;
+    const bool h_ok = lattice_axis((float)ry * v.geo.bin_h + v.geo.start_h, v.height, hs, h_ratio);
+    const int hstart = h_ok ? hs : 0;
     auto request = [&](int px) {
         LatticeTaps t;
-        const float w = (float)px * geo.bin_w + geo.start_w;
-        t.ok = h_ok && !(w < 0 || w >= width);                   // roi_align_kernel.cu:54-55
-        const int wstart = t.ok ? (int)fminf(floorf(w), (float)(width - 2)) : 0;
-        t.w_ratio = w - (float)wstart;
-        const size_t p0 = img + (size_t)hstart * width + wstart; // (a point outside the map reads the map's first pixels and drops them)
+        int ws;
+        const bool w_ok = lattice_axis((float)px * v.geo.bin_w + v.geo.start_w, v.width, ws, t.w_ratio);
+        t.ok = h_ok && w_ok;                                     // roi_align_kernel.cu:54-55
+        const int wstart = t.ok ? ws : 0;
+        const size_t p0 = v.img + (size_t)hstart * v.width + wstart;
         const int gl = live ? g : 0;
-        t.ul = act_load8(base, mfmt, p0, channels, gl);
-        t.ur = act_load8(base, mfmt, p0 + 1, channels, gl);
-        t.dl = act_load8(base, mfmt, p0 + width, channels, gl);
-        t.dr = act_load8(base, mfmt, p0 + width + 1, channels, gl);
+        t.ul = act_load8(v.base, mfmt, p0, channels, gl);
+        t.ur = act_load8(v.base, mfmt, p0 + 1, channels, gl);
+        t.dl = act_load8(v.base, mfmt, p0 + v.width, channels, gl);
+        t.dr = act_load8(v.base, mfmt, p0 + v.width + 1, channels, gl);
         return t;
     };
-    auto blend = [&](const LatticeTaps &t) {                     // lattice_point8's arithmetic
-        float8 v;
-        const double wr1 = 1. - (double)t.w_ratio;
+    auto blend = [&](const LatticeTaps &t) {                     // (h_ratio's part of lattice_blend is loop-invariant: hoisted)
+        float8 b;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float dl_h = t.dl.v[e] * h_ratio;
-            const float dr_hw = t.dr.v[e] * h_ratio * t.w_ratio;
-            const double d = (double)t.ul.v[e] * hr1 * wr1 + (double)t.ur.v[e] * hr1 * (double)t.w_ratio + (double)dl_h * wr1 + (double)dr_hw;
-            v.v[e] = t.ok ? (float)d : 0.0f;
+            const float p = lattice_blend(t.ul.v[e], t.ur.v[e], t.dl.v[e], t.dr.v[e], h_ratio, t.w_ratio);
+            b.v[e] = t.ok ? p : 0.0f;
         }
-        return v;
+        return b;
     };
     LatticeTaps cur = request(0);
-    float8 top_prev, bot_prev;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) top_prev.v[e] = bot_prev.v[e] = 0.f;
+    float8 top_prev = {}, bot_prev = {};
 #pragma unroll 1
     for (int px = 0; px <= A; ++px) {
         LatticeTaps nxt = cur;
@@ -247,18 +194,9 @@ __global__ __launch_bounds__(32 * (A + 1)) void pyramid_roi_align8_roi_kernel(Py
         if (ry < A) {
             const float4 b0 = lat[px & 1][ry + 1][g][0], b1 = lat[px & 1][ry + 1][g][1];
             const float8 bot = {{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w}};
-            if (px >= 1 && live) {
-                float8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float s = top_prev.v[e];
-                    s = s + top.v[e];
-                    s = s + bot_prev.v[e];
-                    s = s + bot.v[e];
-                    o.v[e] = s * 0.25f;
-                }
-                act_store8(out, ofmt, (size_t)(n * A + ry) * A + (px - 1), out_cstride, (out_coffset >> 3) + g, o);
-            }
+            if (px >= 1 && live)
+                act_store8(out, ofmt, (size_t)(n * A + ry) * A + (px - 1), out_cstride, (out_coffset >> 3) + g,
+                           avg2x2(top_prev, top, bot_prev, bot));
             bot_prev = bot;
         }
         top_prev = top;
@@ -269,7 +207,7 @@ __global__ __launch_bounds__(32 * (A + 1)) void pyramid_roi_align8_roi_kernel(Py
 }  // namespace srcnn
 
 // avg_pool2d / max_pool2d (kernel 2, stride 1) over the (planes, h, w) lattice of the legacy op: the reduction behind
-// RoIAlignAvg / RoIAlignMax (modules/roi_align.py:26-29, 41-44).  Sum order of ATen's avg_pool2d (rows, then columns), x 0.25.
+// RoIAlignAvg / RoIAlignMax (modules/roi_align.py:26-29, 41-44): avg2x2() / first_max4().
 __global__ void pool2x2_s1_kernel(const float *__restrict__ x, size_t planes, int h, int w, float *__restrict__ y, int take_max)
 {
     const int oh = h - 1, ow = w - 1;
@@ -280,20 +218,7 @@ __global__ void pool2x2_s1_kernel(const float *__restrict__ x, size_t planes, in
         const size_t pl = idx / ((size_t)ow * oh);
         const float *q = x + (pl * h + py) * w + px;
         const float a = q[0], b = q[1], c = q[w], d = q[w + 1];
-        if (take_max) {
-            // max_pool2d propagates NaN; fmaxf would drop it
-            float m = a;
-            m = (b > m || b != b) ? b : m;
-            m = (c > m || c != c) ? c : m;
-            m = (d > m || d != d) ? d : m;
-            y[idx] = m;
-        } else {
-            float s = a;
-            s = s + b;
-            s = s + c;
-            s = s + d;
-            y[idx] = s * 0.25f;
-        }
+        y[idx] = take_max ? srcnn::first_max4(a, b, c, d).value : srcnn::avg2x2(a, b, c, d);
     }
 }
 
@@ -342,44 +267,29 @@ int srcnn_pyramid_roi_align(const float *const *maps_host, const int *mh_host, c
     if (out_format == 1) SRCNN_REQUIRE(out_cstride % 8 == 0 && out_coffset % 8 == 0, "SPLIT16 output alignment");
     if (num_rois == 0) return SRCNN_OK;
     PyramidArgs pa;
-    pa.roi_limit = roi_limit;
-    for (int l = 0; l < 4; ++l) {
-        pa.maps[l] = maps_host[l];
-        pa.mh[l] = mh_host[l];
-        pa.mw[l] = mw_host[l];
-        // python: feat_maps[i].size(2) / im_info[0][0] -> double, narrowed to float at the C boundary
-        pa.scale[l] = (float)((double)mh_host[l] / (double)im_height);
-    }
+    for (int l = 0; l < 4; ++l) pa.maps[l] = maps_host[l];
+    pa.lv = roi_levels(mh_host, mw_host, im_height, roi_limit);
     static const int roi_form = [] { const char *e = std::getenv("SRCNN_ROI_ALIGN_FORM"); return e ? std::atoi(e) : 1; }();   // A/B switch
-    if (roi_form && out_cstride % 8 == 0 && out_coffset % 8 == 0 && channels <= 256) {
+    // the form: a kernel template (for A = 7 and 14) with its grid and block
+    void (*k7)(PyramidArgs, int, const float *, float *, int, int, int, int);
+    decltype(k7) k14;
+    dim3 grid, block;
+    if (out_cstride % 8 != 0 || out_coffset % 8 != 0) {
+        // per channel: one output row per block
+        k7 = pyramid_roi_align_kernel<7>, k14 = pyramid_roi_align_kernel<14>;
+        grid = dim3(A, num_rois), block = dim3(channels);
+    } else if (roi_form && channels <= 256) {
         // one workgroup per roi, one thread row per lattice row: every lattice point computed once
-        dim3 grid(num_rois), block(32, A + 1);
-        if (A == 7)
-            SRCNN_LAUNCH(pyramid_roi_align8_roi_kernel<7>, grid, block, 0, as_stream(stream), pa, channels, rois, out,
-                               out_cstride, out_coffset, maps_format, out_format);
-        else
-            SRCNN_LAUNCH(pyramid_roi_align8_roi_kernel<14>, grid, block, 0, as_stream(stream), pa, channels, rois, out,
-                               out_cstride, out_coffset, maps_format, out_format);
-        return check_launch("srcnn_pyramid_roi_align");
-    }
-    if (out_cstride % 8 == 0 && out_coffset % 8 == 0) {
+        k7 = pyramid_roi_align8_roi_kernel<7>, k14 = pyramid_roi_align8_roi_kernel<14>;
+        grid = dim3(num_rois), block = dim3(32, A + 1);
+    } else {
+        // row pairs
         const int G = channels / 8, rows = G <= 32 ? 64 / G : 1;   // one or two wavefronts per block: thousands of small blocks
-        dim3 grid8((A + rows - 1) / rows, num_rois), block8(G, rows);
-        if (A == 7)
-            SRCNN_LAUNCH(pyramid_roi_align8_kernel<7>, grid8, block8, 0, as_stream(stream), pa, channels, rois, out,
-                               out_cstride, out_coffset, maps_format, out_format);
-        else
-            SRCNN_LAUNCH(pyramid_roi_align8_kernel<14>, grid8, block8, 0, as_stream(stream), pa, channels, rois, out,
-                               out_cstride, out_coffset, maps_format, out_format);
-        return check_launch("srcnn_pyramid_roi_align");
+        k7 = pyramid_roi_align8_kernel<7>, k14 = pyramid_roi_align8_kernel<14>;
+        grid = dim3((A + rows - 1) / rows, num_rois), block = dim3(G, rows);
     }
-    dim3 grid(A, num_rois), block(channels);
-    if (A == 7)
-        SRCNN_LAUNCH(pyramid_roi_align_kernel<7>, grid, block, 0, as_stream(stream), pa, channels, rois, out,
-                           out_cstride, out_coffset, maps_format, out_format);
-    else
-        SRCNN_LAUNCH(pyramid_roi_align_kernel<14>, grid, block, 0, as_stream(stream), pa, channels, rois,
-                           out, out_cstride, out_coffset, maps_format, out_format);
+    SRCNN_LAUNCH(A == 7 ? k7 : k14, grid, block, 0, as_stream(stream), pa, channels, rois, out, out_cstride, out_coffset, maps_format,
+                 out_format);
     return check_launch("srcnn_pyramid_roi_align");
 }
 

@@ -5,7 +5,8 @@
 // order: a workgroup owns a tile of map pixels, lists the rois that reach the tile in roi order (ballot compaction into
 // LDS), and every (pixel, channel) adds its contributions in ascending (roi, ph, pw) order, starting from 0, and is written
 // exactly once: no atomics, no zero fill, run-to-run bit-equal.  The value of one contribution is the reference's
-// expression with its float/double promotions (:137-140); geometry comes from roi_align_geom.h, shared with the forward.
+// expression with its float/double promotions (:137-140); geometry, the level table and the adjoint of the 2x2 window come
+// from roi_align_geom.h, shared with the forward.
 //
 // Entry points:
 //   * roi_align_backward_cuda          : the reference's operator (NCHW, one map), the drop-in symbol;
@@ -23,10 +24,8 @@ constexpr int BWD_CHUNK = 1024;       // rois tested per chunk (4 per thread); a
 
 struct RoiBwdArgs {
     float *maps[4];
-    int mh[4], mw[4];
-    float scale[4];
+    RoiLevels lv;                     // (roi_limit: the rois from it on contribute nothing)
     int row0[5];                      // blockIdx.y range of each level's tile rows
-    const int *roi_limit;             // device-side count of the rois that matter, or nullptr
     int route;                        // 1: pyramid level routing; 0: every roi belongs to level 0
 };
 
@@ -59,7 +58,7 @@ struct Vec<4> {
 // lanes = channels (VEC consecutive ones each).  Element (c, pixel p) of a map lies at c * map_cs + p * map_ps behind the
 // image's start; the gradient of lattice / output point q of roi n, channel c, at n * g_ns + q * g_ps + c * g_cs.
 // FUSED: g is the gradient of the A x A average-pooled output (A = ah - 1 = aw - 1) and the lattice gradient of a point is
-// ((g00 + g01) + g10) + g11 over the outputs that read it, row-major, x 0.25f; otherwise g is the lattice gradient itself.
+// window2x2_adjoint() of it; otherwise g is the lattice gradient itself.
 template <int VEC, bool FUSED>
 __global__ __launch_bounds__(64 * BWD_TH) void roi_align_backward_kernel(RoiBwdArgs ba, const float *__restrict__ rois, int num_rois,
                                                                          int ah, int aw, const float *__restrict__ g, long long g_ns,
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(64 * BWD_TH) void roi_align_backward_kernel(RoiBwdA
     // (level, tile row) from blockIdx.y, (image, channel block) from blockIdx.z: scalar compares, no division
     int l = 0;
     while (l < 3 && (int)blockIdx.y >= ba.row0[l + 1]) ++l;
-    const int height = ba.mh[l], width = ba.mw[l];
+    const int height = ba.lv.mh[l], width = ba.lv.mw[l];
     const int x0 = blockIdx.x * BWD_TW, y0 = ((int)blockIdx.y - ba.row0[l]) * BWD_TH;
     if (x0 >= width) return;                                        // (uniform: the grid is as wide as the widest level)
     int b = 0, cb = blockIdx.z;
@@ -81,8 +80,8 @@ __global__ __launch_bounds__(64 * BWD_TH) void roi_align_backward_kernel(RoiBwdA
     const bool live = c < channels;
     const int y = y0 + wave;
     const bool row_live = y < height;
-    const float scale = ba.scale[l];
-    const int limit = ba.roi_limit ? min(*ba.roi_limit, num_rois) : num_rois;
+    const float scale = ba.lv.scale[l];
+    const int limit = ba.lv.roi_limit ? min(*ba.lv.roi_limit, num_rois) : num_rois;
     float *out = ba.maps[l] + ((size_t)b * channels * height * width) + (size_t)c * map_cs;
     const int tid = wave * 64 + lane;
 
@@ -165,19 +164,13 @@ __global__ __launch_bounds__(64 * BWD_TH) void roi_align_backward_kernel(RoiBwdA
                         if (FUSED) {
                             // the lattice point's gradient from the (up to four) outputs that averaged it
                             const int A = aw - 1;
-                            bool first = true;
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const int oy = ph - 1 + (q >> 1), ox = pw - 1 + (q & 1);
-                                if (oy < 0 || oy >= A || ox < 0 || ox >= A) continue;
-                                Vec<VEC> t;
-                                t.load(gn + (size_t)(oy * A + ox) * g_ps);
-#pragma unroll
-                                for (int i = 0; i < VEC; ++i) gv.v[i] = first ? t.v[i] : gv.v[i] + t.v[i];
-                                first = false;
-                            }
-#pragma unroll
-                            for (int i = 0; i < VEC; ++i) gv.v[i] = gv.v[i] * 0.25f;
+                            window2x2_adjoint(gv.v, ph, pw, A, A, true,
+                                              [&](int oy, int ox) {
+                                                  Vec<VEC> t;
+                                                  t.load(gn + (size_t)(oy * A + ox) * g_ps);
+                                                  return t;
+                                              },
+                                              [](int, int) { return true; });
                         } else {
                             gv.load(gn + (size_t)(ph * aw + pw) * g_ps);
                         }
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(64 * BWD_TH) void roi_align_backward_kernel(RoiBwdA
     }
 }
 
-// adjoint of pool2x2_s1_kernel: one thread per lattice element, the (up to four) outputs that read it in row-major order.
+// adjoint of pool2x2_s1_kernel: one thread per lattice element, window2x2_adjoint() of the outputs' gradient.
 // Grid (planes, row groups), block (columns, rows): indices come from the grid, no integer division.  The maximum recomputes
 // the argmax of each of those outputs' windows (up to 16 loads of x per element): an op-level drop-in, not a fast path.
 __global__ void pool2x2_s1_backward_kernel(const float *__restrict__ gy, const float *__restrict__ x, int h, int w,
@@ -228,26 +221,17 @@ __global__ void pool2x2_s1_backward_kernel(const float *__restrict__ gy, const f
     const int i = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= h) return;
     for (int j = threadIdx.x; j < w; j += blockDim.x) {
-        float s = 0.0f;
-        bool first = true;
-        for (int q = 0; q < 4; ++q) {
-            const int oy = i - 1 + (q >> 1), ox = j - 1 + (q & 1);
-            if (oy < 0 || oy >= oh || ox < 0 || ox >= ow) continue;
-            if (take_max) {
-                // the window's element max_pool2d picks: the first maximum in row-major order, a NaN wins (pool2x2_s1_kernel)
-                const float *p = x + (pl * h + oy) * w + ox;
-                const float v[4] = {p[0], p[1], p[w], p[w + 1]};
-                int arg = 0;
-                float m = v[0];
-                for (int t = 1; t < 4; ++t)
-                    if (v[t] > m || v[t] != v[t]) m = v[t], arg = t;
-                if (oy + (arg >> 1) != i || ox + (arg & 1) != j) continue;
-            }
-            const float gq = gy[(pl * oh + oy) * ow + ox];
-            s = first ? gq : s + gq;
-            first = false;
-        }
-        gx[(pl * h + i) * w + j] = take_max ? s : s * 0.25f;
+        float s[1] = {0.0f};
+        window2x2_adjoint(s, i, j, oh, ow, !take_max,
+                          [&](int oy, int ox) { return Vec<1>{{gy[(pl * oh + oy) * ow + ox]}}; },
+                          [&](int oy, int ox) {
+                              if (!take_max) return true;
+                              // the output's value came from this element: first_max4 of its window (pool2x2_s1_kernel)
+                              const float *p = x + (pl * h + oy) * w + ox;
+                              const int arg = first_max4(p[0], p[1], p[w], p[w + 1]).index;
+                              return oy + (arg >> 1) == i && ox + (arg & 1) == j;
+                          });
+        gx[(pl * h + i) * w + j] = s[0];
     }
 }
 
@@ -286,8 +270,8 @@ int roi_align_backward_cuda(int aligned_height, int aligned_width, float spatial
     if ((long long)batch * channels * height * width == 0) return 1;
     RoiBwdArgs ba = {};
     ba.maps[0] = bottom_grad;
-    ba.mh[0] = height, ba.mw[0] = width;
-    ba.scale[0] = spatial_scale;
+    ba.lv.mh[0] = height, ba.lv.mw[0] = width;
+    ba.lv.scale[0] = spatial_scale;
     const int tile_rows = cdiv(height, BWD_TH), ncb = cdiv(channels, 64);
     ba.row0[0] = 0;
     for (int l = 1; l <= 4; ++l) ba.row0[l] = tile_rows;
@@ -315,16 +299,13 @@ int srcnn_pyramid_roi_align_backward(const float *grad_out, int out_cstride, int
     SRCNN_REQUIRE(num_rois >= 0 && batch >= 0 && grad_maps_host && mh_host && mw_host, "bad args");
     if (batch == 0) return SRCNN_OK;
     RoiBwdArgs ba = {};
-    ba.roi_limit = roi_limit;
+    ba.lv = roi_levels(mh_host, mw_host, im_height, roi_limit);
     ba.route = 1;
     int wmax = 0;
     ba.row0[0] = 0;
     for (int l = 0; l < 4; ++l) {
         SRCNN_REQUIRE(grad_maps_host[l] && mh_host[l] > 0 && mw_host[l] > 0, "bad map");
         ba.maps[l] = grad_maps_host[l];
-        ba.mh[l] = mh_host[l];
-        ba.mw[l] = mw_host[l];
-        ba.scale[l] = (float)((double)mh_host[l] / (double)im_height);      // as srcnn_pyramid_roi_align
         ba.row0[l + 1] = ba.row0[l] + cdiv(mh_host[l], BWD_TH);
         wmax = mw_host[l] > wmax ? mw_host[l] : wmax;
     }
