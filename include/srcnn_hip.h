@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -571,6 +571,88 @@ SRCNN_API int srcnn_smooth_l1(const float *pred, const int *selector, int n_sel,
 SRCNN_API int srcnn_smooth_l1_backward(const float *pred, const int *selector, int n_sel, const float *target, const float *w_in,
                              int w_in_per_row, const float *w_out, int w_out_per_row, long long rows, int D, float sigma,
                              const float *norm, const float *grad_loss, float *grad_pred, srcnn_stream_t stream);
+
+/* ------------------------------------------------------------------ training target layers
+ * srcnn_anchor_targets    _AnchorTargetLayer.forward (lib/model/rpn/anchor_target_layer.py:64-154),
+ * srcnn_proposal_targets  _ProposalTargetLayer.forward (lib/model/rpn/proposal_target_layer.py:36-333),
+ * both without a host read: every count the reference reads back (nonzero, sum(keep) > 0, sum_fg[i] > num_fg, union1d
+ * through .cpu()) stays on the device.  Floats are float32, labels / selections int32.
+ *
+ * RANDOMNESS IS AN INPUT.  The reference samples with np.random.permutation / np.random.rand; here the caller passes the draws.
+ *   without replacement (anchor fg, anchor bg, proposal fg): one uint32 key per candidate slot; candidates are ranked by
+ *     (key, index), the lower index winning a tie.  The anchor layer keeps the `quota` lowest-ranked candidates and sets the
+ *     other ones to -1; the proposal layer's output row j of the foreground block is the candidate of rank j.
+ *   with replacement (proposal bg, and the fg-only / bg-only branches of proposal_target_layer.py:262-283): one float64
+ *     u[b, r] in [0, 1) per OUTPUT ROW r; row r takes the candidate whose position in ascending index order is
+ *     floor(u[b, r] * count), the product in double as numpy forms it (rows of the without-replacement block ignore their u).
+ *
+ * IoU (bbox_overlaps_batch, bbox_transform.py:230-305) is evaluated as separately rounded float32 operations in the
+ * reference's order -- no contraction, correctly rounded division -- with its zero-area masks (a ground-truth row with
+ * w == 1 && h == 1 gives 0, such an anchor / roi gives -1): an overlap is bit-equal to torch's float32 CPU value, so
+ * `overlaps == gt_max` (:91) means the same thing here.  The argmax is the FIRST maximum (lowest ground-truth index).  The only
+ * floating reduction is a maximum (order-independent; integer atomics on the order-preserving bit pattern): results are
+ * run-to-run bit-equal.  The regression targets follow bbox_transform_batch operation by operation; dw / dh go through the
+ * device's logf, the one place where a last-bit difference from the CPU reference can appear.
+ *
+ * srcnn_anchor_targets: anchors (N, 4) as generate_anchors_all_pyramids gives them; gt_left / gt_right / gt_merge (B, K, 5)
+ * zero-padded, K <= SRCNN_TARGETS_MAX_GT; im_info (B, 3) device, row 0 is used for every image as in the reference (:70-71);
+ * fg_keys / bg_keys (B, N) uint32.  Steps in the reference's order: inside test x2 < (long)im_w, y2 < (long)im_h (anchors outside
+ * take part in no maximum and come out as label -1, targets 0, weights 0: _unmap folded in); labels :88, :90-94 with
+ * gt_max == 0 -> 1e-5, :97, clobber_positives choosing :88 or :100; sum_fg / sum_bg counted BEFORE any subsampling;
+ * foreground kept to num_fg where sum_fg > num_fg; num_bg = batch_size - sum_fg (pre-subsample sum_fg, as the reference), background
+ * kept to num_bg where sum_bg > num_bg, a negative num_bg disabling every background anchor; targets_left / targets_right from
+ * gt_left / gt_right at the MERGED argmax, written for every inside anchor; inside_w = inside_weight on label 1; outside_w =
+ * 1 / num_examples on labels 0 and 1, num_examples = the kept labels >= 0 of the LAST image of the batch (the `i` of :140 is
+ * the loop's leftover; kept).  Outputs: labels (B, N) int32, targets_* (B, N, 4), inside_w / outside_w (B, N), and
+ * max_overlaps (B, N), may be NULL: the merged maximum, -2 outside.  Four launches and one memset.
+ *
+ * srcnn_proposal_targets: rois_left / rois_right (B, R, 5), gt_left / gt_right (B, K, 5), gt_dim_orien (B, K, 5), gt_kpts
+ * (B, K, 6), fg_keys (B, R + K) uint32, u (B, rois_per_image) float64; R + K <= SRCNN_TARGETS_MAX_ROIS, rois_per_image <=
+ * SRCNN_TARGETS_MAX_BATCH_ROIS.  One workgroup per image: the ground-truth boxes are appended as rois R .. R+K-1 (:45-53); both
+ * IoU matrices; foreground = left >= fg_thresh && right >= fg_thresh && the two argmax agree; background = in [bg_thresh_lo,
+ * bg_thresh_hi) on the left OR the right, in index order (np.union1d); the four branches of :246-285 -- where the reference
+ * raises (no foreground and no background) the image's outputs are all zero and status[b] = 1 (0 otherwise); gathers of
+ * :291-310 (labels from gt_left[..., 4], rows past the foreground count 0; column 0 of the rois = b; dim_orien and kpts by the
+ * LEFT assignment); box targets normalised by bbox_means / bbox_stds, dim_orien by dim_means / dim_stds; keypoint targets of
+ * :168-192 (torch 0.3's round = HALF AWAY FROM ZERO, made explicit; -225 out of range; first maximum of the four keypoints;
+ * type * grid + pos; weight 0 where negative); expansion of :77-138 (boxes / dim_orien for label > 0, keypoints for label == 1,
+ * inside = inside_weights, outside = inside > 0).  The foreground ranking compares every pair of foreground candidates (at most
+ * (R + K)^2 / 1024 LDS reads per thread).  Outputs: rois_left / rois_right (B, S, 5), labels (B, S) int32, bbox_targets_left /
+ * _right (B, S, 4), dim_orien_targets (B, S, 5), kpts_targets (B, S, 3) int32, kpts_weight (B, S, 3), inside_w / outside_w
+ * (B, S, 4), status (B) int32, keep_inds (B, S) int32 or NULL (the selected roi rows), S = rois_per_image.  One launch.
+ *
+ * Errors (SRCNN_ERR_ARG / SRCNN_ERR_WORKSPACE, before any launch): a null required pointer or params, B / N / R < 1 or K < 1,
+ * K > SRCNN_TARGETS_MAX_GT, R + K or rois_per_image over their maxima, batch_size < 0, a quota (num_fg, fg_rois_per_image)
+ * below 0 or above its batch size, kpts_grid < 1, a zero std, a workspace smaller than the matching *_workspace_bytes. */
+#define SRCNN_TARGETS_MAX_GT 64
+#define SRCNN_TARGETS_MAX_ROIS 4096
+#define SRCNN_TARGETS_MAX_BATCH_ROIS 1024
+typedef struct srcnn_anchor_target_params {
+    float negative_overlap, positive_overlap;   /* cfg.TRAIN.RPN_NEGATIVE_OVERLAP / RPN_POSITIVE_OVERLAP */
+    int clobber_positives;                      /* cfg.TRAIN.RPN_CLOBBER_POSITIVES */
+    int batch_size;                             /* cfg.TRAIN.RPN_BATCHSIZE */
+    int num_fg;                                 /* int(RPN_FG_FRACTION * RPN_BATCHSIZE) */
+    float inside_weight;                        /* cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS[0] */
+} srcnn_anchor_target_params;
+typedef struct srcnn_proposal_target_params {
+    float fg_thresh, bg_thresh_hi, bg_thresh_lo;
+    int rois_per_image, fg_rois_per_image;      /* cfg.TRAIN.BATCH_SIZE, int(round(FG_FRACTION * BATCH_SIZE)) */
+    int kpts_grid;                              /* cfg.KPTS_GRID */
+    float bbox_means[4], bbox_stds[4], dim_means[5], dim_stds[5], inside_weights[4];
+} srcnn_proposal_target_params;
+SRCNN_API size_t srcnn_anchor_targets_workspace_bytes(int B, int K);
+SRCNN_API int srcnn_anchor_targets(const float *anchors, int N, const float *gt_left, const float *gt_right, const float *gt_merge,
+                         int B, int K, const float *im_info, const unsigned *fg_keys, const unsigned *bg_keys,
+                         const srcnn_anchor_target_params *params, int *labels, float *targets_left, float *targets_right,
+                         float *inside_w, float *outside_w, float *max_overlaps, void *workspace, size_t workspace_bytes,
+                         srcnn_stream_t stream);
+SRCNN_API size_t srcnn_proposal_targets_workspace_bytes(int B, int R, int K);
+SRCNN_API int srcnn_proposal_targets(const float *rois_left, const float *rois_right, int B, int R, const float *gt_left,
+                           const float *gt_right, const float *gt_dim_orien, const float *gt_kpts, int K, const unsigned *fg_keys,
+                           const double *u, const srcnn_proposal_target_params *params, float *out_rois_left, float *out_rois_right,
+                           int *labels, float *bbox_targets_left, float *bbox_targets_right, float *dim_orien_targets,
+                           int *kpts_targets, float *kpts_weight, float *inside_w, float *outside_w, int *status, int *keep_inds,
+                           void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
 /* ------------------------------------------------------------------ recorded launch programs
  * The forward is a fixed list of ~230 asynchronous launches over fixed buffers (one list per input size and buffer set).

@@ -18,6 +18,9 @@ REC_COLS = 32                   # SRCNN_REC_COLS: detection record row (include/
 LOSS_ROWS_PER_WG = 1024         # SRCNN_LOSS_ROWS_PER_WG: rows of one stage-1 workgroup of the loss kernels (one workspace partial each)
 CE_MAX_COLS = 256               # SRCNN_CE_MAX_COLS
 CE_MEAN_KEPT, CE_WEIGHTED = 0, 1    # SRCNN_CE_*
+TARGETS_MAX_GT = 64             # SRCNN_TARGETS_MAX_GT
+TARGETS_MAX_ROIS = 4096         # SRCNN_TARGETS_MAX_ROIS: proposals + ground-truth boxes of one image
+TARGETS_MAX_BATCH_ROIS = 1024   # SRCNN_TARGETS_MAX_BATCH_ROIS: rois_per_image
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
@@ -57,6 +60,20 @@ class KittiMatchDesc(ctypes.Structure):
                 ("cfg_flags", c_void_p), ("cfg_metric", c_void_p), ("cfg_min_overlap", c_void_p), ("cfg_n_thresh", c_void_p),
                 ("thresholds", c_void_p), ("ign_gt", c_void_p), ("ign_det", c_void_p),
                 ("gt_score", c_void_p), ("tp", c_void_p), ("fp", c_void_p), ("fn", c_void_p), ("similarity", c_void_p)]
+
+
+class AnchorTargetParams(ctypes.Structure):
+    """struct srcnn_anchor_target_params (include/srcnn_hip.h)."""
+    _fields_ = [("negative_overlap", c_float), ("positive_overlap", c_float), ("clobber_positives", c_int),
+                ("batch_size", c_int), ("num_fg", c_int), ("inside_weight", c_float)]
+
+
+class ProposalTargetParams(ctypes.Structure):
+    """struct srcnn_proposal_target_params (include/srcnn_hip.h)."""
+    _fields_ = [("fg_thresh", c_float), ("bg_thresh_hi", c_float), ("bg_thresh_lo", c_float),
+                ("rois_per_image", c_int), ("fg_rois_per_image", c_int), ("kpts_grid", c_int),
+                ("bbox_means", c_float * 4), ("bbox_stds", c_float * 4), ("dim_means", c_float * 5), ("dim_stds", c_float * 5),
+                ("inside_weights", c_float * 4)]
 
 
 _SIGNATURES = {
@@ -173,6 +190,13 @@ _SIGNATURES = {
                                 c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "srcnn_smooth_l1_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int,
                                          c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "srcnn_anchor_targets_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "srcnn_anchor_targets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     ctypes.POINTER(AnchorTargetParams)] + [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "srcnn_proposal_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "srcnn_proposal_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p, ctypes.POINTER(ProposalTargetParams)] + [c_void_p] * 12
+                               + [c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

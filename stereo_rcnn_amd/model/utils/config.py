@@ -26,6 +26,27 @@ cfg.RESNET = _Cfg()
 cfg.TRAIN.TRUNCATED = False                       # :43
 cfg.TRAIN.SCALES = (600,)                         # :49
 cfg.TRAIN.MAX_SIZE = 2484                         # :52
+cfg.TRAIN.BATCH_SIZE = 512                        # :55  rois per image of the proposal target layer
+cfg.TRAIN.FG_FRACTION = 0.25                      # :58
+cfg.TRAIN.FG_THRESH = 0.5                         # :61
+cfg.TRAIN.BG_THRESH_HI = 0.5                      # :65
+cfg.TRAIN.BG_THRESH_LO = 0.0                      # :66
+cfg.TRAIN.BBOX_NORMALIZE_TARGETS = True           # :69
+cfg.TRAIN.BBOX_INSIDE_WEIGHTS = (1.0, 1.0, 1.0, 1.0)       # :72
+cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED = True        # :76
+cfg.TRAIN.DIM_NORMALIZE_TARGETS_PRECOMPUTED = True         # :80
+cfg.TRAIN.RPN_POSITIVE_OVERLAP = 0.7              # :86
+cfg.TRAIN.RPN_NEGATIVE_OVERLAP = 0.3              # :88
+cfg.TRAIN.RPN_CLOBBER_POSITIVES = False           # :90
+cfg.TRAIN.RPN_FG_FRACTION = 0.5                   # :92
+cfg.TRAIN.RPN_BATCHSIZE = 512                     # :94
+cfg.TRAIN.RPN_NMS_THRESH = 0.7                    # :96
+cfg.TRAIN.RPN_PRE_NMS_TOP_N = 12000               # :98
+cfg.TRAIN.RPN_POST_NMS_TOP_N = 2000               # :100
+cfg.TRAIN.RPN_MIN_SIZE = 8                        # :102
+cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS = (1.0, 1.0, 1.0, 1.0)   # :104
+cfg.TRAIN.RPN_POSITIVE_WEIGHT = -1.0              # :108
+cfg.MAX_NUM_GT_BOXES = 30                         # :207
 cfg.TRAIN.BBOX_NORMALIZE_MEANS = (0.0, 0.0, 0.0, 0.0)      # :77
 cfg.TRAIN.BBOX_NORMALIZE_STDS = (0.1, 0.1, 0.2, 0.2)       # :78
 cfg.TRAIN.DIM_NORMALIZE_MEANS = (1.6, 1.5, 4.0, 0.0, 0.0)  # :81
