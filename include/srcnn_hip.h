@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 280 = convolution backward: srcnn_conv_bwd_desc, srcnn_conv2d_backward, srcnn_conv2d_backward_workspace_bytes; 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -266,6 +266,74 @@ SRCNN_API int srcnn_conv2d_chain(const srcnn_conv_desc *descs, int n, srcnn_stre
  * coarse levels are launches of 6 to 76 tiles.  Tiles: (2,2,8,2) (4,2,8,3) (4,4,8,2) (2,1,4,2) as (tile_mr, tile_nr, waves, stages).
  * Each convolution's result is bit-identical to its own srcnn_conv2d launch with that tile. */
 SRCNN_API int srcnn_conv2d_group(const srcnn_conv_desc *descs, int n, srcnn_stream_t stream);
+
+/* ------------------------------------------------- convolution backward (training; exact-fp32 engine)
+ * The gradients of y = act(conv(x, w) + bias + residual) as srcnn_conv2d computes it with mode 0, precision 0, F32 formats:
+ * what torch.autograd derives for nn.Conv2d / nn.Linear (the reference has no kernel of its own here).  Both GEMMs run on
+ * v_mfma_f32_32x32x2_f32.  With g = dy where relu == 0 and g = dy * [y > 0] where relu != 0 (y the saved forward output;
+ * y == 0 gives 0, torch's convention):
+ *   db[n]          = sum over (b, oh, ow) of g[b, oh, ow, n]
+ *   dx[b, h, w, c] = sum over (kh, kw, n) of g[b, oh, ow, n] * w[n, kh, kw, c]   for the (oh, ow) with oh * stride - pad + kh = h
+ *                    (and the same for w); taps with no such output pixel contribute nothing
+ *   dw[n, kh, kw, c] = sum over (b, oh, ow) of g[b, oh, ow, n] * x[b, oh * stride - pad + kh, ow * stride - pad + kw, c]
+ *   g_out          = g itself, dense (B, OH, OW, Cout): the gradient of the residual branch
+ * Layouts follow the forward: x and dx are (B, H, W, *) NHWC with pixel stride x_cstride (channels [0, Cin) of every pixel of dx are
+ * written, zeros included -- a 1x1 / stride 2 layer writes 0 to the three pixels in four it never read; floats between Cin and
+ * the stride are left alone); y and dy are read at channels [y_coffset, y_coffset + Cout) of pixels of y_cstride floats; w and dw are
+ * (Cout, KH, KW, Cin); db is (Cout).  Any of dx / dw / db / g_out may be NULL: that gradient is skipped (at least one must be
+ * given); outputs are overwritten, never accumulated into, and need no zero fill.
+ *
+ * SCHEME.  (1) One mask / bias pass reads dy (and y) once and writes g into the workspace as (M, Cp) rows, M = B OH OW, Cp = Cout
+ * rounded up to 32 with zeros in the padding, so that both GEMMs read aligned 128-byte runs whatever Cout is; the same pass
+ * forms the bias partials and writes g_out.  The pass is skipped -- the GEMMs then read dy in place through y_cstride /
+ * y_coffset -- when relu == 0, db and g_out are NULL, Cout is a multiple of 32 and y_cstride, y_coffset are multiples of 4.
+ * (2) dx: a re-layout kernel writes w as (Cin, KH, KW, Cp) into the workspace (weights change every step: it is part of
+ * the call), then an implicit GEMM in gather form, rows = the B H W input pixels, columns = Cin, K = (kh, kw, 32-channel tiles of Cp);
+ * every element of dx is stored once by the workgroup that owns its tile: no memset, no atomics.  (3) dw: a GEMM with rows =
+ * Cout, columns = (kh, kw, c), K = the M output pixels in tiles of 32, split over `splits` contiguous ranges of K tiles.
+ *
+ * DEFINED SUMMATION ORDER (no atomics anywhere; for a given descriptor -- tile_mr, tile_nr and splits included -- results are
+ * run-to-run bit-equal).
+ *   db: stage 1, workgroup q (256 threads) owns pixels [256 q, 256 q + 256) of one 32-channel tile; thread (r = t / 32, c = t % 32)
+ *     adds pixels r, r + 8, r + 16, .. of the block in ascending order from 0; the eight r-sums of a channel are added in
+ *     ascending r from 0 into partial[q][n].  Stage 2, one workgroup per 32-channel tile: thread (r, c) adds partial[r], [r + 8],
+ *     .. in ascending order from 0, then the eight r-sums in ascending r from 0.
+ *   dx: one fmaf chain per element (the MFMA's arithmetic) over taps in (kh, kw) row-major order, inside a tap over the 32-channel
+ *     tiles of Cp in ascending order, inside a tile over the channel pairs (8 j + s, 8 j + 4 + s) for j = 0..3, s = 0..3 in (j, s)
+ *     order -- srcnn_conv2d's K order.  Never split.
+ *   dw: one fmaf chain per element and K slice over the slice's pixels in ascending m = (b, oh, ow) order; slice s covers K tiles
+ *     [s T, min(s T + T, nkt)), T = ceil(nkt / splits), nkt = ceil(M / 32); with more than one slice the slices' sums are added
+ *     in ascending s from 0 by a reduction kernel (partials in the workspace).  Pixels beyond M and taps outside the image enter
+ *     as exact zeros.  splits = 0 lets the library choose (about two workgroups per compute unit, >= 8 K tiles per slice, <= 64
+ *     slices); srcnn_conv2d_backward_workspace_bytes grows with it.
+ * tile_mr / tile_nr in {1, 2} choose the (64 tile_mr) x (64 tile_nr) workgroup tile of BOTH GEMMs (0 = heuristic); any other
+ * value is an error.
+ *
+ * Errors, all before the first launch (SRCNN_ERR_ARG with the reason in srcnn_last_error(); SRCNN_ERR_WORKSPACE for a workspace
+ * smaller than srcnn_conv2d_backward_workspace_bytes, which returns 0 for a descriptor the call would refuse): a null desc /
+ * dy / every output null / x null with dw / w null with dx / y null with relu ("null"); non-positive sizes or OH, OW that are
+ * not the forward's ("shape"); Cin not a multiple of 32; strides too small or x_cstride, not a multiple of 4 ("stride");
+ * mode != 0 ("mode"); precision != 0 ("precision"); a non-F32 format ("format"); head_w / head_wf ("fused head"), x2 ("second
+ * input"), up_top ("upsample") -- the fields exist so that a forward descriptor copied over is refused, not misread. */
+typedef struct srcnn_conv_bwd_desc {
+    const float *x;        /* forward input (needed for dw) */
+    const float *w;        /* forward weights (needed for dx) */
+    const float *y;        /* saved forward output (needed when relu != 0), else NULL */
+    const float *dy;       /* upstream gradient, laid out like y */
+    float *dx, *dw, *db;   /* outputs; NULL = skip */
+    float *g_out;          /* optional: the masked gradient, dense (B, OH, OW, Cout) */
+    int B, H, W, Cin, x_cstride;
+    int OH, OW, Cout;
+    int KH, KW, stride, pad;
+    int y_cstride, y_coffset;
+    int relu;
+    int mode, precision;                   /* must be 0 */
+    int x_format, y_format;                /* must be SRCNN_FMT_F32 */
+    int tile_mr, tile_nr, splits;          /* 0 = heuristic */
+    const void *head_w, *head_wf, *x2, *up_top;   /* must be NULL */
+} srcnn_conv_bwd_desc;
+SRCNN_API size_t srcnn_conv2d_backward_workspace_bytes(const srcnn_conv_bwd_desc *d);
+SRCNN_API int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
 /* SPLIT16 range guard.  The format stores hi = f16(v) unscaled: an activation beyond +-65504 (or a NaN) becomes inf and
  * poisons what it touches, where the fp32 engine would carry on.  Every kernel that writes SPLIT16 from fresh arithmetic

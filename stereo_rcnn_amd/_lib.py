@@ -45,6 +45,19 @@ class ConvDesc(ctypes.Structure):
                 ("up_top", c_void_p), ("up_format", c_int), ("up_H", c_int), ("up_W", c_int)]
 
 
+class ConvBwdDesc(ctypes.Structure):
+    """struct srcnn_conv_bwd_desc (include/srcnn_hip.h)."""
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("y", c_void_p), ("dy", c_void_p),
+                ("dx", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("g_out", c_void_p),
+                ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_cstride", c_int),
+                ("OH", c_int), ("OW", c_int), ("Cout", c_int),
+                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
+                ("y_cstride", c_int), ("y_coffset", c_int), ("relu", c_int),
+                ("mode", c_int), ("precision", c_int), ("x_format", c_int), ("y_format", c_int),
+                ("tile_mr", c_int), ("tile_nr", c_int), ("splits", c_int),
+                ("head_w", c_void_p), ("head_wf", c_void_p), ("x2", c_void_p), ("up_top", c_void_p)]
+
+
 class KittiSplit(ctypes.Structure):
     """struct srcnn_kitti_split (include/srcnn_hip.h): a ragged batch of frames, device pointers."""
     _fields_ = [("n_frames", c_int), ("max_det_per_frame", c_int),
@@ -107,6 +120,8 @@ _SIGNATURES = {
     "srcnn_conv2d_chain_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "srcnn_conv2d_chain": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
     "srcnn_conv2d_group": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
+    "srcnn_conv2d_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
+    "srcnn_conv2d_backward": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
     "srcnn_range_flag_read": (c_int, [c_int]),
     "srcnn_range_flag_device_word": (c_void_p, []),
     "srcnn_range_flag_bind": (c_int, [c_void_p]),

@@ -1,0 +1,559 @@
+// Convolution backward for the exact-fp32 engine: dx, dw, db of y = act(conv(x, w) + bias + residual) (srcnn_conv2d, mode 0).
+//
+// The reference calls cuDNN through torch.autograd for every learnable layer (stereo_rcnn/resnet.py:66-146,243-286;
+// rpn/stereo_rpn.py:32-40); nothing here is derived from it.  include/srcnn_hip.h states the definitions, the scheme and the
+// summation orders; this file is their implementation:
+//
+//   bwd_mask_bias_kernel     g = dy * [y > 0] -> workspace rows of Cp = roundup(Cout, 32) floats (zero padded), g_out, bias partials
+//   bwd_bias_reduce_kernel   partials -> db, fixed order
+//   bwd_weight_relayout      w (Cout, taps, Cin) -> wt (Cin, taps, Cp): dgrad's B operand, K-contiguous rows like the forward's weights
+//   conv_dgrad_kernel        dx: the forward's implicit GEMM (conv_mfma.hip: same tile, LDS layout, prefetch, XCD remap) with the
+//                            A operand GATHERED: row m = input pixel (b, h, w), K tile = 32 channels of g at output pixel
+//                            ((h + pad - kh) / s, (w + pad - kw) / s) when that division is exact and in range, else zeros
+//   conv_wgrad_kernel        dw: rows = Cout, columns = (tap, c), K = output pixels.  Both operands are K-strided in memory (a pixel's
+//                            channels are contiguous), which is the fp32 MFMA's operand layout: lane l holds A[i = l & 31][k = l >> 5],
+//                            so an LDS tile stored [k pixel][channel] -- written with 16-byte stores straight from coalesced
+//                            global rows -- is read back with ds_read_b32 at consecutive addresses over the 32 lanes of a half
+//                            wave: conflict-free (the two halves are served separately) and no padding is needed.
+//   wgrad_reduce_kernel      split-K partials -> dw, ascending slice order
+#include "conv_common.h"
+#include <cstdint>
+
+namespace srcnn {
+
+struct BwdArgs {
+    const float *x, *w, *y, *dy;
+    float *dx, *dw, *db, *g_out;
+    const float *g;            // what the GEMMs read: gp, or dy in place
+    int gcs, gco;              // its pixel stride and channel offset; it has Cp channels
+    float *gp;                 // workspace: masked gradient (M, Cp), or nullptr
+    float *db_part;            // workspace: bias partials (nq, Cp)
+    float *wt;                 // workspace: weights (Cin, taps, Cp)
+    float *partial;            // workspace: wgrad slices (splits, Cout, Kw)
+    int H, W, Cin, xcs;
+    int OH, OW, Cout, Cp;
+    int KH, KW, stride, pad;
+    int ycs, yco, relu;
+    int M, Min;                // output pixels B OH OW, input pixels B H W
+    int taps, Kw;              // KH KW, taps * Cin
+    int d_ctiles, d_nkt, d_mtiles, d_ntiles;                // dgrad: Cp / 32, taps * d_ctiles, tile counts
+    int w_nkt, w_kt_per_split, w_mtiles, w_ntiles;          // wgrad: ceil(M / 32), K tiles per slice, tile counts
+};
+
+struct BwdPlan {
+    bool pass;                 // the mask / bias pass runs
+    int d_mr, d_nr, w_mr, w_nr, splits, nq;
+    size_t off_gp, off_db, off_wt, off_part, bytes;
+};
+
+__global__ __launch_bounds__(256) void bwd_mask_bias_kernel(const BwdArgs p)
+{
+    __shared__ float red[8][32];
+    const int t = threadIdx.x, c = t & 31, r = t >> 5;
+    const int n = blockIdx.y * 32 + c;          // < Cp
+    const bool nok = n < p.Cout;
+    const int m_base = blockIdx.x * 256;
+    float s = 0.f;
+    for (int i = 0; i < 32; ++i) {
+        const int m = m_base + r + 8 * i;
+        if (m >= p.M) break;
+        float v = 0.f;
+        if (nok) {
+            const size_t o = (size_t)m * p.ycs + p.yco + n;
+            v = p.dy[o];
+            if (p.relu && !(p.y[o] > 0.f)) v = 0.f;
+            if (p.g_out) p.g_out[(size_t)m * p.Cout + n] = v;
+        }
+        if (p.gp) p.gp[(size_t)m * p.Cp + n] = v;
+        s += v;
+    }
+    if (!p.db) return;
+    red[r][c] = s;
+    __syncthreads();
+    if (r == 0) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a += red[k][c];
+        p.db_part[(size_t)blockIdx.x * p.Cp + n] = a;
+    }
+}
+
+__global__ __launch_bounds__(256) void bwd_bias_reduce_kernel(const BwdArgs p, int nq)
+{
+    __shared__ float red[8][32];
+    const int t = threadIdx.x, c = t & 31, r = t >> 5;
+    const int n = blockIdx.x * 32 + c;          // < Cp
+    float s = 0.f;
+    for (int q = r; q < nq; q += 8) s += p.db_part[(size_t)q * p.Cp + n];
+    red[r][c] = s;
+    __syncthreads();
+    if (r == 0 && n < p.Cout) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a += red[k][c];
+        p.db[n] = a;
+    }
+}
+
+// grid (Cin / 32, Cp / 32, taps), block (32, 8): one 32 x 32 transpose per block through LDS, both sides coalesced
+__global__ __launch_bounds__(256) void bwd_weight_relayout(const BwdArgs p)
+{
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int c0 = blockIdx.x * 32, n0 = blockIdx.y * 32, tap = blockIdx.z;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + ty + 8 * j;
+        tile[ty + 8 * j][tx] = n < p.Cout ? p.w[((size_t)n * p.taps + tap) * p.Cin + c0 + tx] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = c0 + ty + 8 * j;
+        p.wt[((size_t)c * p.taps + tap) * p.Cp + n0 + tx] = tile[tx][ty + 8 * j];
+    }
+}
+
+// bijective XCD-aware tile id (conv_mfma.hip): consecutive logical tiles run on one XCD and share its L2
+__device__ __forceinline__ int xcd_logical_tile(int bid, int nblk)
+{
+    const int q = nblk >> 3, r = nblk & 7;
+    const int xcd = bid & 7, slot = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+}
+
+template <int MR, int NR>
+__global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
+{
+    constexpr int BM = 64 * MR, BN = 64 * NR;
+    constexpr int A_LD = BM / 32, B_LD = BN / 32;   // float4 loads per thread per tile
+    __shared__ __attribute__((aligned(16))) float smem[2][(BM + BN) * LDS_ROW];
+
+    const int t = threadIdx.x;
+    const int logical = xcd_logical_tile(blockIdx.x, p.d_mtiles * p.d_ntiles);
+    const int mt = logical / p.d_ntiles, nt = logical - mt * p.d_ntiles;
+    const int m0 = mt * BM, n0 = nt * BN;
+
+    const int lrow = t >> 3;          // 0..31
+    const int lcol = (t & 7) * 4;     // float offset inside the 32-float run
+    int a_h[A_LD], a_w[A_LD], a_base[A_LD];
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+        const int m = m0 + lrow + 32 * i;
+        if (m < p.Min) {
+            const int hw = p.H * p.W;
+            const int b = m / hw;
+            const int rem = m - b * hw;
+            const int h = rem / p.W;
+            a_h[i] = h + p.pad;
+            a_w[i] = rem - h * p.W + p.pad;
+            a_base[i] = b * p.OH * p.OW;
+        } else {
+            a_h[i] = -(1 << 28);
+            a_w[i] = 0;
+            a_base[i] = 0;
+        }
+    }
+    const size_t Kd = (size_t)p.taps * p.Cp;
+    const float *b_ptr[B_LD];
+    bool b_ok[B_LD];
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+        const int c = n0 + lrow + 32 * i;
+        b_ok[i] = c < p.Cin;
+        b_ptr[i] = p.wt + (size_t)(b_ok[i] ? c : 0) * Kd + lcol;
+    }
+
+    float4 ra[A_LD], rb[B_LD];
+    auto load_tile = [&](int kt) {
+        const int tap = kt / p.d_ctiles;
+        const int c0 = (kt - tap * p.d_ctiles) * BK;
+        const int kh = tap / p.KW;
+        const int kw = tap - kh * p.KW;
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) {
+            const int th = a_h[i] - kh, tw = a_w[i] - kw;
+            bool ok = th >= 0 && tw >= 0;
+            const int oh = ok ? th / p.stride : 0, ow = ok ? tw / p.stride : 0;
+            ok = ok && oh * p.stride == th && ow * p.stride == tw && oh < p.OH && ow < p.OW;
+            const int pix = ok ? a_base[i] + oh * p.OW + ow : 0;
+            const float4 v = *reinterpret_cast<const float4 *>(p.g + (size_t)pix * p.gcs + p.gco + c0 + lcol);
+            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const float4 v = *reinterpret_cast<const float4 *>(b_ptr[i] + (size_t)kt * BK);
+            rb[i] = b_ok[i] ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store_tile = [&](int buf) {
+        float *sa = smem[buf];
+        float *sb = smem[buf] + BM * LDS_ROW;
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i)
+            *reinterpret_cast<float4 *>(sa + (lrow + 32 * i) * LDS_ROW + lcol) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i)
+            *reinterpret_cast<float4 *>(sb + (lrow + 32 * i) * LDS_ROW + lcol) = rb[i];
+    };
+
+    const int wave = t >> 6, lane = t & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 31, lg = lane >> 5;
+    floatx16 acc[MR][NR];
+#pragma unroll
+    for (int i = 0; i < MR; ++i)
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    const int nkt = p.d_nkt;
+    load_tile(0);
+    store_tile(0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int buf = kt & 1;
+        const bool more = kt + 1 < nkt;
+        if (more) load_tile(kt + 1);
+        const float *sa = smem[buf] + (wm * 32 * MR + li) * LDS_ROW + lg * 4;
+        const float *sb = smem[buf] + BM * LDS_ROW + (wn * 32 * NR + li) * LDS_ROW + lg * 4;
+#pragma unroll
+        for (int kk = 0; kk < BK / 8; ++kk) {
+            float4 fa[MR], fb[NR];
+#pragma unroll
+            for (int i = 0; i < MR; ++i) fa[i] = *reinterpret_cast<const float4 *>(sa + i * 32 * LDS_ROW + kk * 8);
+#pragma unroll
+            for (int j = 0; j < NR; ++j) fb[j] = *reinterpret_cast<const float4 *>(sb + j * 32 * LDS_ROW + kk * 8);
+#pragma unroll
+            for (int i = 0; i < MR; ++i)
+#pragma unroll
+                for (int j = 0; j < NR; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
+                }
+        }
+        if (more) store_tile(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).  Every (row, col) of the tile
+    // inside the tensor is stored, zeros included: dx needs no fill.
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int col = n0 + (wn * NR + j) * 32 + li;
+            if (col >= p.Cin) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
+                if (row >= p.Min) continue;
+                p.dx[(size_t)row * p.xcs + col] = acc[i][j][e];
+            }
+        }
+    }
+}
+
+template <int MR, int NR>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const BwdArgs p)
+{
+    constexpr int BM = 64 * MR, BN = 64 * NR;
+    constexpr int A_LD = BM / 32, B_LD = BN / 32;       // float4 loads per thread per tile (32 pixels x BM / 4 float4 over 256 threads)
+    constexpr int A_Q = BM / 4, B_Q = BN / 4;           // float4 per pixel row
+    constexpr int A_RS = 256 / A_Q, B_RS = 256 / B_Q;   // pixel rows covered by one pass of the 256 threads
+    __shared__ __attribute__((aligned(16))) float smem[2][BK * (BM + BN)];
+
+    const int t = threadIdx.x;
+    const int logical = xcd_logical_tile(blockIdx.x, p.w_mtiles * p.w_ntiles);
+    const int mt = logical / p.w_ntiles, nt = logical - mt * p.w_ntiles;
+    const int n0 = mt * BM, j0 = nt * BN;               // first output channel / first (tap, c) column of the tile
+    const int kt_begin = blockIdx.y * p.w_kt_per_split;
+    const int kt_end = min(p.w_nkt, kt_begin + p.w_kt_per_split);
+
+    // A: g rows.  This thread's channel group is the same in every K tile
+    const int a_c = (t % A_Q) * 4, a_r = t / A_Q;
+    const bool a_ok = n0 + a_c < p.Cp;
+    const float *a_ptr = p.g + p.gco + (a_ok ? n0 + a_c : 0);
+    // B: x rows at a tap.  This thread's (tap, channel group) is the same in every K tile
+    const int b_c = (t % B_Q) * 4, b_r = t / B_Q;
+    const int jcol = j0 + b_c;
+    const bool b_ok = jcol < p.Kw;
+    const int tap = b_ok ? jcol / p.Cin : 0;
+    const int cin0 = b_ok ? jcol - tap * p.Cin : 0;
+    const int kh = tap / p.KW, kw = tap - kh * p.KW;
+    const int ohw = p.OH * p.OW;
+
+    float4 ra[A_LD], rb[B_LD];
+    auto load_tile = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) {
+            const int m = kt * BK + a_r + A_RS * i;
+            const bool ok = a_ok && m < p.M;
+            const float4 v = *reinterpret_cast<const float4 *>(a_ptr + (size_t)(ok ? m : 0) * p.gcs);
+            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const int m = kt * BK + b_r + B_RS * i;
+            bool ok = b_ok && m < p.M;
+            const int mm = ok ? m : 0;
+            const int b = mm / ohw;
+            const int rem = mm - b * ohw;
+            const int oh = rem / p.OW;
+            const int ih = oh * p.stride - p.pad + kh, iw = (rem - oh * p.OW) * p.stride - p.pad + kw;
+            ok = ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+            const int pix = ok ? (b * p.H + ih) * p.W + iw : 0;
+            const float4 v = *reinterpret_cast<const float4 *>(p.x + (size_t)pix * p.xcs + cin0);
+            rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store_tile = [&](int buf) {
+        float *sa = smem[buf];
+        float *sb = smem[buf] + BK * BM;
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) *reinterpret_cast<float4 *>(sa + (a_r + A_RS * i) * BM + a_c) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4 *>(sb + (b_r + B_RS * i) * BN + b_c) = rb[i];
+    };
+
+    const int wave = t >> 6, lane = t & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 31, lg = lane >> 5;
+    floatx16 acc[MR][NR];
+#pragma unroll
+    for (int i = 0; i < MR; ++i)
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    if (kt_begin < kt_end) {
+        load_tile(kt_begin);
+        store_tile(0);
+    }
+    __syncthreads();
+    for (int kt = kt_begin; kt < kt_end; ++kt) {
+        const int buf = (kt - kt_begin) & 1;
+        const bool more = kt + 1 < kt_end;
+        if (more) load_tile(kt + 1);
+        // lane (li, lg) of MFMA step ks holds A[n = li][pixel 2 ks + lg] and B[pixel 2 ks + lg][column li]: ascending pixel order
+        const float *sa = smem[buf] + lg * BM + wm * 32 * MR + li;
+        const float *sb = smem[buf] + BK * BM + lg * BN + wn * 32 * NR + li;
+#pragma unroll
+        for (int ks = 0; ks < BK / 2; ++ks) {
+            float fa[MR], fb[NR];
+#pragma unroll
+            for (int i = 0; i < MR; ++i) fa[i] = sa[2 * ks * BM + i * 32];
+#pragma unroll
+            for (int j = 0; j < NR; ++j) fb[j] = sb[2 * ks * BN + j * 32];
+#pragma unroll
+            for (int i = 0; i < MR; ++i)
+#pragma unroll
+                for (int j = 0; j < NR; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        }
+        if (more) store_tile(buf ^ 1);
+        __syncthreads();
+    }
+
+    const bool split = gridDim.y > 1;
+    float *out = split ? p.partial + (size_t)blockIdx.y * p.Cout * p.Kw : p.dw;
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int col = j0 + (wn * NR + j) * 32 + li;
+            if (col >= p.Kw) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = n0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
+                if (row >= p.Cout) continue;
+                out[(size_t)row * p.Kw + col] = acc[i][j][e];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const BwdArgs p, int splits)
+{
+    const size_t total = (size_t)p.Cout * p.Kw;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        float v = 0.f;
+        for (int s = 0; s < splits; ++s) v += p.partial[(size_t)s * total + idx];
+        p.dw[idx] = v;
+    }
+}
+
+// Validates the descriptor and lays out the call: kernel arguments (workspace pointers as OFFSETS from nullptr until the caller
+// binds them), tiles, slices and the workspace size.
+static int bwd_prepare(const srcnn_conv_bwd_desc *d, BwdArgs &a, BwdPlan &pl)
+{
+    SRCNN_REQUIRE(d != nullptr, "null descriptor");
+    SRCNN_REQUIRE(d->dy != nullptr, "null pointer: dy");
+    SRCNN_REQUIRE(d->dx || d->dw || d->db || d->g_out, "null pointer: no output requested");
+    SRCNN_REQUIRE(!d->dw || d->x, "null pointer: dw needs x");
+    SRCNN_REQUIRE(!d->dx || d->w, "null pointer: dx needs w");
+    SRCNN_REQUIRE(!d->relu || d->y, "null pointer: relu needs the saved output y");
+    SRCNN_REQUIRE(d->mode == 0, "mode 0 only (ConvTranspose2d and the RPN pair mode have no backward)");
+    SRCNN_REQUIRE(d->precision == 0, "precision must be 0 (the exact fp32 engine)");
+    SRCNN_REQUIRE(d->x_format == SRCNN_FMT_F32 && d->y_format == SRCNN_FMT_F32, "format must be SRCNN_FMT_F32");
+    SRCNN_REQUIRE(!d->head_w && !d->head_wf, "a fused head has no backward");
+    SRCNN_REQUIRE(!d->x2, "a second input has no backward");
+    SRCNN_REQUIRE(!d->up_top, "the fused upsample-add has no backward");
+    SRCNN_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->Cin > 0, "bad shape: sizes must be positive");
+    SRCNN_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "bad shape: kernel, stride > 0 and pad >= 0");
+    SRCNN_REQUIRE(d->H + 2 * d->pad >= d->KH && d->W + 2 * d->pad >= d->KW &&
+                      d->OH == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
+                  "bad shape: OH / OW are not the forward's output size");
+    SRCNN_REQUIRE(d->Cin % BK == 0, "Cin must be a positive multiple of 32");
+    SRCNN_REQUIRE(d->x_cstride >= d->Cin && d->x_cstride % 4 == 0, "x_cstride: a stride of at least Cin floats, a multiple of 4");
+    SRCNN_REQUIRE(d->y_coffset >= 0 && d->y_cstride >= d->y_coffset + d->Cout, "y_cstride: a stride of at least y_coffset + Cout floats");
+    SRCNN_REQUIRE(!d->dw || (reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "x must be 16-byte aligned (stride-4 vector loads)");
+    SRCNN_REQUIRE((unsigned)d->tile_mr <= 2 && (unsigned)d->tile_nr <= 2, "tile_mr / tile_nr must be 0, 1 or 2");
+    SRCNN_REQUIRE(d->splits >= 0, "splits must be >= 0");
+    const long long M = (long long)d->B * d->OH * d->OW, Min = (long long)d->B * d->H * d->W;
+    const long long Kw = (long long)d->KH * d->KW * d->Cin;
+    SRCNN_REQUIRE(M < (1LL << 31) && Min < (1LL << 31) && Kw < (1LL << 31) && d->Cout < (1 << 20) && d->KH < 256 && d->KW < 256,
+                  "bad shape: tensor too large");
+
+    a.x = d->x; a.w = d->w; a.y = d->y; a.dy = d->dy;
+    a.dx = d->dx; a.dw = d->dw; a.db = d->db; a.g_out = d->g_out;
+    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
+    a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+    a.ycs = d->y_cstride; a.yco = d->y_coffset; a.relu = d->relu ? 1 : 0;
+    a.M = (int)M; a.Min = (int)Min; a.taps = d->KH * d->KW; a.Kw = (int)Kw;
+    const bool gemm = d->dx || d->dw;
+    pl.pass = d->relu || d->db || d->g_out || d->Cout % BK != 0 || d->y_cstride % 4 != 0 || d->y_coffset % 4 != 0 ||
+              (reinterpret_cast<uintptr_t>(d->dy) & 15) != 0;
+    pl.nq = cdiv(a.M, 256);
+
+    // dgrad tile: the forward's rule (conv_mfma.hip make_plan) -- the largest tile that still gives two workgroups per CU
+    pl.d_mr = pl.d_nr = 1;
+    {
+        static const int cand[4][2] = {{2, 2}, {2, 1}, {1, 2}, {1, 1}};
+        for (auto &c : cand) {
+            if (c[1] == 2 && a.Cin <= 64) continue;
+            if ((long)cdiv(a.Min, 64 * c[0]) * cdiv(a.Cin, 64 * c[1]) >= 512) {
+                pl.d_mr = c[0];
+                pl.d_nr = c[1];
+                break;
+            }
+        }
+    }
+    // wgrad tile: M x N is small and K long, so the tile is as large as the matrix allows and split-K fills the chip
+    pl.w_mr = a.Cout > 64 ? 2 : 1;
+    pl.w_nr = a.Kw > 64 ? 2 : 1;
+    if (d->tile_mr > 0 && d->tile_nr > 0) {
+        pl.d_mr = pl.w_mr = d->tile_mr;
+        pl.d_nr = pl.w_nr = d->tile_nr;
+    }
+    a.d_ctiles = a.Cp / BK;
+    a.d_nkt = a.taps * a.d_ctiles;
+    a.d_mtiles = cdiv(a.Min, 64 * pl.d_mr);
+    a.d_ntiles = cdiv(a.Cin, 64 * pl.d_nr);
+    SRCNN_REQUIRE((long long)a.d_mtiles * a.d_ntiles < (1LL << 31), "bad shape: tensor too large");
+    a.w_nkt = cdiv(a.M, BK);
+    a.w_mtiles = cdiv(a.Cout, 64 * pl.w_mr);
+    a.w_ntiles = cdiv(a.Kw, 64 * pl.w_nr);
+    SRCNN_REQUIRE((long long)a.w_mtiles * a.w_ntiles < (1LL << 31), "bad shape: tensor too large");
+    int s = d->splits;
+    if (s <= 0) {
+        const long blocks = (long)a.w_mtiles * a.w_ntiles;
+        s = (int)min(64L, (512 + blocks - 1) / blocks);
+        s = min(s, max(1, a.w_nkt / 8));
+    }
+    s = max(1, min(min(s, a.w_nkt), 65535));
+    a.w_kt_per_split = cdiv(a.w_nkt, s);
+    pl.splits = cdiv(a.w_nkt, a.w_kt_per_split);
+
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        const size_t at = off;
+        off += align_up(floats * sizeof(float), 256);
+        return at;
+    };
+    pl.off_gp = pl.off_db = pl.off_wt = pl.off_part = 0;
+    if (pl.pass && gemm) pl.off_gp = take((size_t)a.M * a.Cp);
+    if (d->db) pl.off_db = take((size_t)pl.nq * a.Cp);
+    if (d->dx) pl.off_wt = take((size_t)a.Cin * a.taps * a.Cp);
+    if (d->dw && pl.splits > 1) pl.off_part = take((size_t)pl.splits * a.Cout * a.Kw);
+    pl.bytes = off > 256 ? off : 256;
+    return SRCNN_OK;
+}
+
+template <int MR, int NR>
+static void launch_dgrad(const BwdArgs &a, hipStream_t st)
+{
+    SRCNN_LAUNCH((conv_dgrad_kernel<MR, NR>), dim3(a.d_mtiles * a.d_ntiles), dim3(256), 0, st, a);
+}
+
+template <int MR, int NR>
+static void launch_wgrad(const BwdArgs &a, int splits, hipStream_t st)
+{
+    SRCNN_LAUNCH((conv_wgrad_kernel<MR, NR>), dim3(a.w_mtiles * a.w_ntiles, splits), dim3(256), 0, st, a);
+}
+
+}  // namespace srcnn
+
+extern "C" {
+
+size_t srcnn_conv2d_backward_workspace_bytes(const srcnn_conv_bwd_desc *d)
+{
+    using namespace srcnn;
+    BwdArgs a;
+    BwdPlan pl;
+    if (bwd_prepare(d, a, pl) != SRCNN_OK) return 0;
+    return pl.bytes;
+}
+
+int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
+{
+    using namespace srcnn;
+    BwdArgs a;
+    BwdPlan pl;
+    int rc = bwd_prepare(d, a, pl);
+    if (rc != SRCNN_OK) return rc;
+    if (!workspace || workspace_bytes < pl.bytes) {
+        set_error("srcnn_conv2d_backward: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
+        return SRCNN_ERR_WORKSPACE;
+    }
+    char *ws = static_cast<char *>(workspace);
+    const bool gemm = d->dx || d->dw;
+    a.gp = (pl.pass && gemm) ? reinterpret_cast<float *>(ws + pl.off_gp) : nullptr;
+    a.db_part = d->db ? reinterpret_cast<float *>(ws + pl.off_db) : nullptr;
+    a.wt = d->dx ? reinterpret_cast<float *>(ws + pl.off_wt) : nullptr;
+    a.partial = (d->dw && pl.splits > 1) ? reinterpret_cast<float *>(ws + pl.off_part) : nullptr;
+    if (pl.pass) {
+        a.g = a.gp; a.gcs = a.Cp; a.gco = 0;
+    } else {
+        a.g = a.dy; a.gcs = a.ycs; a.gco = a.yco;
+    }
+    hipStream_t st = as_stream(stream);
+    if (pl.pass) {
+        SRCNN_LAUNCH(bwd_mask_bias_kernel, dim3(pl.nq, a.Cp / BK), dim3(256), 0, st, a);
+        if (d->db) SRCNN_LAUNCH(bwd_bias_reduce_kernel, dim3(a.Cp / BK), dim3(256), 0, st, a, pl.nq);
+    }
+    if (d->dx) {
+        SRCNN_LAUNCH(bwd_weight_relayout, dim3(a.Cin / BK, a.Cp / BK, a.taps), dim3(32, 8), 0, st, a);
+        if (pl.d_mr == 2 && pl.d_nr == 2) launch_dgrad<2, 2>(a, st);
+        else if (pl.d_mr == 2) launch_dgrad<2, 1>(a, st);
+        else if (pl.d_nr == 2) launch_dgrad<1, 2>(a, st);
+        else launch_dgrad<1, 1>(a, st);
+    }
+    if (d->dw) {
+        if (pl.w_mr == 2 && pl.w_nr == 2) launch_wgrad<2, 2>(a, pl.splits, st);
+        else if (pl.w_mr == 2) launch_wgrad<2, 1>(a, pl.splits, st);
+        else if (pl.w_nr == 2) launch_wgrad<1, 2>(a, pl.splits, st);
+        else launch_wgrad<1, 1>(a, pl.splits, st);
+        if (pl.splits > 1) {
+            const size_t total = (size_t)a.Cout * a.Kw;
+            SRCNN_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)min((size_t)2048, (total + 255) / 256)), dim3(256), 0, st, a, pl.splits);
+        }
+    }
+    return check_launch("srcnn_conv2d_backward");
+}
+
+}  // extern "C"

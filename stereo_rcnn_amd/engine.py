@@ -615,6 +615,50 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
     return used
 
 
+def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), splits=0, x_cstride=None, y_cstride=None, y_coffset=0,
+                    relu=None, g_out=None, out=None, tile=None):
+    """Gradients of conv2d(cw, x, ..., precision='f32') (srcnn_conv2d_backward; include/srcnn_hip.h states the sums' orders).
+    x (B, H, W, *) and dy / y (B, OH, OW, *) are raw NHWC device tensors with the forward's strides; y is the saved forward output
+    (needed when relu, else may be None); relu defaults to cw.relu.  want: which of 'dx' (like x: pixel stride x_cstride), 'dw'
+    (Cout, KH, KW, Cin) and 'db' (Cout) to compute -- the others are neither computed nor allocated.  g_out: optional dense
+    (B, OH, OW, Cout) tensor that receives the masked gradient dy * [y > 0] (the residual branch's gradient).  out: {name: tensor}
+    to write into instead of fresh tensors (every element is overwritten).  splits: K slices of the weight gradient (0 = the
+    library's choice); tile: (tile_mr, tile_nr).  Returns {name: tensor} for the names in want."""
+    L = _lib.lib()
+    assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a backward"
+    unknown = set(want) - {'dx', 'dw', 'db'}
+    assert not unknown, unknown
+    d = _lib.ConvBwdDesc()
+    xcs = cw.cin if x_cstride is None else x_cstride
+    res = dict(out or {})
+    if 'dx' in want and 'dx' not in res:
+        res['dx'] = torch.empty((B, H, W, xcs), dtype=torch.float32, device=dy.device)
+    if 'dw' in want and 'dw' not in res:
+        res['dw'] = torch.empty((cw.cout, cw.kh, cw.kw, cw.cin), dtype=torch.float32, device=dy.device)
+    if 'db' in want and 'db' not in res:
+        res['db'] = torch.empty((cw.cout,), dtype=torch.float32, device=dy.device)
+    res = {k: res[k] for k in want}
+    d.x = x.data_ptr() if x is not None else None
+    d.w = cw.weight.data_ptr()
+    d.y = y.data_ptr() if y is not None else None
+    d.dy = dy.data_ptr()
+    d.dx, d.dw, d.db = (res[k].data_ptr() if k in res else None for k in ('dx', 'dw', 'db'))
+    d.g_out = g_out.data_ptr() if g_out is not None else None
+    d.B, d.H, d.W, d.Cin, d.x_cstride = B, H, W, cw.cin, xcs
+    d.OH, d.OW, d.Cout = OH, OW, cw.cout
+    d.KH, d.KW, d.stride, d.pad = cw.kh, cw.kw, cw.stride, cw.pad
+    d.y_cstride = cw.cout if y_cstride is None else y_cstride
+    d.y_coffset = y_coffset
+    d.relu = cw.relu if relu is None else int(relu)
+    d.splits = int(splits)
+    if tile is not None:
+        d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
+    nbytes = L.srcnn_conv2d_backward_workspace_bytes(ctypes.byref(d))
+    ws = _lib.workspace(nbytes, dy.device, "conv_backward")
+    _lib.check(L.srcnn_conv2d_backward(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_backward")
+    return res
+
+
 def chain_enabled():
     if BOTTLENECK_CHAIN == 'auto':
         from . import streams

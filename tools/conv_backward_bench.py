@@ -1,0 +1,126 @@
+"""Convolution backward (dx + dw + db in one srcnn_conv2d_backward call) against torch's own fp32 convolution backward.
+
+    python tools/conv_backward_bench.py [--out profiles/conv_backward_bench.txt] [--reps 50]
+
+Shapes: the trainable trunk and head at B = 1, one 600 x 1987 image (pyramid maps 150x497, 75x249, 38x125, 19x63) -- the (M, N, K)
+of the per-layer table (stereo_rcnn_amd/layer_table.py) for a representative bottleneck of layer2 / layer3 / layer4, an FPN lateral
+and a smooth conv, RPN_Conv and the 24-channel RPN head on P2, RCNN_top and the stacked linear heads at 512 rois
+(cfg.TRAIN.BATCH_SIZE).  layer0 / layer1 are frozen in the reference and not listed.
+  * hip   : srcnn_conv2d_backward (mask / bias pass, weight re-layout, dgrad, wgrad, split-K reduction -- everything the call
+            issues, the re-layout included: weights change every step), heuristic tiles and splits, ReLU mask on;
+  * torch : aten.convolution_backward (dx, dw, db) on the same values in NCHW float32 plus the ReLU's threshold_backward, i.e.
+            what torch.autograd runs for relu(conv(x)) on this device;
+  * fwd   : the exact-fp32 forward (srcnn_conv2d, precision 0, heuristic plan) of the same layer, the second yardstick.
+FLOPs: 2 M N K for the forward, twice that for the backward (dgrad + wgrad), whatever zeros a stride multiplies.
+One process, 10 untimed runs of each first; hip and torch ALTERNATE; every run is timed with device events; medians of --reps.
+The parent runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
+import argparse
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# name, B, H, W, Cin, Cout, k, stride, pad
+LAYERS = [
+    ('layer2.conv2 3x3', 1, 75, 249, 128, 128, 3, 1, 1),
+    ('layer2.conv3 1x1', 1, 75, 249, 128, 512, 1, 1, 0),
+    ('layer2.downsample 1x1/2', 1, 150, 497, 256, 512, 1, 2, 0),
+    ('layer3.conv1 1x1', 1, 38, 125, 1024, 256, 1, 1, 0),
+    ('layer3.conv2 3x3', 1, 38, 125, 256, 256, 3, 1, 1),
+    ('layer3.conv3 1x1', 1, 38, 125, 256, 1024, 1, 1, 0),
+    ('layer3.downsample 1x1/2', 1, 75, 249, 512, 1024, 1, 2, 0),
+    ('layer4.conv2 3x3', 1, 19, 63, 512, 512, 3, 1, 1),
+    ('layer4.conv3 1x1', 1, 19, 63, 512, 2048, 1, 1, 0),
+    ('fpn.lateral C2 1x1', 1, 150, 497, 256, 256, 1, 1, 0),
+    ('fpn.smooth P2 3x3', 1, 150, 497, 256, 256, 3, 1, 1),
+    ('RPN_Conv P2 3x3', 1, 150, 497, 256, 512, 3, 1, 1),
+    ('RPN head P2 1x1 (24)', 1, 150, 497, 512, 24, 1, 1, 0),
+    ('RCNN_top 7x7/7, 512 rois', 512, 7, 7, 512, 2048, 7, 7, 0),
+    ('RCNN_top 1x1, 512 rois', 512, 1, 1, 2048, 2048, 1, 1, 0),
+    ('linear heads (24), 512 rois', 512, 1, 1, 2048, 24, 1, 1, 0),
+]
+
+
+def child(reps):
+    import numpy as np
+    import torch
+    from stereo_rcnn_amd import _lib, engine
+    _lib.lib()
+    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
+    dev = torch.device('cuda:0')
+    aten = torch.ops.aten
+    print('%-30s %9s %6s %7s | %9s %7s | %9s %7s | %9s %7s' % ('layer', 'M', 'N', 'K', 'hip us', 'TF/s', 'torch us', 'TF/s', 'hip/torch', 'fwd TF/s'))
+    for name, B, H, W, cin, cout, k, s, p in LAYERS:
+        gen = torch.Generator().manual_seed(1)
+        OH, OW = engine.conv_out_hw(H, W, k, k, s, p)
+        x = torch.randn(B, H, W, cin, generator=gen).to(dev)
+        w = (torch.randn(cout, k, k, cin, generator=gen) / float(k * k * cin) ** 0.5).to(dev)
+        dy = torch.randn(B, OH, OW, cout, generator=gen).to(dev)
+        cw = engine.ConvW(w, torch.zeros(cout, device=dev), k, k, s, p, True)
+        y = torch.empty(B, OH, OW, cout, device=dev)
+        out = {'dx': torch.empty(B, H, W, cin, device=dev), 'dw': torch.empty_like(w), 'db': torch.empty(cout, device=dev)}
+        xn, wn = x.permute(0, 3, 1, 2).contiguous(), w.permute(0, 3, 1, 2).contiguous()
+        yn, dyn = None, dy.permute(0, 3, 1, 2).contiguous()
+
+        def fwd():
+            engine.conv2d(cw, x, B, H, W, y, OH, OW, precision='f32', plan=(0, 0, 0, 0, 0))
+
+        def hip():
+            engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, out=out)
+
+        def eager():
+            g = aten.threshold_backward(dyn, yn, 0)
+            return aten.convolution_backward(g, xn, wn, [cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [True, True, True])
+
+        fwd()
+        yn = y.permute(0, 3, 1, 2).contiguous()
+        hip()
+        ref = eager()
+        torch.cuda.synchronize()
+        agree = [float((a - b).abs().max() / b.abs().max()) for a, b in
+                 ((out['dx'].permute(0, 3, 1, 2), ref[0]), (out['dw'].permute(0, 3, 1, 2), ref[1]), (out['db'], ref[2]))]
+        assert max(agree) < 1e-3, (name, agree)            # the two compute the same thing (the tests hold the real bound)
+        times = {'hip': [], 'torch': [], 'fwd': []}
+        for rep in range(reps + 10):
+            for key, fn in (('hip', hip), ('torch', eager), ('fwd', fwd)):          # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if rep >= 10:
+                    times[key].append(e0.elapsed_time(e1) * 1e3)
+        med = {k_: float(np.median(v)) for k_, v in times.items()}
+        M, K = B * OH * OW, k * k * cin
+        fl = 2.0 * M * cout * K
+        print('%-30s %9d %6d %7d | %9.1f %7.1f | %9.1f %7.1f | %9.2f %7.1f'
+              % (name, M, cout, K, med['hip'], 2 * fl / med['hip'] / 1e6, med['torch'], 2 * fl / med['torch'] / 1e6,
+                 med['hip'] / med['torch'], fl / med['fwd'] / 1e6), flush=True)
+    print('(times are medians of %d runs in us, event-timed one call at a time, launch overhead of the 3 to 6 launches of a call included;'
+          ' TF/s = 4 M N K / time for the backward, 2 M N K / time for the forward)' % reps)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'conv_backward_bench.txt'))
+    ap.add_argument('--reps', type=int, default=50)
+    ap.add_argument('--child', action='store_true')
+    ap.add_argument('--timeout', type=int, default=420)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.reps)
+    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
+                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
+    sys.stdout.write(r.stdout)
+    if r.returncode != 0:
+        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write('# python tools/conv_backward_bench.py --reps %d   (see the tool for what each column measures)\n' % a.reps)
+        f.write(r.stdout)
+
+
+if __name__ == '__main__':
+    main()

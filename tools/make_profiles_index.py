@@ -31,6 +31,7 @@ COMMANDS = [      # (family regex, how the family is produced)
     (r'^skip_probe', 'python tools/skip_probe.py'),
     (r'^energy_per_kernel', 'python tools/energy_probe.py'),
     (r'^tune_', 'tools/tune_headline.py / tools/tune_from_shipped.py'),
+    (r'^conv_backward_bench', 'python tools/conv_backward_bench.py   (srcnn_conv2d_backward against torch\'s convolution backward, per layer)'),
     (r'^conv_microbench', 'SWEEP=1 python tools/conv_bench.py f16s | f32'),
 ]
 
