@@ -335,6 +335,44 @@ typedef struct srcnn_conv_bwd_desc {
 SRCNN_API size_t srcnn_conv2d_backward_workspace_bytes(const srcnn_conv_bwd_desc *d);
 SRCNN_API int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
+/* ------------------------------------------------- training: remaining adjoints
+ * The three differentiable operators of the reference's training branch that are neither a convolution, a ROIAlign nor a loss:
+ * _upsample_add (stereo_rcnn.py:91-108), MaxPool2d(1, stride 2) (stereo_rcnn.py:39,168) and the layout step of
+ * ConvTranspose2d(256, 256, 2, 2) (conv mode 1).  NHWC float32, channel counts multiples of 8, 16-byte aligned pointers.  No
+ * atomics: every output element is owned by one thread and written exactly once (zeros included), so outputs need no zero fill
+ * and results are run-to-run bit-equal.
+ *
+ * srcnn_upsample_add_backward: the adjoint of srcnn_upsample_add with respect to top; dy (B, H, W, C), d_top (B, TH, TW, C).  (The
+ * lateral's gradient is dy itself; no kernel.)  With the forward's float32 expressions rh = (TH - 1) / (H - 1) (0 for H == 1),
+ * h1 = (int)(rh * h), h1p = [h1 < TH - 1], h1l = rh * h - h1, h0l = 1 - h1l, and the same for columns, the forward reads for
+ * output pixel (h, w) the four taps  (h1, w1) (h1, w1 + w1p) (h1 + h1p, w1) (h1 + h1p, w1 + w1p)  with coefficients
+ * h0l w0l, h0l w1l, h1l w0l, h1l w1l.  Then
+ *   d_top[b, th, tw, c] = sum over (h, w, tap) with tap position == (th, tw) of coefficient * dy[b, h, w, c]
+ * in gather form, one thread per (top pixel, 8-channel group).  Candidate rows are taken from th / rh with one row of slack on
+ * each side and accepted only after h1 has been recomputed the forward's way, so a rounding disagreement can neither drop nor
+ * double a term; at the last top row, where h1p == 0, both row taps of an output row are the same top row and both count.
+ * DEFINED SUMMATION ORDER: ascending h, inside a row ascending w, inside an output pixel the four taps in the order above; one
+ * chain acc = fmaf(k, dy, acc) from 0 with k = hl * wl rounded to float32 once.  rh == 0 (H == 1 or TH == 1): every output
+ * row reads top row 0.  Holds for any H >= TH, W >= TW, not only H ~ 2 TH.
+ *
+ * srcnn_subsample2_backward: dx[b, 2i, 2j, :] = dy[b, i, j, :] and 0 elsewhere; dy (B, OH, OW, C), dx (B, H, W, C),
+ * OH = ceil(H / 2), OW = ceil(W / 2) (H, W may be odd).  No sum.
+ *
+ * srcnn_pixel_shuffle2: the layout step of conv mode 1 as a copy of its own.  packed (M, h, w, 4 Cq), channels ordered (i, j, co)
+ * as engine.prep_deconv2x2 orders the GEMM's rows, and wide (M, 2h, 2w, Cq):  wide[m, 2a + i, 2b + j, co] =
+ * packed[m, a, b, (2i + j) Cq + co].  inverse == 0: x is packed, y is wide; inverse == 1: x is wide, y is packed.  No sum.  With it
+ * the differentiable deconvolution is a mode-0 1x1 convolution to 4 Cq channels (+ ReLU) followed by the shuffle, and its
+ * backward the inverse shuffle of dy followed by srcnn_conv2d_backward, which keeps refusing mode != 0.
+ *
+ * Errors, all before the first launch (SRCNN_ERR_ARG with the reason in srcnn_last_error()): a null pointer ("null"); a
+ * non-positive size, H < TH or W < TW, OH / OW that are not ceil(H / 2) / ceil(W / 2), inverse outside {0, 1}, a map beyond the
+ * launch grid ("shape"); a channel count that is not a multiple of 8 ("stride"); a pointer that is not 16-byte aligned
+ * ("aligned"). */
+SRCNN_API int srcnn_upsample_add_backward(const float *dy, int B, int H, int W, int C, float *d_top, int TH, int TW,
+                                          srcnn_stream_t stream);
+SRCNN_API int srcnn_subsample2_backward(const float *dy, int B, int OH, int OW, int C, float *dx, int H, int W, srcnn_stream_t stream);
+SRCNN_API int srcnn_pixel_shuffle2(const float *x, int M, int h, int w, int Cq, float *y, int inverse, srcnn_stream_t stream);
+
 /* SPLIT16 range guard.  The format stores hi = f16(v) unscaled: an activation beyond +-65504 (or a NaN) becomes inf and
  * poisons what it touches, where the fp32 engine would carry on.  Every kernel that writes SPLIT16 from fresh arithmetic
  * records it: a library-owned device word keeps max(layer_tag + 1) over the launches that produced such a value since

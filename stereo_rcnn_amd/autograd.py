@@ -1,14 +1,19 @@
-"""Differentiable convolution and linear layers on the exact-fp32 HIP engine.
+"""Differentiable convolution, linear, FPN top-down and deconvolution layers on the exact-fp32 HIP engine.
 
 Every learnable layer of the network goes through the conv engine (the ResNet and FPN convs, RPN_Conv and its heads, RCNN_top,
 the linear heads, the keypoint tower).  These functions are that engine with a backward: the forward is `engine.conv2d(...,
 precision='f32')`, the backward `engine.conv2d_backward` (srcnn_conv2d_backward: dx, dw, db on the fp32 MFMA; include/srcnn_hip.h
 states the sums and their order).  Tensors are NCHW at the edge and NHWC inside, like the ROIAlign modules.  Nothing here waits for
 the device.  CPU tensors raise NotImplementedError, as the project's other ops.
+
+conv2d_nhwc is the same convolution NHWC to NHWC: a graph of many layers (stereo_rcnn_amd.training) stays in the engine's layout
+and pays no transpose per layer.  upsample_add, subsample2 and conv_transpose2x2 are the three remaining differentiable operators
+of the reference's training branch (_upsample_add, MaxPool2d(1, stride 2), ConvTranspose2d(k=2, s=2) + ReLU) over the adjoint
+kernels of csrc/train_ops.hip; they are NHWC on both sides.
 """
 import torch
 
-from . import engine
+from . import _lib, engine
 
 
 def _bn_scale_shift(bn, eps=1e-5):
@@ -116,3 +121,133 @@ def linear(x, weight, bias=None, relu=False):
     out = int(weight.shape[0])
     y = _Conv2dNHWC.apply(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu))
     return y.view(n, out)
+
+
+def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None):
+    """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
+    (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back)."""
+    _check(x, weight)
+    if int(x.shape[3]) % 32 != 0:
+        raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
+    w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
+    return _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
+                             int(stride), int(padding), bool(relu))
+
+
+def _check_nhwc(x, what):
+    if not x.is_cuda:
+        raise NotImplementedError
+    if x.dtype != torch.float32:
+        raise TypeError("float32 tensors only")
+    if x.dim() != 4 or int(x.shape[3]) % 8 != 0:
+        raise ValueError("%s: (B, H, W, C) with C a multiple of 8 (got %s)" % (what, tuple(x.shape)))
+
+
+class _UpsampleAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, top, lateral):
+        B, H, W, C = (int(v) for v in lateral.shape)
+        TH, TW = int(top.shape[1]), int(top.shape[2])
+        y = torch.empty_like(lateral)
+        engine.upsample_add(top, TH, TW, lateral, B, H, W, C, y)
+        ctx.geom = (B, H, W, C, TH, TW)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, H, W, C, TH, TW = ctx.geom
+        dy = dy.contiguous()
+        d_top = None
+        if ctx.needs_input_grad[0]:
+            d_top = torch.empty((B, TH, TW, C), dtype=torch.float32, device=dy.device)
+            _lib.check(_lib.lib().srcnn_upsample_add_backward(dy.data_ptr(), B, H, W, C, d_top.data_ptr(), TH, TW, _lib.stream()),
+                       "srcnn_upsample_add_backward")
+        return d_top, (dy if ctx.needs_input_grad[1] else None)        # the lateral's gradient is dy itself
+
+
+def upsample_add(top, lateral):
+    """bilinear(top -> lateral's size, align_corners=True) + lateral (stereo_rcnn.py:91-108): top (B, TH, TW, C), lateral
+    (B, H, W, C) with H >= TH, W >= TW; NHWC, differentiable with respect to both."""
+    _check_nhwc(top, "upsample_add"), _check_nhwc(lateral, "upsample_add")
+    if top.shape[0] != lateral.shape[0] or top.shape[3] != lateral.shape[3] or top.shape[1] > lateral.shape[1] \
+            or top.shape[2] > lateral.shape[2]:
+        raise ValueError("upsample_add: top %s does not go with lateral %s" % (tuple(top.shape), tuple(lateral.shape)))
+    return _UpsampleAdd.apply(top.contiguous(), lateral.contiguous())
+
+
+class _Subsample2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        B, H, W, C = (int(v) for v in x.shape)
+        OH, OW = (H + 1) // 2, (W + 1) // 2
+        y = torch.empty((B, OH, OW, C), dtype=torch.float32, device=x.device)
+        engine.subsample2(x, B, H, W, C, y, OH, OW)
+        ctx.geom = (B, H, W, C, OH, OW)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, H, W, C, OH, OW = ctx.geom
+        dy = dy.contiguous()
+        dx = torch.empty((B, H, W, C), dtype=torch.float32, device=dy.device)
+        _lib.check(_lib.lib().srcnn_subsample2_backward(dy.data_ptr(), B, OH, OW, C, dx.data_ptr(), H, W, _lib.stream()),
+                   "srcnn_subsample2_backward")
+        return dx
+
+
+def subsample2(x):
+    """MaxPool2d(1, stride=2) (stereo_rcnn.py:39,168): y[b, i, j, :] = x[b, 2i, 2j, :], NHWC, differentiable."""
+    _check_nhwc(x, "subsample2")
+    return _Subsample2.apply(x.contiguous())
+
+
+def pixel_shuffle2(x, cq, inverse=False):
+    """srcnn_pixel_shuffle2: packed (M, h, w, 4 cq) ordered (i, j, co) -> (M, 2h, 2w, cq), or back with inverse: (M, 2h, 2w, cq)
+    -> (M, h, w, 4 cq).  float32 device tensors, cq a multiple of 8; a shape that is not one of the two raises ValueError."""
+    _check_nhwc(x, "pixel_shuffle2")
+    cq = int(cq)
+    M, H, W, C = (int(v) for v in x.shape)
+    if cq <= 0 or cq % 8 != 0:
+        raise ValueError("pixel_shuffle2: cq must be a positive multiple of 8 (got %d)" % cq)
+    if inverse:
+        if C != cq or H % 2 != 0 or W % 2 != 0:
+            raise ValueError("pixel_shuffle2 inverse: (M, 2h, 2w, %d) expected (got %s)" % (cq, tuple(x.shape)))
+        h, w = H // 2, W // 2
+    else:
+        if C != 4 * cq:
+            raise ValueError("pixel_shuffle2: (M, h, w, %d) expected (got %s)" % (4 * cq, tuple(x.shape)))
+        h, w = H, W
+    x = x.contiguous()
+    y = torch.empty((M, h, w, 4 * cq) if inverse else (M, 2 * h, 2 * w, cq), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().srcnn_pixel_shuffle2(x.data_ptr(), M, h, w, cq, y.data_ptr(), int(bool(inverse)), _lib.stream()),
+               "srcnn_pixel_shuffle2")
+    return y
+
+
+class _PixelShuffle2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cq):
+        ctx.cq = cq
+        return pixel_shuffle2(x, cq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
+
+
+def conv_transpose2x2(x, weight, bias=None, relu=False):
+    """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
+    nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
+    engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
+    with the shuffle and stays in the convolution's epilogue.  Backward: the inverse shuffle of dy, then the convolution's
+    backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups."""
+    _check(x, weight)
+    cin, cout = int(weight.shape[0]), int(weight.shape[1])
+    if tuple(weight.shape[2:]) != (2, 2) or int(x.shape[3]) != cin:
+        raise ValueError("conv_transpose2x2: weight (Cin, Cout, 2, 2) with x's Cin (got %s)" % (tuple(weight.shape),))
+    if cin % 32 != 0 or cout % 8 != 0:
+        raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
+    w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
+    b = None if bias is None else bias.repeat(4)
+    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu))
+    return _PixelShuffle2.apply(y, cout)
