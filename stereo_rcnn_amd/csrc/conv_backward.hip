@@ -7,7 +7,7 @@
 //   bwd_mask_bias_kernel     g = dy * [y > 0] -> workspace rows of Cp = roundup(Cout, 32) floats (zero padded), g_out, bias partials
 //   bwd_bias_reduce_kernel   partials -> db, fixed order
 //   bwd_weight_relayout      w (Cout, taps, Cin) -> wt (Cin, taps, Cp): dgrad's B operand, K-contiguous rows like the forward's weights
-//   conv_dgrad_kernel        dx: the forward's implicit GEMM (conv_mfma.hip: same tile, LDS layout, prefetch, XCD remap) with the
+//   conv_dgrad_kernel        dx: the forward's implicit GEMM (conv_tile_4w.h: the same tile, LDS layout, prefetch, XCD remap) with the
 //                            A operand GATHERED: row m = input pixel (b, h, w), K tile = 32 channels of g at output pixel
 //                            ((h + pad - kh) / s, (w + pad - kw) / s) when that division is exact and in range, else zeros
 //   conv_wgrad_kernel        dw: rows = Cout, columns = (tap, c), K = output pixels.  Both operands are K-strided in memory (a pixel's
@@ -16,7 +16,7 @@
 //                            global rows -- is read back with ds_read_b32 at consecutive addresses over the 32 lanes of a half
 //                            wave: conflict-free (the two halves are served separately) and no padding is needed.
 //   wgrad_reduce_kernel      split-K partials -> dw, ascending slice order
-#include "conv_common.h"
+#include "conv_tile_4w.h"
 #include <cstdint>
 
 namespace srcnn {
@@ -114,14 +114,6 @@ __global__ __launch_bounds__(256) void bwd_weight_relayout(const BwdArgs p)
     }
 }
 
-// bijective XCD-aware tile id (conv_mfma.hip): consecutive logical tiles run on one XCD and share its L2
-__device__ __forceinline__ int xcd_logical_tile(int bid, int nblk)
-{
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-}
-
 template <int MR, int NR>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
 {
@@ -154,15 +146,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
             a_base[i] = 0;
         }
     }
-    const size_t Kd = (size_t)p.taps * p.Cp;
-    const float *b_ptr[B_LD];
-    bool b_ok[B_LD];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-        const int c = n0 + lrow + 32 * i;
-        b_ok[i] = c < p.Cin;
-        b_ptr[i] = p.wt + (size_t)(b_ok[i] ? c : 0) * Kd + lcol;
-    }
+    const WeightRows<B_LD> b(p.wt, n0, lrow, lcol, p.Cin, (size_t)p.taps * p.Cp);
 
     float4 ra[A_LD], rb[B_LD];
     auto load_tile = [&](int kt) {
@@ -180,13 +164,9 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
             const float4 v = *reinterpret_cast<const float4 *>(p.g + (size_t)pix * p.gcs + p.gco + c0 + lcol);
             ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) {
-            const float4 v = *reinterpret_cast<const float4 *>(b_ptr[i] + (size_t)kt * BK);
-            rb[i] = b_ok[i] ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        b.load(kt, rb);
     };
-    auto store_tile = [&](int buf) {
+    auto store_tile = [&](int buf) {      // conv_mfma_kernel's store
         float *sa = smem[buf];
         float *sb = smem[buf] + BM * LDS_ROW;
 #pragma unroll
@@ -197,17 +177,13 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
             *reinterpret_cast<float4 *>(sb + (lrow + 32 * i) * LDS_ROW + lcol) = rb[i];
     };
 
-    const int wave = t >> 6, lane = t & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lg = lane >> 5;
+    const WaveGeom g(t);
     floatx16 acc[MR][NR];
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NR; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
+    // Own copies of the LDS store, of ktile_pipeline and of the for_each_c walk (conv_tile_4w.h), kept after measurement: with for_each_c
+    // the 24-channel RPN head (one K tile, all epilogue) is 1.4 % slower, and of the compositions without it this one is the
+    // one whose every layer stays inside the run-to-run spread of the kernel as it was (profiles/conv_tile_core_ab.txt).
     const int nkt = p.d_nkt;
     load_tile(0);
     store_tile(0);
@@ -216,40 +192,21 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
         const int buf = kt & 1;
         const bool more = kt + 1 < nkt;
         if (more) load_tile(kt + 1);
-        const float *sa = smem[buf] + (wm * 32 * MR + li) * LDS_ROW + lg * 4;
-        const float *sb = smem[buf] + BM * LDS_ROW + (wn * 32 * NR + li) * LDS_ROW + lg * 4;
-#pragma unroll
-        for (int kk = 0; kk < BK / 8; ++kk) {
-            float4 fa[MR], fb[NR];
-#pragma unroll
-            for (int i = 0; i < MR; ++i) fa[i] = *reinterpret_cast<const float4 *>(sa + i * 32 * LDS_ROW + kk * 8);
-#pragma unroll
-            for (int j = 0; j < NR; ++j) fb[j] = *reinterpret_cast<const float4 *>(sb + j * 32 * LDS_ROW + kk * 8);
-#pragma unroll
-            for (int i = 0; i < MR; ++i)
-#pragma unroll
-                for (int j = 0; j < NR; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
-                }
-        }
+        mfma_ktile_f32(smem[buf], g, acc);
         if (more) store_tile(buf ^ 1);
         __syncthreads();
     }
 
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).  Every (row, col) of the tile
-    // inside the tensor is stored, zeros included: dx needs no fill.
+    // every (row, col) of the tile inside the tensor is stored, zeros included: dx needs no fill
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
-            const int col = n0 + (wn * NR + j) * 32 + li;
+            const int col = c_col<NR>(g, n0, j);
             if (col >= p.Cin) continue;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = m0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
+                const int row = c_row<MR>(g, m0, i, e);
                 if (row >= p.Min) continue;
                 p.dx[(size_t)row * p.xcs + col] = acc[i][j][e];
             }
@@ -319,29 +276,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const BwdArgs p)
         for (int i = 0; i < B_LD; ++i) *reinterpret_cast<float4 *>(sb + (b_r + B_RS * i) * BN + b_c) = rb[i];
     };
 
-    const int wave = t >> 6, lane = t & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lg = lane >> 5;
+    const WaveGeom g(t);
     floatx16 acc[MR][NR];
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NR; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    if (kt_begin < kt_end) {
-        load_tile(kt_begin);
-        store_tile(0);
-    }
-    __syncthreads();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int buf = (kt - kt_begin) & 1;
-        const bool more = kt + 1 < kt_end;
-        if (more) load_tile(kt + 1);
+    zero_acc(acc);
+    ktile_pipeline(kt_begin, kt_end, load_tile, store_tile, [&](int buf) {
         // lane (li, lg) of MFMA step ks holds A[n = li][pixel 2 ks + lg] and B[pixel 2 ks + lg][column li]: ascending pixel order
-        const float *sa = smem[buf] + lg * BM + wm * 32 * MR + li;
-        const float *sb = smem[buf] + BK * BM + lg * BN + wn * 32 * NR + li;
+        const float *sa = smem[buf] + g.lg * BM + g.wm * 32 * MR + g.li;
+        const float *sb = smem[buf] + BK * BM + g.lg * BN + g.wn * 32 * NR + g.li;
 #pragma unroll
         for (int ks = 0; ks < BK / 2; ++ks) {
             float fa[MR], fb[NR];
@@ -354,26 +295,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const BwdArgs p)
 #pragma unroll
                 for (int j = 0; j < NR; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
         }
-        if (more) store_tile(buf ^ 1);
-        __syncthreads();
-    }
+    });
 
-    const bool split = gridDim.y > 1;
-    float *out = split ? p.partial + (size_t)blockIdx.y * p.Cout * p.Kw : p.dw;
-#pragma unroll
-    for (int i = 0; i < MR; ++i) {
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int col = j0 + (wn * NR + j) * 32 + li;
-            if (col >= p.Kw) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = n0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
-                if (row >= p.Cout) continue;
-                out[(size_t)row * p.Kw + col] = acc[i][j][e];
-            }
-        }
-    }
+    float *out = gridDim.y > 1 ? p.partial + (size_t)blockIdx.y * p.Cout * p.Kw : p.dw;
+    for_each_c(acc, g, n0, j0, p.Cout, p.Kw, [&](int row, int col, float v) { out[(size_t)row * p.Kw + col] = v; });
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const BwdArgs p, int splits)
@@ -430,19 +355,8 @@ static int bwd_prepare(const srcnn_conv_bwd_desc *d, BwdArgs &a, BwdPlan &pl)
               (reinterpret_cast<uintptr_t>(d->dy) & 15) != 0;
     pl.nq = cdiv(a.M, 256);
 
-    // dgrad tile: the forward's rule (conv_mfma.hip make_plan) -- the largest tile that still gives two workgroups per CU
-    pl.d_mr = pl.d_nr = 1;
-    {
-        static const int cand[4][2] = {{2, 2}, {2, 1}, {1, 2}, {1, 1}};
-        for (auto &c : cand) {
-            if (c[1] == 2 && a.Cin <= 64) continue;
-            if ((long)cdiv(a.Min, 64 * c[0]) * cdiv(a.Cin, 64 * c[1]) >= 512) {
-                pl.d_mr = c[0];
-                pl.d_nr = c[1];
-                break;
-            }
-        }
-    }
+    // dgrad tile: the forward's rule -- the largest tile that still gives two workgroups per CU
+    choose_tile_4w(a.Min, a.Cin, &pl.d_mr, &pl.d_nr);
     // wgrad tile: M x N is small and K long, so the tile is as large as the matrix allows and split-K fills the chip
     pl.w_mr = a.Cout > 64 ? 2 : 1;
     pl.w_nr = a.Kw > 64 ? 2 : 1;
@@ -482,18 +396,6 @@ static int bwd_prepare(const srcnn_conv_bwd_desc *d, BwdArgs &a, BwdPlan &pl)
     if (d->dw && pl.splits > 1) pl.off_part = take((size_t)pl.splits * a.Cout * a.Kw);
     pl.bytes = off > 256 ? off : 256;
     return SRCNN_OK;
-}
-
-template <int MR, int NR>
-static void launch_dgrad(const BwdArgs &a, hipStream_t st)
-{
-    SRCNN_LAUNCH((conv_dgrad_kernel<MR, NR>), dim3(a.d_mtiles * a.d_ntiles), dim3(256), 0, st, a);
-}
-
-template <int MR, int NR>
-static void launch_wgrad(const BwdArgs &a, int splits, hipStream_t st)
-{
-    SRCNN_LAUNCH((conv_wgrad_kernel<MR, NR>), dim3(a.w_mtiles * a.w_ntiles, splits), dim3(256), 0, st, a);
 }
 
 }  // namespace srcnn
@@ -538,16 +440,14 @@ int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t 
     }
     if (d->dx) {
         SRCNN_LAUNCH(bwd_weight_relayout, dim3(a.Cin / BK, a.Cp / BK, a.taps), dim3(32, 8), 0, st, a);
-        if (pl.d_mr == 2 && pl.d_nr == 2) launch_dgrad<2, 2>(a, st);
-        else if (pl.d_mr == 2) launch_dgrad<2, 1>(a, st);
-        else if (pl.d_nr == 2) launch_dgrad<1, 2>(a, st);
-        else launch_dgrad<1, 1>(a, st);
+        dispatch_tile_4w(pl.d_mr, pl.d_nr, [&](auto mr, auto nr) {
+            SRCNN_LAUNCH((conv_dgrad_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.d_mtiles * a.d_ntiles), dim3(256), 0, st, a);
+        });
     }
     if (d->dw) {
-        if (pl.w_mr == 2 && pl.w_nr == 2) launch_wgrad<2, 2>(a, pl.splits, st);
-        else if (pl.w_mr == 2) launch_wgrad<2, 1>(a, pl.splits, st);
-        else if (pl.w_nr == 2) launch_wgrad<1, 2>(a, pl.splits, st);
-        else launch_wgrad<1, 1>(a, pl.splits, st);
+        dispatch_tile_4w(pl.w_mr, pl.w_nr, [&](auto mr, auto nr) {
+            SRCNN_LAUNCH((conv_wgrad_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.w_mtiles * a.w_ntiles, pl.splits), dim3(256), 0, st, a);
+        });
         if (pl.splits > 1) {
             const size_t total = (size_t)a.Cout * a.Kw;
             SRCNN_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)min((size_t)2048, (total + 255) / 256)), dim3(256), 0, st, a, pl.splits);

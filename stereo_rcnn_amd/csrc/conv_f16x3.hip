@@ -12,14 +12,15 @@
 // activations stay fp32 in HBM and are split while they are staged into LDS, so every
 // non-conv kernel (ROIAlign, NMS, decode ...) is untouched and still bit-exact.
 //
-// Same structure as conv_mfma.hip (implicit GEMM, NHWC, K tile = 32 channels of one tap,
-// register prefetch, double-buffered LDS, XCD-aware tile map, split-K, fused epilogue); what
-// changes: LDS holds four f16 panels (A_hi, A_lo, B_hi, B_lo) of 64-byte rows whose 16-byte
+// Same structure as the fp32 engine, built from the same pieces (conv_tile_4w.h: implicit GEMM,
+// NHWC, K tile = 32 channels of one tap, register prefetch, double-buffered LDS, XCD-aware tile
+// map, split-K, fused epilogue); what changes:
+// LDS holds four f16 panels (A_hi, A_lo, B_hi, B_lo) of 64-byte rows whose 16-byte
 // chunks are XOR-swizzled with (row>>2)&3 (conflict-free ds_read_b128 / ds_write without padding,
 // so two 128x128 workgroups fit one CU's 160 KB), one ds_read_b128 = the 8-half operand of one
 // MFMA, 3 MFMAs per operand pair issued round-robin over independent accumulators (small tiles
 // keep the cross terms in their own accumulators so no MFMA waits on its predecessor).
-#include "conv_common.h"
+#include "conv_tile_4w.h"
 
 namespace srcnn {
 
@@ -38,11 +39,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
     __shared__ __attribute__((aligned(16))) _Float16 smem[2][2 * PANEL_A + 2 * PANEL_B];
 
     const int t = threadIdx.x;
-    const int nblk = p.mtiles * p.ntiles;
-    const int bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    const int logical = xcd_logical_tile(blockIdx.x, p.mtiles * p.ntiles);
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int kt_begin = blockIdx.y * p.kt_per_split;
@@ -50,25 +47,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
 
     // ---- A staging geometry (fp32 rows of 32 floats: 8 lanes x float4)
     const int lrow = t >> 3, lcol = (t & 7) * 4;
-    int a_ih0[A_LD], a_iw0[A_LD], a_pix[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        if (m < p.M) {
-            const int ohw = p.OH * p.OW;
-            const int b = m / ohw;
-            const int rem = m - b * ohw;
-            const int oh = rem / p.OW;
-            const int ow = rem - oh * p.OW;
-            a_ih0[i] = oh * p.stride - p.pad;
-            a_iw0[i] = ow * p.stride - p.pad;
-            a_pix[i] = (b * p.H + a_ih0[i]) * p.W + a_iw0[i];
-        } else {
-            a_ih0[i] = -(1 << 28);
-            a_iw0[i] = 0;
-            a_pix[i] = 0;
-        }
-    }
+    const OutPixelGather<A_LD> a(m0, lrow, p);
     // ---- B staging geometry (f16 rows of 32 halves: 4 lanes x 16 B), two panels (hi, lo)
     const int brow = t >> 2, bcol = (t & 3) * 8;
     const _Float16 *bh_ptr[B_LD], *bl_ptr[B_LD];
@@ -103,13 +82,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
             if (++ld_kw == p.KW) { ld_kw = 0; ++ld_kh; }
         }
 #pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
-            const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            const int pix = ok ? a_pix[i] + kh * p.W + kw : 0;
-            const float4 v = *reinterpret_cast<const float4 *>(p.x + (size_t)pix * p.xcs + c0 + lcol);
-            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int i = 0; i < A_LD; ++i) ra[i] = a.load(i, kh, kw, c0 + lcol);
 #pragma unroll
         for (int i = 0; i < B_LD; ++i) {
             const uint4 vh = *reinterpret_cast<const uint4 *>(bh_ptr[i] + (size_t)kt * BK);
@@ -142,39 +115,22 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
         }
     };
 
-    const int wave = t >> 6, lane = t & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lg = lane >> 5;
-    const int r_sw = (lg ^ ((li >> 2) & 3)) << 3;     // chunk kk*2+lg swizzled; kk=1 flips bit 4 (halves)
+    const WaveGeom g(t);
+    const int r_sw = (g.lg ^ ((g.li >> 2) & 3)) << 3;     // chunk kk*2+lg swizzled; kk=1 flips bit 4 (halves)
     // XACC: small tiles keep the two cross terms in their own accumulators -> every MFMA in the
     // round-robin below targets a different accumulator than its predecessor.
     constexpr bool XACC = (MR * NR <= 2);
     constexpr int NX = XACC ? (MR * NR == 1 ? 2 : 1) : 0;
     floatx16 acc[MR][NR];
     floatx16 accx[NX > 0 ? NX : 1][MR][NR];
+    zero_acc(acc);
 #pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NR; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                acc[i][j][e] = 0.f;
-#pragma unroll
-                for (int x = 0; x < (NX > 0 ? NX : 1); ++x) accx[x][i][j][e] = 0.f;
-            }
+    for (int x = 0; x < (NX > 0 ? NX : 1); ++x) zero_acc(accx[x]);
 
-    if (kt_begin < kt_end) {
-        load_tile(kt_begin);
-        store_tile(0);
-    }
-    __syncthreads();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int buf = (kt - kt_begin) & 1;
-        const bool more = kt + 1 < kt_end;
-        if (more) load_tile(kt + 1);
-        const _Float16 *sah = smem[buf] + (wm * 32 * MR + li) * HROW + r_sw;
+    ktile_pipeline(kt_begin, kt_end, load_tile, store_tile, [&](int buf) {
+        const _Float16 *sah = smem[buf] + (g.wm * 32 * MR + g.li) * HROW + r_sw;
         const _Float16 *sal = sah + PANEL_A;
-        const _Float16 *sbh = smem[buf] + 2 * PANEL_A + (wn * 32 * NR + li) * HROW + r_sw;
+        const _Float16 *sbh = smem[buf] + 2 * PANEL_A + (g.wn * 32 * NR + g.li) * HROW + r_sw;
         const _Float16 *sbl = sbh + PANEL_B;
 #pragma unroll
         for (int kk = 0; kk < BK / 16; ++kk) {
@@ -210,9 +166,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
                 for (int j = 0; j < NR; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
         }
-        if (more) store_tile(buf ^ 1);
-        __syncthreads();
-    }
+    });
     if (NX > 0) {
 #pragma unroll
         for (int i = 0; i < MR; ++i)
@@ -226,57 +180,14 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs p)
                 }
     }
 
-    // ---- epilogue (identical to the fp32 engine apart from the power-of-two rescale)
-    const bool split = gridDim.y > 1;
-    const float os = p.out_scale;
-#pragma unroll
-    for (int i = 0; i < MR; ++i) {
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int col = n0 + (wn * NR + j) * 32 + li;
-            if (col >= p.Cout) continue;
-            const float bv = (!split && p.bias) ? p.bias[p.mode == 1 ? col % (p.Cout >> 2) : col] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = m0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
-                if (row >= p.M) continue;
-                float v = acc[i][j][e] * os;
-                if (split) {
-                    p.partial[((size_t)blockIdx.y * p.M + row) * p.Cout + col] = v;
-                    continue;
-                }
-                v += bv;
-                if (p.mode == 0) {
-                    if (p.res) v += p.res[(size_t)row * p.rcs + col];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    p.y[(size_t)row * p.ycs + p.yco + col] = v;
-                } else {
-                    const int cq = p.Cout >> 2;
-                    const int ij = col / cq, co = col - ij * cq;
-                    const int ohw = p.OH * p.OW;
-                    const int b = row / ohw, rem = row - b * ohw;
-                    const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                    const size_t opix = ((size_t)b * 2 * p.OH + 2 * oh + (ij >> 1)) * (2 * p.OW) + 2 * ow + (ij & 1);
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    p.y[opix * p.ycs + p.yco + co] = v;
-                }
-            }
-        }
-    }
-}
-
-template <int MR, int NR>
-static void launch(const ConvArgs &a, int splits, hipStream_t st)
-{
-    SRCNN_LAUNCH((conv_f16x3_kernel<MR, NR>), dim3(a.mtiles * a.ntiles, splits), dim3(256), 0, st, a);
+    conv_epilogue<true>(p, acc, g, m0, n0);   // the fp32 engine's epilogue on the sums rescaled by the power of two
 }
 
 void launch_conv_f16x3(const ConvArgs &a, const Plan &pl, hipStream_t st)
 {
-    if (pl.mr == 2 && pl.nr == 2) launch<2, 2>(a, pl.splits, st);
-    else if (pl.mr == 2 && pl.nr == 1) launch<2, 1>(a, pl.splits, st);
-    else if (pl.mr == 1 && pl.nr == 2) launch<1, 2>(a, pl.splits, st);
-    else launch<1, 1>(a, pl.splits, st);
+    dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
+        SRCNN_LAUNCH((conv_f16x3_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.mtiles * a.ntiles, pl.splits), dim3(256), 0, st, a);
+    });
 }
 
 }  // namespace srcnn

@@ -2,30 +2,15 @@
 //
 // Replaces the cuDNN convolutions behind nn.Conv2d / nn.ConvTranspose2d / nn.Linear on the
 // reference's hot path (stereo_rcnn/resnet.py:66-146,243-286; rpn/stereo_rpn.py:32-40).
+// conv_tile_4w.h states the design and holds the workgroup's shared pieces; this file has the exact-fp32
+// kernel, the split-K reduction, the launch plan and the C entry points of every conv engine.
 //
-//   y[m, n] = act( sum_k A[m, k] * W[n, k] + bias[n] + residual[m, n] )
-//   m = (b, oh, ow)   k = (kh, kw, c)   n = cout          NHWC activations, W = [Cout][KH][KW][Cin]
-//
-// Design (MI355X-first, not a cuDNN/CUTLASS shape):
-//   * v_mfma_f32_32x32x2_f32: exact fp32 (bitwise an fmaf chain), 157 TF peak.  It is paced at
-//     64 cycles/instruction, so LDS/HBM pressure per flop is 16x lower than a bf16 GEMM: a 2x2
-//     wave grid with (32*MR)x(32*NR) wave tiles saturates the pipe without deep pipelining.
-//   * K order inside a 32-wide K tile is permuted so that ONE ds_read_b128 feeds FOUR MFMAs:
-//     lane (i, g) reads k = kk*8 + g*4 .. +3 of row i; MFMA s pairs k=kk*8+s (g=0) with
-//     k=kk*8+4+s (g=1) on both operands.  The sum over k is order-independent in exact
-//     arithmetic; in fp32 it is one fixed, deterministic order.
-//   * LDS rows are 32 floats + 4 pad (144 B): the 16-lane groups of ds_read_b128 then touch 16
-//     distinct 4-bank slots -> conflict-free; ds_write_b128 writes one row per 8 lanes.
-//   * im2col is never materialised: a K tile is 32 contiguous channels of one (kh, kw) tap,
-//     i.e. one 128-B run per output pixel, fetched as 8 lanes x 16 B (coalesced), zero-filled
-//     outside the image.  Global->register prefetch of tile t+1 overlaps the MFMAs of tile t;
-//     LDS is double-buffered -> one barrier per K tile.
-//   * 256 CUs / 8 XCDs: tile ids are remapped so that consecutive logical tiles (which share the
-//     activation rows) run on the same XCD and hit its L2; small-M layers use split-K so that
-//     the grid still covers the chip (partials in the caller's workspace, deterministic reduce).
-//   * epilogue fuses folded-BN bias, residual add, ReLU, channel-offset writes (concat in place)
-//     and the ConvTranspose2d(2,2) pixel scatter.
-#include "conv_common.h"
+// conv_mfma_kernel takes the tile id, wave geometry, MFMA K tile and epilogue from conv_tile_4w.h and KEEPS ITS OWN
+// COPY of three pieces: the A / B gather (OutPixelGather, WeightRows), the register -> LDS store (the same text is in
+// conv_dgrad_kernel) and the K loop (ktile_pipeline).  With any one of them shared the 128x128 tile measured 0.6 - 2.0 %
+// slower than before on the 3x3 256-channel layers (profiles/conv_tile_core_ab.txt), with the same resources and, for
+// the store, the same instruction stream but for register numbers.  A change to one of these pieces is made here too.
+#include "conv_tile_4w.h"
 #include <cstdlib>
 
 namespace srcnn {
@@ -38,18 +23,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs p)
     __shared__ __attribute__((aligned(16))) float smem[2][(BM + BN) * LDS_ROW];
 
     const int t = threadIdx.x;
-    // ---- XCD-aware tile mapping (bijective; blocks b -> XCD b%8)
-    const int nblk = p.mtiles * p.ntiles;
-    const int bid = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    const int logical = xcd_logical_tile(blockIdx.x, p.mtiles * p.ntiles);
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int kt_begin = blockIdx.y * p.kt_per_split;
     const int kt_end = min(p.nkt, kt_begin + p.kt_per_split);
 
-    // ---- per-thread staging geometry
+    // ---- per-thread staging geometry (own copy of OutPixelGather / WeightRows, see the top of the file)
     const int lrow = t >> 3;          // 0..31
     const int lcol = (t & 7) * 4;     // float offset inside the 32-float run
     int a_ih0[A_LD], a_iw0[A_LD], a_pix[A_LD];
@@ -112,17 +92,11 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs p)
     };
 
     // ---- wave geometry
-    const int wave = t >> 6, lane = t & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lg = lane >> 5;
+    const WaveGeom g(t);
     floatx16 acc[MR][NR];
-#pragma unroll
-    for (int i = 0; i < MR; ++i)
-#pragma unroll
-        for (int j = 0; j < NR; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
+    // own copy of ktile_pipeline
     if (kt_begin < kt_end) {
         load_tile(kt_begin);
         store_tile(0);
@@ -132,65 +106,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs p)
         const int buf = (kt - kt_begin) & 1;
         const bool more = kt + 1 < kt_end;
         if (more) load_tile(kt + 1);
-        const float *sa = smem[buf] + (wm * 32 * MR + li) * LDS_ROW + lg * 4;
-        const float *sb = smem[buf] + BM * LDS_ROW + (wn * 32 * NR + li) * LDS_ROW + lg * 4;
-#pragma unroll
-        for (int kk = 0; kk < BK / 8; ++kk) {
-            float4 fa[MR], fb[NR];
-#pragma unroll
-            for (int i = 0; i < MR; ++i) fa[i] = *reinterpret_cast<const float4 *>(sa + i * 32 * LDS_ROW + kk * 8);
-#pragma unroll
-            for (int j = 0; j < NR; ++j) fb[j] = *reinterpret_cast<const float4 *>(sb + j * 32 * LDS_ROW + kk * 8);
-#pragma unroll
-            for (int i = 0; i < MR; ++i)
-#pragma unroll
-                for (int j = 0; j < NR; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].x, fb[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].y, fb[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].z, fb[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i].w, fb[j].w, acc[i][j], 0, 0, 0);
-                }
-        }
+        mfma_ktile_f32(smem[buf], g, acc);
         if (more) store_tile(buf ^ 1);
         __syncthreads();
     }
 
-    // ---- epilogue.  C/D layout of 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
-    const bool split = gridDim.y > 1;
-#pragma unroll
-    for (int i = 0; i < MR; ++i) {
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int col = n0 + (wn * NR + j) * 32 + li;
-            if (col >= p.Cout) continue;
-            const float bv = (!split && p.bias) ? p.bias[p.mode == 1 ? col % (p.Cout >> 2) : col] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = m0 + (wm * MR + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lg;
-                if (row >= p.M) continue;
-                float v = acc[i][j][e];
-                if (split) {
-                    p.partial[((size_t)blockIdx.y * p.M + row) * p.Cout + col] = v;
-                    continue;
-                }
-                v += bv;
-                if (p.mode == 0) {
-                    if (p.res) v += p.res[(size_t)row * p.rcs + col];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    p.y[(size_t)row * p.ycs + p.yco + col] = v;
-                } else {   // ConvTranspose2d(k=2, s=2): col = (i2*2 + j2)*Cq + co
-                    const int cq = p.Cout >> 2;
-                    const int ij = col / cq, co = col - ij * cq;
-                    const int ohw = p.OH * p.OW;
-                    const int b = row / ohw, rem = row - b * ohw;
-                    const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                    const size_t opix = ((size_t)b * 2 * p.OH + 2 * oh + (ij >> 1)) * (2 * p.OW) + 2 * ow + (ij & 1);
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    p.y[opix * p.ycs + p.yco + co] = v;
-                }
-            }
-        }
-    }
+    conv_epilogue<false>(p, acc, g, m0, n0);
 }
 
 // deterministic split-K reduction + epilogue (modes 0 and 2)
@@ -278,26 +199,11 @@ __global__ void splitk_reduce_kernel(const ConvArgs p, int splits)
     }
 }
 
-static Plan make_plan(int M, int N, int nkt, int mode, int precision)
+static Plan make_plan(int M, int N, int nkt, int mode)
 {
-    (void)precision;
-    static const int cand[4][2] = {{2, 2}, {2, 1}, {1, 2}, {1, 1}};
     Plan pl{1, 1, 1, nkt};
     const long target = 512;   // >= 2 workgroups per CU
-    bool found = false;
-    for (auto &c : cand) {
-        if (c[1] == 2 && N <= 64) continue;
-        long blocks = (long)cdiv(M, 64 * c[0]) * cdiv(N, 64 * c[1]);
-        if (blocks >= target) {
-            pl.mr = c[0];
-            pl.nr = c[1];
-            found = true;
-            break;
-        }
-    }
-    if (!found) {
-        pl.mr = 1;
-        pl.nr = 1;
+    if (!choose_tile_4w(M, N, &pl.mr, &pl.nr)) {
         long blocks = (long)cdiv(M, 64) * cdiv(N, 64);
         if (mode != 1 && blocks < 256 && nkt >= 16) {
             int s = (int)((target + blocks - 1) / blocks);
@@ -314,7 +220,7 @@ static Plan make_plan(int M, int N, int nkt, int mode, int precision)
 
 static Plan plan_for(const srcnn_conv_desc *d, const ConvArgs &a)
 {
-    Plan pl = make_plan(a.M, a.Cout, a.nkt, a.mode, d->precision);
+    Plan pl = make_plan(a.M, a.Cout, a.nkt, a.mode);
     if (a.x2 || a.up_top) {        // the K walk of a second input has no mid-K entry points: never split; the fused top-down
         pl.splits = 1;             // addition lives in the conv kernel's epilogue, not in the split-K reduction
         pl.kt_per_split = a.nkt;
@@ -471,12 +377,6 @@ int conv_fill_args(const srcnn_conv_desc *d, ConvArgs &a)
     return SRCNN_OK;
 }
 
-template <int MR, int NR>
-static void launch(const ConvArgs &a, int splits, hipStream_t st)
-{
-    SRCNN_LAUNCH((conv_mfma_kernel<MR, NR>), dim3(a.mtiles * a.ntiles, splits), dim3(256), 0, st, a);
-}
-
 }  // namespace srcnn
 
 extern "C" {
@@ -517,10 +417,10 @@ int srcnn_conv2d(const srcnn_conv_desc *d, void *workspace, size_t workspace_byt
                                      a.M, a.Cout, a.K);
     if (d->precision == 1 && a.x_fmt == 1) launch_conv_f16s(a, pl, st);
     else if (d->precision == 1) launch_conv_f16x3(a, pl, st);
-    else if (pl.mr == 2 && pl.nr == 2) launch<2, 2>(a, pl.splits, st);
-    else if (pl.mr == 2 && pl.nr == 1) launch<2, 1>(a, pl.splits, st);
-    else if (pl.mr == 1 && pl.nr == 2) launch<1, 2>(a, pl.splits, st);
-    else launch<1, 1>(a, pl.splits, st);
+    else
+        dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
+            SRCNN_LAUNCH((conv_mfma_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.mtiles * a.ntiles, pl.splits), dim3(256), 0, st, a);
+        });
     if (pl.splits > 1) {
         const size_t total = (size_t)a.M * a.Cout;
         const int blocks = (int)min((size_t)2048, (total + 255) / 256);

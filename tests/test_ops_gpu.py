@@ -233,6 +233,115 @@ def test_conv_f16s_every_plan(dev, plan, case):
         engine._TUNED, engine.AUTOTUNE = saved_tuned, saved_flag
 
 
+TILES_4W = [(1, 1), (2, 1), (1, 2), (2, 2)]          # the four instantiations of the fp32 and the fp32-input f16x3 kernel
+
+
+def _guarded_out(shape, dev, guard=256, sentinel=12345.0):
+    """A NaN-filled output inside sentinel guards (as tests/test_conv_backward_gpu.py): an element left unwritten shows as NaN, a
+    write outside the tensor changes a sentinel.  Returns (view, check); check() asserts both and returns the result on the CPU."""
+    numel = int(np.prod(shape))
+    buf = torch.full((numel + 2 * guard,), sentinel, device=dev)
+    buf[guard:guard + numel] = float('nan')
+    view = buf[guard:guard + numel].view(shape)
+
+    def check(label):
+        torch.cuda.synchronize()
+        assert bool((buf[:guard] == sentinel).all()) and bool((buf[-guard:] == sentinel).all()), '%s: stray write' % (label,)
+        got = view.cpu()
+        assert not bool(torch.isnan(got).any()), '%s: %d elements left unwritten' % (label, int(torch.isnan(got).sum()))
+        return got
+    return view, check
+
+
+CASES_4W = [
+    # B, H, W, cin, cout, k, stride, pad, relu, res, bn
+    (2, 23, 37, 96, 200, 3, 1, 1, True, True, True),      # M = 1702, N = 200: ragged for every tile, border taps; K = 27 tiles:
+                                                          # splits 3 -> slices of 9, splits 4 -> 7, 7, 7, 6 (a short last slice)
+    (1, 12, 40, 32, 64, 1, 1, 0, True, False, True),      # K = 1 tile: the prologue-only pipeline; any splits request clamps to 1
+]
+
+
+def _conv_4w_case(dev, case):
+    """Engine weights, inputs and the float64 reference (NHWC) of one CASES_4W case."""
+    from stereo_rcnn_amd import engine
+    B, H, W, cin, cout, k, stride, pad, relu, res, bn = case
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
+    b = None if bn else torch.randn(cout, generator=g)
+    bnp = None
+    if bn:
+        bnp = {'weight': torch.rand(cout, generator=g) + 0.5, 'bias': torch.randn(cout, generator=g),
+               'running_mean': torch.randn(cout, generator=g) * 0.1, 'running_var': torch.rand(cout, generator=g) + 0.5}
+    ref = F.conv2d(x.double(), w.double(), None if b is None else b.double(), stride, pad)
+    if bn:
+        ref = F.batch_norm(ref, bnp['running_mean'].double(), bnp['running_var'].double(), bnp['weight'].double(),
+                           bnp['bias'].double(), False, 0.0, 1e-5)
+    r = torch.randn(B, cout, ref.shape[2], ref.shape[3], generator=g) if res else None
+    if res:
+        ref = ref + r.double()
+    if relu:
+        ref = F.relu(ref)
+    return (engine.prep_conv(w, b, stride, pad, relu, bn=bnp, device=dev), x.to(dev).permute(0, 2, 3, 1).contiguous(),
+            r.to(dev).permute(0, 2, 3, 1).contiguous() if res else None, ref.permute(0, 2, 3, 1).contiguous())
+
+
+@pytest.fixture(scope='module')
+def conv_4w_cases(dev):
+    """Every CASES_4W case computed once for the module and released with it."""
+    return {case: _conv_4w_case(dev, case) for case in CASES_4W}
+
+
+@pytest.mark.parametrize("splits", [1, 3, 4])
+@pytest.mark.parametrize("case", CASES_4W)
+@pytest.mark.parametrize("precision", ['f32', 'f16x3'])
+def test_conv_4wave_every_tile(dev, conv_4w_cases, precision, case, splits):
+    """Forces each of the four tiles of the exact-fp32 kernel (csrc/conv_mfma.hip) and of the fp32-input f16x3 kernel
+    (csrc/conv_f16x3.hip), with and without split-K, instead of the heuristic's choice: the _conv_case tolerance against float64
+    torch on the CPU.  Per element the K order does not depend on the tile and the slice boundaries only on (K tiles, splits), so
+    at one splits value the four fp32 tiles give identical bits; of the f16x3 tiles (2,1) and (1,2) keep the cross terms in the
+    same accumulator scheme and give identical bits, (1,1) and (2,2) use other schemes and are held by the tolerance alone."""
+    from stereo_rcnn_amd import engine
+    cw, xd, rd, ref = conv_4w_cases[case]
+    B, H, W = case[:3]
+    OH, OW, cout = ref.shape[1], ref.shape[2], ref.shape[3]
+    got = {}
+    for tile in TILES_4W:
+        y, check = _guarded_out((B, OH, OW, cout), dev)
+        engine.conv2d(cw, xd, B, H, W, y, OH, OW, residual=rd, precision=precision, plan=tile + (4, 2, splits))
+        got[tile] = check((precision, tile, splits))
+        err = float((got[tile].double() - ref).abs().max())
+        assert err < 2e-5 * max(1.0, float(ref.abs().max())), (precision, tile, splits, err)
+    same = TILES_4W if precision == 'f32' else [(2, 1), (1, 2)]
+    for tile in same[1:]:
+        assert torch.equal(got[tile].view(torch.int32), got[same[0]].view(torch.int32)), (precision, tile, splits)
+
+
+@pytest.mark.parametrize("precision", ['f32', 'f16x3'])
+def test_deconv2x2_every_4wave_tile(dev, precision):
+    """ConvTranspose2d(2, 2) (mode 1, engine.prep_deconv2x2) on each of the four tiles.  Cq = 40: the GEMM's N = 160 is ragged for
+    the 128-wide tiles, and tile boundaries (64, 128) fall inside an (i, j) group of the pixel scatter.  The tolerance of
+    test_deconv2x2_vs_torch_cpu against float64 torch; the fp32 tiles give identical bits."""
+    from stereo_rcnn_amd import engine
+    g = torch.Generator().manual_seed(2)
+    M, h, w_, cin, cq = 2, 9, 11, 64, 40
+    x = torch.randn(M, cin, h, w_, generator=g)
+    w = torch.randn(cin, cq, 2, 2, generator=g) / 8
+    b = torch.randn(cq, generator=g)
+    ref = F.relu(F.conv_transpose2d(x.double(), w.double(), b.double(), 2)).permute(0, 2, 3, 1)
+    cw = engine.prep_deconv2x2(w, b, device=dev)
+    xd = x.to(dev).permute(0, 2, 3, 1).contiguous()
+    got = {}
+    for tile in TILES_4W:
+        y, check = _guarded_out((M, 2 * h, 2 * w_, cq), dev)
+        engine.conv2d(cw, xd, M, h, w_, y, h, w_, precision=precision, plan=tile + (4, 2, 1))
+        got[tile] = check((precision, tile))
+        assert float((got[tile].double() - ref).abs().max()) < 2e-5, (precision, tile)
+    if precision == 'f32':
+        for tile in TILES_4W[1:]:
+            assert torch.equal(got[tile].view(torch.int32), got[TILES_4W[0]].view(torch.int32)), tile
+
+
 @pytest.mark.parametrize("plan", [None, (1, 1, 4, 2, 1), (1, 1, 4, 4, 1), (2, 1, 4, 3, 1), (1, 2, 4, 2, 1), (2, 2, 4, 2, 1), (2, 2, 8, 4, 1),
                                   (4, 2, 8, 3, 1), (2, 2, 8, 2, 3), (4, 4, 8, 2, 1)])
 @pytest.mark.parametrize("case", [
