@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 280 = convolution backward: srcnn_conv_bwd_desc, srcnn_conv2d_backward, srcnn_conv2d_backward_workspace_bytes; 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 300 = training: optimiser step: srcnn_grad_norm (+ _workspace_bytes), srcnn_grad_scale, srcnn_sgd_step; 290 = training: remaining adjoints: srcnn_upsample_add_backward, srcnn_subsample2_backward, srcnn_pixel_shuffle2; 280 =convolution backward: srcnn_conv_bwd_desc, srcnn_conv2d_backward, srcnn_conv2d_backward_workspace_bytes; 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -759,6 +759,59 @@ SRCNN_API int srcnn_proposal_targets(const float *rois_left, const float *rois_r
                            int *labels, float *bbox_targets_left, float *bbox_targets_right, float *dim_orien_targets,
                            int *kpts_targets, float *kpts_weight, float *inside_w, float *outside_w, int *status, int *keep_inds,
                            void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+
+/* ------------------------------------------------------------------ training: optimiser step
+ * clip_gradient (lib/model/utils/net_utils.py:37-49) and torch.optim.SGD with momentum as trainval_net.py:158-168, 224-227
+ * uses it (dampening 0, no Nesterov), over a LIST of tensors per call.  The reference takes one norm per parameter, reads the
+ * total back to the host, scales every gradient in a second pass and then makes four more passes over parameters, gradients
+ * and momentum buffers; here one pass reads the gradients for the norm and one pass reads p, g, m and writes p, m, the clip
+ * coefficient staying on the device.  Nothing is read back, nothing is uploaded: the lists are HOST arrays (device pointers,
+ * element counts, per-tensor scalars) and travel in the kernels' argument blocks, at most SRCNN_OPT_TENSORS_PER_LAUNCH tensors per
+ * launch, a longer list taking several launches.  All tensors are dense float32.  An entry with numel 0 is skipped (its pointers
+ * may be NULL); every other pointer must be non-NULL and 4-byte aligned.  Tensors whose pointers are all 16-byte aligned are
+ * read and written as float4, any other one element by element, with the same arithmetic and the same summation order.
+ *
+ * CHUNKS.  Tensor i is cut into ceil(numel[i] / SRCNN_OPT_CHUNK) chunks of SRCNN_OPT_CHUNK consecutive elements (the last one
+ * shorter); the chunks of the whole list are numbered in list order, tensor 0's first.  One workgroup of 256 threads handles a
+ * chunk at a time; the grid is min(chunks of the launch, 2048) workgroups which loop over the rest, and which workgroup takes
+ * which chunk has no influence on any result.
+ *
+ * srcnn_grad_norm: out[0] = sqrt(sum over every listed element of g^2), out[1] = clip_norm / max(out[0], clip_norm) (exactly 1
+ * where the norm does not exceed clip_norm), both float32 in device memory.  DEFINED SUMMATION ORDER (no atomics; the result
+ * depends on the list and the data only, never on the grid, the device or the pointers' alignment).  Stage 1, float32: in chunk c
+ * thread t owns the local elements 4 (256 j + t) + k, j = 0..3, k = 0..3; it adds their squares (each rounded once) in ascending
+ * (j, k) order starting from 0, elements past the tensor's end adding nothing; a wavefront adds its 64 lanes by an xor butterfly
+ * (offsets 32, 16, 8, 4, 2, 1); thread 0 adds the four wavefront sums ((w0 + w1) + w2) + w3 and writes workspace[c], c the
+ * chunk's number in the whole list.  Stage 2, one workgroup, float64: thread t adds workspace[t], workspace[t + 256], .. in
+ * ascending order starting from 0, then the same butterfly and four-term sum in double; thread 0 takes the square root in
+ * double, rounds it to float32 and divides in float32.  A list without elements gives norm 0, coefficient 1.
+ * workspace: srcnn_grad_norm_workspace_bytes(n_tensors, numel_host) bytes (one float per chunk), 0 for an invalid list.
+ *
+ * srcnn_grad_scale: g *= *coef for every listed tensor (one rounding per element) -- the in-place effect of the reference's
+ * clip_gradient for callers that keep their own optimiser; srcnn_sgd_step does not need it.
+ *
+ * srcnn_sgd_step: per element, every float32 operation rounded once (no fused multiply-add), in this order
+ *     d = clipped[i] && coef ? g * *coef : g
+ *     d = weight_decay[i] != 0 ? d + weight_decay[i] * p : d
+ *     m = first_step ? d : momentum * m + d          (momentum == 0: d is used directly, m_host and its entries may be NULL)
+ *     p = p - lr[i] * m
+ * p and m are updated in place, g is only read.  first_step != 0 says that the momentum buffers are uninitialised: they are
+ * written and not read.  coef: NULL (nothing is clipped) or a device float, e.g. out + 1 of srcnn_grad_norm on the same stream.
+ * clipped_host: NULL = every tensor is clipped.  Tensors must not overlap.
+ *
+ * Errors (SRCNN_ERR_ARG / SRCNN_ERR_WORKSPACE, before any launch): a null array, n_tensors <= 0, a negative numel, more than
+ * 2^31 - 1 chunks, a NULL or misaligned p / g / m entry of a tensor with elements (m only when momentum != 0), momentum < 0 or
+ * not finite, clip_norm <= 0, a null out / coef where required, a workspace smaller than srcnn_grad_norm_workspace_bytes. */
+#define SRCNN_OPT_CHUNK 4096
+#define SRCNN_OPT_TENSORS_PER_LAUNCH 64
+SRCNN_API size_t srcnn_grad_norm_workspace_bytes(int n_tensors, const long long *numel_host);
+SRCNN_API int srcnn_grad_norm(const float *const *g_host, const long long *numel_host, int n_tensors, float clip_norm, float *out,
+                    void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_grad_scale(float *const *g_host, const long long *numel_host, int n_tensors, const float *coef,
+                     srcnn_stream_t stream);
+SRCNN_API int srcnn_sgd_step(float *const *p_host, const float *const *g_host, float *const *m_host, const long long *numel_host,
+                   const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors, float momentum,
+                   int first_step, const float *coef, srcnn_stream_t stream);
 
 /* ------------------------------------------------------------------ recorded launch programs
  * The forward is a fixed list of ~230 asynchronous launches over fixed buffers (one list per input size and buffer set).

@@ -21,6 +21,8 @@ CE_MEAN_KEPT, CE_WEIGHTED = 0, 1    # SRCNN_CE_*
 TARGETS_MAX_GT = 64             # SRCNN_TARGETS_MAX_GT
 TARGETS_MAX_ROIS = 4096         # SRCNN_TARGETS_MAX_ROIS: proposals + ground-truth boxes of one image
 TARGETS_MAX_BATCH_ROIS = 1024   # SRCNN_TARGETS_MAX_BATCH_ROIS: rois_per_image
+OPT_CHUNK = 4096                # SRCNN_OPT_CHUNK: elements of one chunk of the optimiser kernels (one norm partial each)
+OPT_TENSORS_PER_LAUNCH = 64     # SRCNN_OPT_TENSORS_PER_LAUNCH: tensors one launch of the optimiser kernels carries in its arguments
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
@@ -215,6 +217,13 @@ _SIGNATURES = {
     "srcnn_proposal_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p, ctypes.POINTER(ProposalTargetParams)] + [c_void_p] * 12
                                + [c_void_p, c_size_t, c_void_p]),
+    "srcnn_grad_norm_workspace_bytes": (c_size_t, [c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "srcnn_grad_norm": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong), c_int, c_float, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "srcnn_grad_scale": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong), c_int, c_void_p, c_void_p]),
+    "srcnn_sgd_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong),
+                               ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int, c_float, c_int, c_void_p,
+                               c_void_p]),
 }
 
 _lib = None

@@ -23,6 +23,11 @@ cfg.TRAIN = _Cfg()
 cfg.TEST = _Cfg()
 cfg.RESNET = _Cfg()
 
+cfg.TRAIN.LEARNING_RATE = 0.001                   # :22
+cfg.TRAIN.MOMENTUM = 0.9                          # :25
+cfg.TRAIN.WEIGHT_DECAY = 0.0001                   # :28
+cfg.TRAIN.DOUBLE_BIAS = False                     # :40
+cfg.TRAIN.BIAS_DECAY = False                      # :46
 cfg.TRAIN.TRUNCATED = False                       # :43
 cfg.TRAIN.SCALES = (600,)                         # :49
 cfg.TRAIN.MAX_SIZE = 2484                         # :52

@@ -5,7 +5,34 @@ nothing is read back to the host, and the sum has a defined order (include/srcnn
 """
 import torch
 
-from ... import _lib
+from ... import _lib, optim
+
+
+def clip_gradient(model, clip_norm):
+    """Reference signature and effect (net_utils.py:37-49): every gradient of the model's trainable parameters is multiplied in
+    place by clip_norm / max(total L2 norm, clip_norm).  One norm pass and one scaling pass on the device (srcnn_grad_norm,
+    srcnn_grad_scale); the coefficient is never read back.  Returns the norm as a 0-d device tensor.  Parameters without a
+    gradient are passed over (the reference would raise on them).  `optim.SGD.step(clip_norm=...)` folds the same coefficient
+    into the update and needs no call of this function."""
+    grads = [p.grad for p in model.parameters() if p.requires_grad and p.grad is not None]
+    if not grads:
+        raise ValueError("clip_gradient: the model has no gradients")
+    if not grads[0].is_cuda:
+        raise NotImplementedError
+    out = optim.grad_norm(grads, clip_norm)
+    optim.scale_grads(grads, out[1:])
+    return out[0]
+
+
+def adjust_learning_rate(optimizer, decay=0.1):
+    """net_utils.py:70-73: every group's learning rate times `decay`."""
+    for param_group in optimizer.param_groups:
+        param_group['lr'] = decay * param_group['lr']
+
+
+def save_checkpoint(state, filename):
+    """net_utils.py:76-77."""
+    torch.save(state, filename)
 
 
 def _workspace(rows, device):

@@ -23,7 +23,13 @@ multiply by mask / 0.8, mask = [torch.rand(...) >= 0.2].
 Limit: srcnn_proposal_layer ranks at most 8192 candidates before the NMS, so cfg.TRAIN.RPN_PRE_NMS_TOP_N (12000 in the
 reference's configuration) has to be set to 8192 or less for any image with more anchors than that; forward_train raises otherwise.
 
-Still missing for a trainval_net.py: the optimiser step, the data loader and clip_gradient.
+The rest of an iteration of trainval_net.py:207-227 is here too: make_optimizer builds the reference's parameter groups on
+stereo_rcnn_amd.optim.SGD, and train_step runs zero-grad, forward_train, the multi-task loss, backward() and the clipped SGD step
+(csrc/optim.hip: one norm pass over the gradients, one fused update) as one call without a further host read.  After training, an
+inference plan's prepared weights (plan.py, engine.prep_*) are copies made from the parameters as they were: rebuild the plan
+from the updated parameters before running inference.
+
+Still missing for a trainval_net.py: the data loader.
 """
 import contextlib
 
@@ -51,6 +57,46 @@ def trainable_parameters(model):
             frozen.update(name + '.' + k for k, _ in m.named_parameters(recurse=False))
     fixed = tuple('RCNN_layer%d.' % i for i in range(0, cfg.RESNET.FIXED_BLOCKS + 1))
     return {k: p for k, p in model.named_parameters() if k not in frozen and not k.startswith(fixed)}
+
+
+def make_optimizer(model, uncert, lr=None):
+    """The optimiser of trainval_net.py:153-168 on optim.SGD: one group per trainable parameter -- a name containing 'bias' gets
+    lr * (DOUBLE_BIAS + 1) and weight decay `BIAS_DECAY and WEIGHT_DECAY or 0`, every other one lr and WEIGHT_DECAY -- and a last
+    group for `uncert` (the six log-variances of the multi-task loss) with lr and no weight decay; momentum cfg.TRAIN.MOMENTUM."""
+    from . import optim
+    T = cfg.TRAIN
+    lr = T.LEARNING_RATE if lr is None else lr
+    params = []
+    for key, value in trainable_parameters(model).items():
+        if 'bias' in key:
+            params.append({'params': [value], 'lr': lr * (T.DOUBLE_BIAS + 1), 'weight_decay': T.BIAS_DECAY and T.WEIGHT_DECAY or 0})
+        else:
+            params.append({'params': [value], 'lr': lr, 'weight_decay': T.WEIGHT_DECAY})
+    params.append({'params': [uncert], 'lr': lr})
+    return optim.SGD(params, momentum=T.MOMENTUM)
+
+
+LOSS_NAMES = ('rpn_loss_cls', 'rpn_loss_bbox_left_right', 'RCNN_loss_cls', 'RCNN_loss_bbox', 'RCNN_loss_dim_orien', 'RCNN_loss_kpts')
+
+
+def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None):
+    """One iteration of trainval_net.py:207-227.  batch: forward_train's nine inputs (im_left, im_right, im_info, gt_boxes_left,
+    gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes).  Gradients are set to None, forward_train and
+    losses.multi_task_loss build the total, backward() fills the gradients, and optimizer.step clips the MODEL's gradients to
+    `clip_norm` (uncert's stays as it is, as in the reference) inside the fused update.  Returns device scalars: 'loss', the six
+    terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0]."""
+    optimizer.zero_grad(set_to_none=True)
+    for p in model.parameters():
+        p.grad = None
+    out = forward_train(model, *batch, generator=generator)
+    terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
+    total = losses.multi_task_loss(terms, uncert)
+    total.backward()
+    optimizer.step(clip_norm=clip_norm, clip_params=[p for p in model.parameters() if p.requires_grad])
+    result = {'loss': total.detach()}
+    result.update((name, t.detach()) for name, t in zip(LOSS_NAMES, terms))
+    result['grad_norm'] = optimizer.last_norm[0] if clip_norm is not None else None
+    return result
 
 
 def _bn(m):
