@@ -813,6 +813,58 @@ SRCNN_API int srcnn_sgd_step(float *const *p_host, const float *const *g_host, f
                    const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors, float momentum,
                    int first_step, const float *coef, srcnn_stream_t stream);
 
+/* ------------------------------------------------------------------ training: batch assembly
+ * The per-iteration half of the reference's data loader (lib/roi_data_layer/minibatch.py, roibatchLoader.py:72-110,
+ * lib/model/utils/blob.py), for a whole batch of at most SRCNN_LOADER_MAX_BATCH slots per launch.  The per-slot descriptions
+ * are HOST arrays and travel in the kernels' argument blocks: nothing is uploaded, nothing is read back.  Both kernels write
+ * every output element exactly once (pass uninitialised buffers) and use no atomics.
+ *
+ * srcnn_gt_batch.  `table`: the roidb packed once into device memory, SRCNN_GT_COLS float32 per object:
+ *     [0..3] left box, [4..7] right box, [8..11] merge box (x1 y1 x2 y2, unscaled), [12..14] dim w h l, [15] sin(alpha),
+ *     [16] cos(alpha) (taken on the host at packing time, as minibatch.py:68-69 takes them on every call), [17..22] kpts, [23] class.
+ * Slot b describes rows [row_begin, row_begin + n) of it, the image's float32 im_scale and its blob width im_width;
+ * keys[b * key_stride + c] is the uint32 shuffle key of the slot's row c (device memory, n <= key_stride).  Per row, float32,
+ * each operation rounded once:  box = table box * im_scale, x1 = min(x1, im_width), column 4 = class (three box sets);
+ * dim_orien = (w, h, l, sin, cos) as stored;  kpt = table kpt * im_scale, replaced by -1 where kpt < 0 or kpt > im_width - 1.
+ * Row c goes to output row rank(c) = #{d : (key[d], d) < (key[c], c)} (srcnn_proposal_targets' convention: equal keys rank
+ * by index) -- np.random.shuffle as a sort by key; only ranks < min(n, K) are kept (truncation AFTER the shuffle,
+ * roibatchLoader.py:83-107), every other output row is zero.  Outputs: gt_left / gt_right / gt_merge / gt_dim_orien (B, K, 5),
+ * gt_kpts (B, K, 6), num_boxes (B) int64 = min(n, K).  One workgroup per slot ranks its keys in LDS: n is at most
+ * SRCNN_GT_MAX_ROWS, a larger entry is refused.
+ *
+ * srcnn_preprocess_train.  Slot b: the decoded uint8 RGB left / right images (H, W, 3) (device memory, or page-locked host
+ * memory read where it is), `flipped`, and `scale` (target size / short side, double).  Writes out_left / out_right, float32
+ * (B, 3, Hmax, Wmax): per pixel RGB -> BGR, minus PIXEL_MEANS (in double, stored as float32), cv2.resize(fx = fy = scale,
+ * INTER_LINEAR) exactly as srcnn_preprocess does it, output size OH = cvRound(H * scale), OW = cvRound(W * scale); columns >=
+ * min(OW, max_size) (blob.py:59-61) and rows >= OH of a slot are zero (blob.py:20-37).  flipped != 0 (minibatch.py:116-119): the
+ * left output is the RIGHT source read mirrored (column W - 1 - x) and the right output the left source mirrored; the mirror
+ * applies to the source index, before the mean and the resize.  Every slot needs OH <= Hmax and min(OW, max_size) <= Wmax;
+ * the outputs must be 16-byte aligned (a thread stores four consecutive floats of the flat blob) and a blob has fewer than 2^31
+ * elements.
+ *
+ * Errors (SRCNN_ERR_ARG, before any launch): a null array / output / image, B outside 1..SRCNN_LOADER_MAX_BATCH, K <= 0, a
+ * negative or out-of-table row range, n > SRCNN_GT_MAX_ROWS or > key_stride, a non-positive or non-finite scale, a null table
+ * or keys when any slot has rows, a resized image larger than (Hmax, Wmax), misaligned outputs, a blob of 2^31 elements or more. */
+#define SRCNN_LOADER_MAX_BATCH 16
+#define SRCNN_GT_COLS 24
+#define SRCNN_GT_MAX_ROWS 512
+typedef struct srcnn_gt_slot {
+    int row_begin, n;            /* rows [row_begin, row_begin + n) of the table */
+    float im_scale;              /* float32(target size / short side) */
+    float im_width;              /* the image's blob width: min(OW, max_size) */
+} srcnn_gt_slot;
+typedef struct srcnn_train_image {
+    const unsigned char *left, *right;   /* decoded uint8 RGB (H, W, 3) */
+    int H, W;
+    int flipped;
+    double scale;
+} srcnn_train_image;
+SRCNN_API int srcnn_gt_batch(const float *table, int table_rows, const srcnn_gt_slot *slots_host, int B, const unsigned *keys,
+                   int key_stride, int K, float *gt_left, float *gt_right, float *gt_merge, float *gt_dim_orien, float *gt_kpts,
+                   long long *num_boxes, srcnn_stream_t stream);
+SRCNN_API int srcnn_preprocess_train(const srcnn_train_image *slots_host, int B, int Hmax, int Wmax, int max_size, float *out_left,
+                           float *out_right, srcnn_stream_t stream);
+
 /* ------------------------------------------------------------------ recorded launch programs
  * The forward is a fixed list of ~230 asynchronous launches over fixed buffers (one list per input size and buffer set).
  * Between srcnn_program_begin and srcnn_program_end every srcnn_* call made BY THE CALLING THREAD records its kernel

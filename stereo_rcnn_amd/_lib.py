@@ -23,6 +23,9 @@ TARGETS_MAX_ROIS = 4096         # SRCNN_TARGETS_MAX_ROIS: proposals + ground-tru
 TARGETS_MAX_BATCH_ROIS = 1024   # SRCNN_TARGETS_MAX_BATCH_ROIS: rois_per_image
 OPT_CHUNK = 4096                # SRCNN_OPT_CHUNK: elements of one chunk of the optimiser kernels (one norm partial each)
 OPT_TENSORS_PER_LAUNCH = 64     # SRCNN_OPT_TENSORS_PER_LAUNCH: tensors one launch of the optimiser kernels carries in its arguments
+LOADER_MAX_BATCH = 16           # SRCNN_LOADER_MAX_BATCH: batch slots one launch of the batch assembly kernels carries in its arguments
+GT_COLS = 24                    # SRCNN_GT_COLS: floats of one object row of the ground-truth table (include/srcnn_hip.h lists the columns)
+GT_MAX_ROWS = 512               # SRCNN_GT_MAX_ROWS: objects of one roidb entry srcnn_gt_batch ranks
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
@@ -89,6 +92,16 @@ class ProposalTargetParams(ctypes.Structure):
                 ("rois_per_image", c_int), ("fg_rois_per_image", c_int), ("kpts_grid", c_int),
                 ("bbox_means", c_float * 4), ("bbox_stds", c_float * 4), ("dim_means", c_float * 5), ("dim_stds", c_float * 5),
                 ("inside_weights", c_float * 4)]
+
+
+class GtSlot(ctypes.Structure):
+    """struct srcnn_gt_slot (include/srcnn_hip.h)."""
+    _fields_ = [("row_begin", c_int), ("n", c_int), ("im_scale", c_float), ("im_width", c_float)]
+
+
+class TrainImage(ctypes.Structure):
+    """struct srcnn_train_image (include/srcnn_hip.h)."""
+    _fields_ = [("left", c_void_p), ("right", c_void_p), ("H", c_int), ("W", c_int), ("flipped", c_int), ("scale", c_double)]
 
 
 _SIGNATURES = {
@@ -224,6 +237,8 @@ _SIGNATURES = {
     "srcnn_sgd_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong),
                                ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int, c_float, c_int, c_void_p,
                                c_void_p]),
+    "srcnn_gt_batch": (c_int, [c_void_p, c_int, ctypes.POINTER(GtSlot), c_int, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_void_p]),
+    "srcnn_preprocess_train": (c_int, [ctypes.POINTER(TrainImage), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

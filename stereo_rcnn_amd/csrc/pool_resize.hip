@@ -6,6 +6,7 @@
 // stereo_rcnn.py:91-108 (_upsample_add; torch-0.3 bilinear == align_corners=True),
 // stereo_rcnn.py:39,168 (MaxPool2d(1, stride=2)).
 #include "conv_common.h"
+#include "resize_tap.h"
 
 namespace srcnn {
 
@@ -165,59 +166,7 @@ __global__ void act_convert_kernel(const void *__restrict__ x, int xfmt, void *_
     }
 }
 
-// A0 (demo.py:103-129, blob.py:39-64): uint8 RGB (H, W, 3) -> float32 BGR, minus PIXEL_MEANS, resized by
-// cv2.resize(img, None, None, fx=s, fy=s, INTER_LINEAR).  The resize follows OpenCV's published float path operation by
-// operation (modules/imgproc/src/resize.cpp; restated and pinned in oracle/preprocess.py): tap position
-// (float)((d + 0.5) * (1/s) - 0.5) in double then float, cvFloor, float fraction; horizontal taps clamp AND zero the
-// fraction at the borders, vertical taps clip the two rows but keep the fraction; HResizeLinear S[sx]*a0 + S[sx+1]*a1,
-// VResizeLinear S0*b0 + S1*b1, each product and sum rounded to float32 on its own (this file is built with
-// -ffp-contract=off).  Mean subtraction happens BEFORE the resize and in double, as numpy does for float32 -= float64.
-struct ResizeTap {
-    int s0, s1;
-    float w0, w1;
-    bool copy;     // horizontal only: dx >= xmax, D = S[cols-1] * 1.f
-};
-
-__device__ __forceinline__ ResizeTap resize_tap(int d, int n_src, double step, bool horizontal)
-{
-    ResizeTap t;
-    float f = (float)(((double)d + 0.5) * step - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    t.copy = false;
-    if (horizontal) {
-        if (s < 0) { s = 0; f = 0.f; }
-        if (s >= n_src - 1) { s = n_src - 1; f = 0.f; t.copy = true; }
-        t.s0 = s;
-        t.s1 = min(s + 1, n_src - 1);
-    } else {
-        t.s0 = min(max(s, 0), n_src - 1);
-        t.s1 = min(max(s + 1, 0), n_src - 1);
-    }
-    t.w1 = f;
-    t.w0 = 1.f - f;
-    return t;
-}
-
-__device__ __forceinline__ float u8_minus_mean(unsigned char v, double mean) { return (float)((double)v - mean); }
-
-// resized BGR value of output pixel (oy, ox): bgr[0..2]
-__device__ __forceinline__ void preprocess_pixel(const unsigned char *__restrict__ img, int H, int W, int oy, int ox,
-                                                 double step, float bgr[3])
-{
-    const ResizeTap tx = resize_tap(ox, W, step, true), ty = resize_tap(oy, H, step, false);
-    const unsigned char *r0 = img + (size_t)ty.s0 * W * 3, *r1 = img + (size_t)ty.s1 * W * 3;
-    const double mean[3] = {102.9801, 115.9465, 122.7717};        // PIXEL_MEANS (config.py:170), BGR
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {          // output channel c = B,G,R  <-  input channel 2-c
-        const int ic = 2 - c;
-        const float a = u8_minus_mean(r0[tx.s0 * 3 + ic], mean[c]), b = u8_minus_mean(r0[tx.s1 * 3 + ic], mean[c]);
-        const float cc = u8_minus_mean(r1[tx.s0 * 3 + ic], mean[c]), d = u8_minus_mean(r1[tx.s1 * 3 + ic], mean[c]);
-        const float h0 = tx.copy ? a : a * tx.w0 + b * tx.w1;
-        const float h1 = tx.copy ? cc : cc * tx.w0 + d * tx.w1;
-        bgr[c] = h0 * ty.w0 + h1 * ty.w1;
-    }
-}
+// A0 (demo.py:103-129, blob.py:39-64): resize_tap / preprocess_pixel live in resize_tap.h, shared with loader.hip.
 
 // One thread per PAIR of padded stem-input pixels (the 32-byte group of the packed layouts, see stem_pack*_kernel):
 // computes the (up to) two resized pixels once and writes them wherever asked -- the planar float32 network input

@@ -744,6 +744,56 @@ def preprocess(img_rgb_u8, target_short=600, max_size=2484, packed=None, packed_
     return out, scale
 
 
+def preprocess_train(pairs, flipped, scales, max_size=2484, device=None, out=None):
+    """The image blobs of a training batch in one launch (minibatch._get_image_blob + blob.im_list_to_blob; csrc/loader.hip).
+    pairs: per slot (left, right) uint8 RGB (H, W, 3) tensors -- on the device, or page-locked host tensors the kernel reads where
+    they are (then give `device`); flipped: per slot; scales: per slot the Python float target / short side.  Returns
+    (im_left, im_right) float32 (B, 3, Hmax, Wmax), zero-padded to the batch maximum, and the per-slot (OH, OWc): each image's
+    own resized height and its width after the max_size crop.  Bit-equal to oracle/preprocess.py per image.  `out`: the two
+    (B, 3, Hmax, Wmax) tensors to write into (every element is written)."""
+    B = len(pairs)
+    assert B == len(flipped) == len(scales) and 0 < B <= _lib.LOADER_MAX_BATCH
+    slots, sizes = (_lib.TrainImage * B)(), []
+    for b, ((l, r), f, s) in enumerate(zip(pairs, flipped, scales)):
+        assert l.dtype == torch.uint8 and l.dim() == 3 and l.shape[2] == 3 and tuple(l.shape) == tuple(r.shape)
+        assert l.is_contiguous() and r.is_contiguous() and (l.is_cuda or l.is_pinned()) and (r.is_cuda or r.is_pinned())
+        if l.is_cuda:
+            device = l.device
+        H, W = int(l.shape[0]), int(l.shape[1])
+        slots[b] = _lib.TrainImage(l.data_ptr(), r.data_ptr(), H, W, int(bool(f)), float(s))
+        sizes.append((int(round(H * float(s))), min(int(round(W * float(s))), int(max_size))))
+    assert device is not None, "page-locked host images: say which device reads them"
+    Hmax, Wmax = max(s[0] for s in sizes), max(s[1] for s in sizes)
+    if out is None:
+        out = (torch.empty((B, 3, Hmax, Wmax), dtype=torch.float32, device=device),      # the kernel writes every element
+               torch.empty((B, 3, Hmax, Wmax), dtype=torch.float32, device=device))
+    out_l, out_r = out
+    assert all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, 3, Hmax, Wmax) for t in out)
+    _lib.check(_lib.lib().srcnn_preprocess_train(slots, B, Hmax, Wmax, int(max_size), out_l.data_ptr(), out_r.data_ptr(), _lib.stream()),
+               "srcnn_preprocess_train")
+    return out_l, out_r, sizes
+
+
+def gt_batch(table, slots, keys, K, out=None):
+    """The ground-truth tensors of a training batch in one launch (minibatch.py:47-82, roibatchLoader.py:72-110; csrc/loader.hip).
+    table: (rows, GT_COLS) float32 device tensor (data.pack_gt_table); slots: per batch slot (row_begin, n, im_scale, im_width);
+    keys: (B, key_stride) device tensor of uint32 shuffle keys, the words held in a 4-byte integer dtype (data.keys_to_words).
+    Returns [gt_boxes_left, gt_boxes_right, gt_boxes_merge (B, K, 5), gt_dim_orien (B, K, 5), gt_kpts (B, K, 6), num_boxes (B) int64];
+    `out`: the same six tensors to write into (every element is written)."""
+    B = len(slots)
+    assert 0 < B <= _lib.LOADER_MAX_BATCH
+    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == _lib.GT_COLS
+    assert keys.is_cuda and keys.is_contiguous() and keys.element_size() == 4 and keys.dim() == 2 and keys.shape[0] == B
+    dev = table.device
+    if out is None:
+        out = [torch.empty((B, K, c), dtype=torch.float32, device=dev) for c in (5, 5, 5, 5, 6)]
+        out.append(torch.empty((B,), dtype=torch.int64, device=dev))
+    arr = (_lib.GtSlot * B)(*[_lib.GtSlot(int(s[0]), int(s[1]), float(s[2]), float(s[3])) for s in slots])
+    _lib.check(_lib.lib().srcnn_gt_batch(table.data_ptr(), int(table.shape[0]), arr, B, keys.data_ptr(), int(keys.shape[1]), int(K),
+                                         *[t.data_ptr() for t in out], _lib.stream()), "srcnn_gt_batch")
+    return out
+
+
 def stem_pack(im_nchw, out, batch_offset=0, out_fmt=0):
     """NCHW image -> zero-bordered NHWC4 for the stem conv; out_fmt FMT_SPLIT16 writes the same buffer in the layout the
     DMA conv engine reads (pass x_fmt=FMT_SPLIT16 to conv2d)."""

@@ -1,7 +1,7 @@
 """Host-side KITTI helpers on the inference path - reference lib/model/utils/kitti_utils.py:
-`read_obj_calibration` (:97-159), `infer_boundary` (:398-437), `write_detection_results` (:440-460).
-Pure host I/O / tiny numpy loops in the reference as well; label/lidar/visualisation helpers of that
-file are training / viz code and out of scope."""
+`read_obj_calibration` (:97-159), `infer_boundary` (:398-437), `write_detection_results` (:440-460) -- and, for the training
+data loader (stereo_rcnn_amd/datasets/kitti.py), `Box2d` / `KittiObject` (:13-31), `E2R` (:57-76) and `read_obj_data` (:161-265).
+Pure host I/O / tiny numpy loops in the reference as well; lidar/visualisation helpers of that file are out of scope."""
 import math
 import os
 
@@ -88,3 +88,122 @@ def write_detection_results(result_dir, file_number, calib, box_left, pos, dim, 
     os.makedirs(result_dir, exist_ok=True)
     with open(os.path.join(result_dir, file_number + '.txt'), 'a') as fh:
         fh.write(line)
+
+
+class Box2d(object):
+    """kitti_utils.py:13-18."""
+
+    def __init__(self):
+        self.box = []               # left, top, right, bottom in the image
+        self.keypoints = []         # u coordinates of the 4 keypoints, -1 = invisible
+        self.visible_left = 0       # leftmost column not occluded by another object
+        self.visible_right = 0      # rightmost one
+
+
+class KittiObject(object):
+    """kitti_utils.py:20-31."""
+
+    def __init__(self):
+        self.cls = ''               # Car, Van, Truck, Misc
+        self.truncate = 0           # float 0 (not truncated) .. 1
+        self.occlusion = 0          # integer 0..3
+        self.alpha = 0              # viewpoint angle
+        self.boxes = (Box2d(), Box2d(), Box2d())      # left, right, merge
+        self.pos = []               # x, y, z in the cam2 frame
+        self.dim = []               # width (x), height (y), length (z)
+        self.orientation = 0
+        self.R = []                 # rotation matrix in the cam2 frame
+
+
+def E2R(Ry, Rx, Rz):
+    """Euler angles to the rotation matrix, R_pitch . R_yaw (kitti_utils.py:57-76; Rz is unused there too)."""
+    R_yaw = np.array([[math.cos(Ry), 0, math.sin(Ry)],
+                      [0, 1, 0],
+                      [-math.sin(Ry), 0, math.cos(Ry)]])
+    R_pitch = np.array([[1, 0, 0],
+                        [0, math.cos(Rx), -math.sin(Rx)],
+                        [0, math.sin(Rx), math.cos(Rx)]])
+    return R_pitch.dot(R_yaw)
+
+
+def _space2image(P, pts3):
+    n = P.dot(pts3)                 # kitti_utils.py:78-90
+    return np.array([n[0] / n[2], n[1] / n[2]])
+
+
+USED_CLASSES = ('Car', 'Van', 'Truck', 'Misc')
+
+
+def read_obj_data(label_path, calib=None, im_shape=None):
+    """The labelled objects of one KITTI frame (kitti_utils.py:161-265), float64 in the reference's order of operations: the four
+    used classes; position moved from the cam0 to the cam2 frame; orientation + pi/2 and E2R; the eight box corners projected
+    through p2_2 (left) / p2_3 (right), corners with z < 0 skipped; boxes clamped to the image; of the four bottom keypoints the
+    leftmost and the rightmost stay and the others stay only if no deeper than the centre; the merge box is the union."""
+    objects = []
+    with open(label_path, 'r') as fh:
+        lines = fh.readlines()
+    for line in lines:
+        d = line.split()
+        if d[0] not in USED_CLASSES:
+            continue
+        o = KittiObject()
+        o.cls = d[0]
+        o.truncate = float(d[1])
+        o.occlusion = int(d[2])
+        o.alpha = float(d[3])
+        o.dim = np.array([d[9], d[8], d[10]]).astype(float)                # width, height, length
+        o.pos = np.array(d[11:14]).astype(float) + calib.t_cam2_cam0
+        o.orientation = float(d[14]) + math.pi / 2
+        o.R = E2R(o.orientation, 0, 0)
+        w, h, l = o.dim[0], o.dim[1], o.dim[2]
+        corners = [o.pos + o.R.dot([-w, 0, -l]) / 2.0,
+                   o.pos + o.R.dot([-w, 0, l]) / 2.0,
+                   o.pos + o.R.dot([w, 0, l]) / 2.0,
+                   o.pos + o.R.dot([w, 0, -l]) / 2.0,
+                   o.pos + o.R.dot([-w, -2.0 * h, -l]) / 2.0,
+                   o.pos + o.R.dot([-w, -2.0 * h, l]) / 2.0,
+                   o.pos + o.R.dot([w, -2.0 * h, l]) / 2.0,
+                   o.pos + o.R.dot([w, -2.0 * h, -l]) / 2.0]
+        o.boxes[0].box = np.array([10000, 10000, 0, 0]).astype(float)
+        o.boxes[1].box = np.array([10000, 10000, 0, 0]).astype(float)
+        o.boxes[2].box = np.array([0.0, 0.0, 0.0, 0.0]).astype(float)
+        o.boxes[0].keypoints = np.array([-1.0, -1.0, -1.0, -1.0]).astype(float)
+        o.boxes[1].keypoints = np.array([-1.0, -1.0, -1.0, -1.0]).astype(float)
+        for j in range(2):
+            bx = o.boxes[j]
+            P = calib.p2_2 if j == 0 else calib.p2_3
+            for i in range(8):
+                if corners[i][2] < 0:
+                    continue
+                pt2 = _space2image(P, np.append(corners[i], [1]))
+                if i < 4:
+                    bx.keypoints[i] = pt2[0]
+                bx.box[0] = min(bx.box[0], pt2[0])
+                bx.box[1] = min(bx.box[1], pt2[1])
+                bx.box[2] = max(bx.box[2], pt2[0])
+                bx.box[3] = max(bx.box[3], pt2[1])
+            bx.box[0] = max(bx.box[0], 0)
+            bx.box[1] = max(bx.box[1], 0)
+            if im_shape is not None:
+                bx.box[2] = min(bx.box[2], im_shape[1] - 1)
+                bx.box[3] = min(bx.box[3], im_shape[0] - 1)
+            left_keypoint, right_keypoint = 5000, 0
+            left_inx, right_inx = -1, -1
+            for i in range(4):
+                if bx.keypoints[i] < left_keypoint:
+                    left_keypoint = bx.keypoints[i]
+                    left_inx = i
+                if bx.keypoints[i] > right_keypoint:
+                    right_keypoint = bx.keypoints[i]
+                    right_inx = i
+            for i in range(4):
+                if i == left_inx or i == right_inx:
+                    continue
+                if corners[i][2] > o.pos[2]:
+                    bx.keypoints[i] = -1
+        o.boxes[2].box[0] = min(o.boxes[1].box[0], o.boxes[0].box[0])
+        o.boxes[2].box[1] = min(o.boxes[1].box[1], o.boxes[0].box[1])
+        o.boxes[2].box[2] = max(o.boxes[1].box[2], o.boxes[0].box[2])
+        o.boxes[2].box[3] = max(o.boxes[1].box[3], o.boxes[0].box[3])
+        objects.append(o)
+    return objects

@@ -29,7 +29,9 @@ stereo_rcnn_amd.optim.SGD, and train_step runs zero-grad, forward_train, the mul
 inference plan's prepared weights (plan.py, engine.prep_*) are copies made from the parameters as they were: rebuild the plan
 from the updated parameters before running inference.
 
-Still missing for a trainval_net.py: the data loader.
+The data side is stereo_rcnn_amd/datasets/kitti.py (annotations -> roidb, once) and stereo_rcnn_amd/data.py (TrainLoader: PNG
+decode in worker processes, batch assembly in csrc/loader.hip), and stereo_rcnn_amd/trainval_net.py is the reference's training
+loop on these pieces.
 """
 import contextlib
 

@@ -1,0 +1,136 @@
+"""Train Stereo R-CNN on KITTI: the reference's trainval_net.py on this project's pieces.
+
+    python -m stereo_rcnn_amd.trainval_net --kitti-path data/kitti --split data/kitti/splits/train.txt [--epochs 20 --bs 1 ...]
+
+datasets.kitti.build_roidb (annotations, flipped copies, filter, ratio ranking) -> data.TrainLoader (PNG decode in worker
+processes, batch assembly in csrc/loader.hip) -> training.train_step per batch (forward_train, multi-task loss, backward, clipped
+SGD step) with training.make_optimizer's groups and the six log-variances `uncert` initialised to -1 (trainval_net.py:155-156);
+net_utils.adjust_learning_rate at the decay epochs (:189-191), net_utils.save_checkpoint at each epoch's end (:248-254: 'epoch' is
+the NEXT epoch, 'model', 'optimizer', 'uncert').  Losses are read to the host only every --disp_interval iterations; in between
+nothing waits for the device.  --resume loads model, optimiser state and uncert back and continues at the stored epoch.
+
+The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
+initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+PRE_NMS_ADVICE = ("cfg.TRAIN.RPN_PRE_NMS_TOP_N = %d: the proposal kernel ranks at most %d candidates, so on full-size images "
+                  "forward_train refuses it.  Lower it to %d (--pre_nms_top_n %d), as the README's training paragraph says.")
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description='Train the Stereo R-CNN network')
+    p.add_argument('--kitti-path', dest='kitti_path', required=True, help='KITTI object root (holds training/image_2, image_3, label_2, calib)')
+    p.add_argument('--split', required=True, help='split file: one frame id per line')
+    p.add_argument('--start_epoch', default=1, type=int)
+    p.add_argument('--epochs', dest='max_epochs', default=20, type=int)
+    p.add_argument('--save_dir', default='models_stereo')
+    p.add_argument('--nw', dest='num_workers', default=4, type=int, help='PNG decode processes (0: decode in-process)')
+    p.add_argument('--prefetch', default=2, type=int)
+    p.add_argument('--bs', dest='batch_size', default=1, type=int)
+    p.add_argument('--lr', default=None, type=float, help='default: cfg.TRAIN.LEARNING_RATE')
+    p.add_argument('--lr_decay_step', default=5, type=int, help='unit: epoch')
+    p.add_argument('--lr_decay_gamma', default=0.1, type=float)
+    p.add_argument('--disp_interval', default=100, type=int)
+    p.add_argument('--net', default=101, type=int, help='ResNet depth')
+    p.add_argument('--init', default=None, help='state dict (or checkpoint with a "model" entry) to start from')
+    p.add_argument('--resume', default=None, help='checkpoint written by an earlier run')
+    p.add_argument('--pre_nms_top_n', default=None, type=int, help='sets cfg.TRAIN.RPN_PRE_NMS_TOP_N')
+    p.add_argument('--no_flip', action='store_true', help='do not append the flipped copies (cfg.TRAIN.USE_FLIPPED)')
+    p.add_argument('--seed', default=None, type=int, help='default: cfg.RNG_SEED')
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    """Runs the loop; returns the list of checkpoint files written."""
+    args = parse_args(argv)
+    from . import data, training
+    from .datasets import kitti
+    from .model.stereo_rcnn.resnet import resnet
+    from .model.utils import net_utils
+    from .model.utils.config import cfg
+
+    if args.pre_nms_top_n is not None:
+        cfg.TRAIN.RPN_PRE_NMS_TOP_N = int(args.pre_nms_top_n)
+    limit = training.PROPOSAL_MAX_PRE_NMS
+    if cfg.TRAIN.RPN_PRE_NMS_TOP_N > limit:
+        print(PRE_NMS_ADVICE % (cfg.TRAIN.RPN_PRE_NMS_TOP_N, limit, limit, limit))
+        return []
+    if not torch.cuda.is_available():
+        raise RuntimeError("training needs a GPU")
+    dev = torch.device('cuda:0')
+    seed = int(cfg.RNG_SEED if args.seed is None else args.seed)
+
+    roidb, ratio_list, ratio_index = kitti.build_roidb(args.kitti_path, args.split, use_flipped=not args.no_flip)
+    train_size = len(roidb)
+    os.makedirs(args.save_dir, exist_ok=True)
+    log_info = open(os.path.join(args.save_dir, 'trainlog.txt'), 'a' if args.resume else 'w')
+
+    def log_string(s):
+        log_info.write(s + '\n')
+        log_info.flush()
+        print(s)
+
+    log_string('{:d} roidb entries'.format(train_size))
+    model = resnet(kitti.CLASSES, args.net, pretrained=False)
+    model.create_architecture()
+    if args.init:
+        sd = torch.load(args.init, map_location='cpu')
+        model.load_state_dict(sd['model'] if 'model' in sd else sd)
+    model.to(dev)
+    lr = cfg.TRAIN.LEARNING_RATE if args.lr is None else args.lr
+    uncert = torch.full((6,), -1.0, dtype=torch.float32, device=dev, requires_grad=True)
+    optimizer = training.make_optimizer(model, uncert, lr=lr)
+    start_epoch = args.start_epoch
+    if args.resume:
+        log_string('loading checkpoint %s' % args.resume)
+        ckpt = torch.load(args.resume, map_location=dev)
+        start_epoch = int(ckpt['epoch'])
+        model.load_state_dict(ckpt['model'])
+        optimizer.load_state_dict(ckpt['optimizer'])
+        with torch.no_grad():
+            uncert.copy_(ckpt['uncert'].to(dev))
+        lr = optimizer.param_groups[0]['lr']
+
+    gen_host = torch.Generator().manual_seed(seed)
+    gen_dev = torch.Generator(device=dev).manual_seed(seed)
+    loader = data.TrainLoader(roidb, ratio_index, args.batch_size, dev, generator=gen_host, workers=args.num_workers,
+                              prefetch=args.prefetch)
+    iters_per_epoch = int(train_size / args.batch_size)
+    written = []
+    try:
+        for epoch in range(start_epoch, args.max_epochs + 1):
+            start = time.time()
+            if epoch % (args.lr_decay_step + 1) == 0:
+                net_utils.adjust_learning_rate(optimizer, args.lr_decay_gamma)
+                lr *= args.lr_decay_gamma
+            step = -1
+            for step, batch in enumerate(loader):
+                if step >= iters_per_epoch:              # trainval_net.py:183,194: the leftover samples are not trained on
+                    break
+                res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev)
+                if args.disp_interval > 0 and step % args.disp_interval == 0:
+                    vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
+                    log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))
+                    log_string('\t\t\tuncert: ' + ', '.join('%.4f' % v for v in uncert.detach().cpu().tolist()))
+                    log_string('\t\t\trpn_cls: %.4f, rpn_box_left_right: %.4f, rcnn_cls: %.4f, rcnn_box_left_right %.4f, dim_orien %.4f, '
+                               'kpts %.4f, grad norm %.3f' % tuple([vals[k] for k in training.LOSS_NAMES] + [vals['grad_norm']]))
+            save_name = os.path.join(args.save_dir, 'stereo_rcnn_{}_{}.pth'.format(epoch, min(step, iters_per_epoch - 1)))
+            net_utils.save_checkpoint({'epoch': epoch + 1, 'model': model.state_dict(), 'optimizer': optimizer.state_dict(),
+                                       'uncert': uncert.detach().clone()}, save_name)
+            written.append(save_name)
+            log_string('save model: {}'.format(save_name))
+            log_string('time %.4f' % (time.time() - start))
+    finally:
+        loader.close()
+        log_info.close()
+    return written
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])
