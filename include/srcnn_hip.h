@@ -41,7 +41,7 @@ typedef void *srcnn_stream_t; /* hipStream_t */
 
 #define SRCNN_API __attribute__((visibility("default")))
 
-SRCNN_API int srcnn_version(void);   /* 300 = training: optimiser step: srcnn_grad_norm (+ _workspace_bytes), srcnn_grad_scale, srcnn_sgd_step; 290 = training: remaining adjoints: srcnn_upsample_add_backward, srcnn_subsample2_backward, srcnn_pixel_shuffle2; 280 =convolution backward: srcnn_conv_bwd_desc, srcnn_conv2d_backward, srcnn_conv2d_backward_workspace_bytes; 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
+SRCNN_API int srcnn_version(void);   /* 310 = result visualisation: srcnn_render_overlay, srcnn_overlay_workspace_bytes, srcnn_bev_lidar; 300 = training: optimiser step: srcnn_grad_norm (+ _workspace_bytes), srcnn_grad_scale, srcnn_sgd_step; 290 = training: remaining adjoints: srcnn_upsample_add_backward, srcnn_subsample2_backward, srcnn_pixel_shuffle2; 280 =convolution backward: srcnn_conv_bwd_desc, srcnn_conv2d_backward, srcnn_conv2d_backward_workspace_bytes; 270 = training target layers: srcnn_anchor_targets, srcnn_proposal_targets and their *_workspace_bytes; 260 = training losses: srcnn_cross_entropy, srcnn_smooth_l1, their _backward, srcnn_loss_workspace_bytes; 250 = KITTI object evaluation: srcnn_kitti_overlaps, srcnn_kitti_match (srcnn_kitti_split, srcnn_kitti_match_desc); 230 = round 5, second half: srcnn_conv_desc.up_top / up_format / up_H / up_W appended, srcnn_stem_pack_pair, srcnn_pool2x2_s1; 220 = round 5: srcnn_conv_desc.head_wf / head_rows / head_parts / head_plane appended, srcnn_rpn_score_levels / _parts, srcnn_box_head_tail, srcnn_proposal_workspace_layout; 210 = round 4: stream creation, placement probe, srcnn_conv_desc.head_* appended (older callers that zero the struct are unaffected) */
 SRCNN_API const char *srcnn_last_error(void);
 
 /* ------------------------------------------------------------------ NMS (A6)
@@ -864,6 +864,78 @@ SRCNN_API int srcnn_gt_batch(const float *table, int table_rows, const srcnn_gt_
                    long long *num_boxes, srcnn_stream_t stream);
 SRCNN_API int srcnn_preprocess_train(const srcnn_train_image *slots_host, int B, int Hmax, int Wmax, int max_size, float *out_left,
                            float *out_right, srcnn_stream_t stream);
+
+/* ------------------------------------------------------------------ result visualisation
+ * The picture the reference's demo.py:225-333 / test_net.py:231-339 show, drawn on the device from one image's detection record
+ * (see srcnn_pack_detections) with no host read of a detection: the left image over the right image with the 2-D boxes
+ * (net_utils.vis_detections), the projected 3-D wireframes on the left image (vis_3d_utils.vis_single_box_in_img) and, to the
+ * right of both, a bird's-eye view of the lidar points with the 3-D boxes (vis_lidar_in_bev, vis_box_in_bev).  Everything up to
+ * the integer pixel coordinates follows the reference -- which objects are drawn, their end points, the integer conversions,
+ * colours, thicknesses, panel sizes and layout.  The RASTERISATION RULE below is this project's own definition: OpenCV's
+ * cv2.line is not available to compare with, so pixel equality with OpenCV is NOT claimed.
+ *
+ * srcnn_render_overlay.  left / right: uint8 RGB (H, W, 3); rec: (max_det + 1, SRCNN_REC_COLS); p2_host: the 3x4 P2, 12 host
+ * doubles, row-major; bev_plane: uint8 (y_max, x_max) gray plane as srcnn_bev_lidar writes it, or NULL = all white (255); panel:
+ * uint8 RGB (2 H, W + x_max, 3) -- rows [0, H) x columns [0, W) the left image, rows [H, 2 H) the right image, columns
+ * [W, W + x_max) the bird's-eye view (x_max == 0: no such columns; otherwise y_max must equal 2 H, as the reference's
+ * np.concatenate needs).  res, x_max, y_max, x_off, y_off are the reference's float64 host values for width = 2 H:
+ * res = 70.0 / width, x_max = int(40 / res), y_max = int(70 / res), x_off = int(floor(-20 / res)), y_off = int(floor(70 / res)) - 1.
+ * With count = the record's row 0 column 0 (clamped to [0, max_det]) and row r the r-th detection:
+ *   2-D boxes (layer 1): rows r < min(100, count) with score > vis_thresh: the left box on the left image and the right box on
+ *     the right image, each four segments between the corners (rint(x1), rint(y1)), (rint(x2), rint(y2)), rint = float32
+ *     round-half-even; RGB (204, 0, 0), thickness 1.
+ *   wireframes (layer 2): rows r < count with alignment status (column 25) > 0 and score > vis_thresh; in float64, with
+ *     (x, y, z, theta) = columns 27-30, (w, h, l) = columns 9-11, c = cos(theta), s = sin(theta): corner(a, b, d) =
+ *     (x + (c a + s d) / 2, y + b / 2, z + (-s a + c d) / 2) for (a, b, d) = (-w, 0, -l), (-w, 0, l), (w, 0, l), (w, 0, -l) and the same
+ *     four with b = -2 h; pixel = (trunc(u / n), trunc(v / n)) with (u, v, n) = P2[:, 0:3] . corner, each sum left to right.  A
+ *     box with ANY corner at z < 0 is skipped whole.  Edges 0-1 1-2 2-3 0-3, 4-5 5-6 6-7 7-4, 4-0 5-1 6-2 7-3; RGB (0, 200, 0),
+ *     thickness 1, on the left image.
+ *   bird's-eye boxes (layer 4): the same rows; points 0-3 = the four corners with b = 0, point 4 = (x + s t, y, z + c t) with
+ *     t = l * 2 / 3; pixel = (trunc(X / res) - x_off, trunc(-Z / res) + y_off); edges 0-1 1-2 2-3 0-3 1-4 2-4; RGB (0, 200, 0),
+ *     thickness 2.
+ * `layers`: the sum of the layers to draw (7 = all).  Every coordinate is clamped to [-2^30, 2^30] (NaN -> -2^30) before its
+ * conversion to an integer, and all line arithmetic is 64-bit: a corner near z -> 0+ projects arbitrarily far away.
+ * Draw order, later wins: image pixels, 2-D boxes in record order, wireframes in record order; on the bird's-eye view the plane,
+ * then the boxes in record order.  An object drawn on one of the three targets never spills into another.
+ *
+ * RASTERISATION RULE.  A segment p0 -> p1 has adx = |x1 - x0|, ady = |y1 - y0|, sx = sign(x1 - x0), sy = sign(y1 - y0).  If
+ * adx >= ady (x-major) its pixels are x = x0 + sx i, y = y0 + sy ((2 i ady + adx) / (2 adx)) for i = 0..adx, the division
+ * rounding down; a zero-length segment is the single pixel p0; the y-major case (adx < ady) is the same with x and y exchanged.
+ * Thickness t stamps, at each such pixel, the offsets dx, dy in [-(t / 2), (t - 1) / 2] (integer division).  Pixels outside the
+ * target rectangle are dropped.  The rule is a closed-form membership test: the kernel is a gather -- a thread owns pixels,
+ * walks the segments whose bounding box meets its tile and keeps the last one that covers the pixel -- so every panel byte is
+ * written exactly once, without atomics, and the panel does not depend on the launch geometry (`rows_per_thread`: 1, 2, 4 or
+ * 8 pixel rows per thread, 0 = the default; a tile is 64 x 4 rows_per_thread pixels).
+ * workspace: srcnn_overlay_workspace_bytes(max_det) bytes, the segment list (26 slots per record row).
+ *
+ * srcnn_bev_lidar.  kitti_utils.get_point_cloud without its image crop + vis_3d_utils.vis_lidar_in_bev:53-66.  points: n_points
+ * x (x, y, z, intensity) float32, 16-byte aligned; velo_to_cam2_host: rows 0-2 of the reference's float64 product
+ * T(t_cam2_cam0) . pad(R0_rect) . pad(Tr_velo_to_cam), 12 host doubles.  Sets the whole (y_max, x_max) plane to 255, then per
+ * point, float64: X = m00 x + m01 y + m02 z + m03 (left to right), Z likewise from row 2; kept when 0 < Z < 70 and -20 < X < 20;
+ * x_img = trunc(X / res) - x_off, y_img = trunc(-Z / res) + y_off, each clamped from ABOVE only (x_max - 1, y_max - 1) as the
+ * reference does; plane[y_img, x_img] = 100.  A negative index, which numpy would wrap to the other end of the plane, is
+ * skipped: after the filter trunc(X / res) >= trunc(-20 / res) >= x_off and trunc(-Z / res) >= -floor(70 / res), so none occurs
+ * for the geometry above.  Every store writes the same value, so plain stores are race-free in outcome.  n_points == 0 leaves the
+ * plane white: what the reference shows without a lidar file (its single point at the origin is filtered out).
+ *
+ * Errors (SRCNN_ERR_ARG, before any HIP call): a null pointer (left, right, rec, p2_host, panel, workspace; plane,
+ * velo_to_cam2_host, points when n_points > 0), H or W <= 0 or > 32768, max_det < 0 or > 4096, rec_cols != SRCNN_REC_COLS,
+ * x_max < 0 or > 65536, |x_off| or |y_off| > SRCNN_OVERLAY_MAX_OFFSET (2^20: with the clamp and the panel sizes above every end
+ * point stays inside 32 bits), x_max > 0 with y_max != 2 H, x_max or y_max <= 0 (srcnn_bev_lidar), a non-finite or non-positive res,
+ * layers outside 0..7, rows_per_thread not one of 0, 1, 2, 4, 8, a non-finite vis_thresh, n_points < 0, misaligned points, a
+ * panel (plane) that overlaps one of the inputs; SRCNN_ERR_WORKSPACE: a workspace smaller than srcnn_overlay_workspace_bytes. */
+#define SRCNN_OVERLAY_SLOTS_PER_ROW 26
+#define SRCNN_OVERLAY_MAX_OFFSET 1048576
+#define SRCNN_OVERLAY_BOXES 1
+#define SRCNN_OVERLAY_WIREFRAMES 2
+#define SRCNN_OVERLAY_BEV_BOXES 4
+SRCNN_API size_t srcnn_overlay_workspace_bytes(int max_det);
+SRCNN_API int srcnn_render_overlay(const unsigned char *left, const unsigned char *right, int H, int W, const float *rec,
+                         int max_det, int rec_cols, const double *p2_host, float vis_thresh, const unsigned char *bev_plane,
+                         double res, int x_max, int y_max, int x_off, int y_off, int layers, int rows_per_thread,
+                         unsigned char *panel, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_bev_lidar(const float *points, int n_points, const double *velo_to_cam2_host, double res, int x_max, int y_max,
+                    int x_off, int y_off, unsigned char *plane, srcnn_stream_t stream);
 
 /* ------------------------------------------------------------------ recorded launch programs
  * The forward is a fixed list of ~230 asynchronous launches over fixed buffers (one list per input size and buffer set).

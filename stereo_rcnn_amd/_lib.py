@@ -26,6 +26,8 @@ OPT_TENSORS_PER_LAUNCH = 64     # SRCNN_OPT_TENSORS_PER_LAUNCH: tensors one laun
 LOADER_MAX_BATCH = 16           # SRCNN_LOADER_MAX_BATCH: batch slots one launch of the batch assembly kernels carries in its arguments
 GT_COLS = 24                    # SRCNN_GT_COLS: floats of one object row of the ground-truth table (include/srcnn_hip.h lists the columns)
 GT_MAX_ROWS = 512               # SRCNN_GT_MAX_ROWS: objects of one roidb entry srcnn_gt_batch ranks
+OVERLAY_SLOTS_PER_ROW = 26      # SRCNN_OVERLAY_SLOTS_PER_ROW: segments srcnn_render_overlay keeps per record row (8 + 12 + 6)
+OVERLAY_BOXES, OVERLAY_WIREFRAMES, OVERLAY_BEV_BOXES = 1, 2, 4      # SRCNN_OVERLAY_*: the layers of srcnn_render_overlay
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
@@ -239,6 +241,10 @@ _SIGNATURES = {
                                c_void_p]),
     "srcnn_gt_batch": (c_int, [c_void_p, c_int, ctypes.POINTER(GtSlot), c_int, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_void_p]),
     "srcnn_preprocess_train": (c_int, [ctypes.POINTER(TrainImage), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "srcnn_overlay_workspace_bytes": (c_size_t, [c_int]),
+    "srcnn_render_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.POINTER(c_double), c_float, c_void_p,
+                                     c_double, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "srcnn_bev_lidar": (c_int, [c_void_p, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -206,7 +206,7 @@ SRCNN_API int srcnn_debug_stamp_log(long long *rows, int max_rows)
     return n;
 }
 
-int srcnn_version(void) { return 300; }   // 300: srcnn_grad_norm (+ _workspace_bytes), srcnn_grad_scale, srcnn_sgd_step; 290: srcnn_upsample_add_backward, srcnn_subsample2_backward, srcnn_pixel_shuffle2; 280: srcnn_conv2d_backward (+ _workspace_bytes, srcnn_conv_bwd_desc); 270: srcnn_anchor_targets / srcnn_proposal_targets (+ *_workspace_bytes); 260: srcnn_cross_entropy / srcnn_smooth_l1 (+ _backward), srcnn_loss_workspace_bytes; 250: srcnn_kitti_overlaps / srcnn_kitti_match; 210: srcnn_stream_create*, srcnn_probe_placement, srcnn_conv_desc.head_* (appended fields)
+int srcnn_version(void) { return 310; }   // 310: srcnn_render_overlay (+ srcnn_overlay_workspace_bytes), srcnn_bev_lidar; 300: srcnn_grad_norm (+ _workspace_bytes), srcnn_grad_scale, srcnn_sgd_step; 290: srcnn_upsample_add_backward, srcnn_subsample2_backward, srcnn_pixel_shuffle2; 280: srcnn_conv2d_backward (+ _workspace_bytes, srcnn_conv_bwd_desc); 270: srcnn_anchor_targets / srcnn_proposal_targets (+ *_workspace_bytes); 260: srcnn_cross_entropy / srcnn_smooth_l1 (+ _backward), srcnn_loss_workspace_bytes; 250: srcnn_kitti_overlaps / srcnn_kitti_match; 210: srcnn_stream_create*, srcnn_probe_placement, srcnn_conv_desc.head_* (appended fields)
 
 int srcnn_range_flag_read(int reset)
 {

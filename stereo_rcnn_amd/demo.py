@@ -1,10 +1,13 @@
-"""One stereo pair from disk - the reference's demo.py:63-338 without the OpenCV visualisation:
+"""One stereo pair from disk - the reference's demo.py:63-338:
 
     python -m stereo_rcnn_amd.demo --left demo/left.png --right demo/right.png --calib demo/calib.txt --checkpoint models_stereo/stereo_rcnn_12_6477.pth
 
 Prints one KITTI-format line per aligned object (class, alpha, 2-D box, h w l, x y z, ry, score) and the two phase
-times the reference reports (`det_time`: forward + decode, `solve_time`: 3-D solve + dense alignment)."""
+times the reference reports (`det_time`: forward + decode, `solve_time`: 3-D solve + dense alignment).  `--out result.png` also
+writes the picture the reference shows in a window (demo.py:225-333: both images with the 2-D boxes, the 3-D wireframes, the
+bird's-eye view of `--lidar demo/lidar.bin` with the 3-D boxes), drawn on the device by stereo_rcnn_amd/visualize.py."""
 import argparse
+import os
 import sys
 import tempfile
 import time
@@ -24,7 +27,12 @@ def main(argv=None):
     ap.add_argument('--calib', required=True)
     ap.add_argument('--checkpoint', required=True)
     ap.add_argument('--precision', choices=['f16x3', 'f32'], default='f16x3')
+    ap.add_argument('--out', default=None, help='write the result picture (PNG) here')
+    ap.add_argument('--lidar', default=None, help='velodyne .bin for the bird\'s-eye view of --out (absent: a white one, as the reference)')
+    ap.add_argument('--vis-thresh', type=float, default=0.7, help='score above which --out draws a detection (demo.py:95)')
     args = ap.parse_args(argv)
+    if args.lidar and not os.path.isfile(args.lidar):
+        ap.error('--lidar %s: no such file (leave the option out for a white bird\'s-eye view)' % args.lidar)
     from . import serving
     serving.before_hip()
     serving.enter(1)                      # one pair: latency regime (branches on side streams, in-situ plans)
@@ -52,6 +60,12 @@ def main(argv=None):
         except FileNotFoundError:
             pass
     print('%d objects (%d aligned) in %.1f ms' % (len(objs), sum(o['aligned'] for o in objs), dt * 1e3))
+    if args.out:
+        from . import visualize
+        from .distributed import objects_to_record
+        lidar = visualize.read_lidar(args.lidar) if args.lidar else None           # none: a white bird's-eye view (kitti_utils.py:353-354)
+        panel = visualize.render_result(lu, ru, objects_to_record(objs).to(dev), calib, lidar, args.vis_thresh)
+        visualize.save_png(panel, args.out)
 
 
 if __name__ == '__main__':

@@ -794,6 +794,81 @@ def gt_batch(table, slots, keys, K, out=None):
     return out
 
 
+def bev_geometry(H):
+    """The bird's-eye view's geometry for an image of H rows, in Python float64 as the reference takes it (demo.py:229 passes
+    width = 2 H; vis_3d_utils.py:44, 56-60): (res, x_max, y_max, x_off, y_off)."""
+    import math
+    width = 2 * int(H)
+    res = 70.0 / width
+    return res, int(40 / res), int(70 / res), int(math.floor(-20 / res)), int(math.floor(70 / res)) - 1
+
+
+def _device_u8(t, what):
+    if not t.is_cuda:
+        raise NotImplementedError("%s on %s: the overlay kernels run on the GPU only" % (what, t.device))
+    assert t.dtype == torch.uint8 and t.is_contiguous(), "%s must be a contiguous uint8 tensor" % what
+
+
+def bev_lidar(points, velo_to_cam2, H, out=None):
+    """The gray bird's-eye plane of a lidar cloud (kitti_utils.get_point_cloud + vis_3d_utils.vis_lidar_in_bev; csrc/overlay.hip).
+    points: (N, 4) float32 device tensor (x, y, z, intensity), N may be 0; velo_to_cam2: the 3x4 (or 4x4) float64 velodyne ->
+    camera-2 matrix (kitti_utils.velo_to_cam2); H: the image height the plane stands beside.  Returns the (y_max, x_max) uint8
+    plane: 255, 100 where a point falls."""
+    import numpy as np
+    if not points.is_cuda:
+        raise NotImplementedError("bev_lidar on %s: the overlay kernels run on the GPU only" % points.device)
+    assert points.dtype == torch.float32 and points.is_contiguous() and points.dim() == 2 and points.shape[1] == 4
+    res, x_max, y_max, x_off, y_off = bev_geometry(H)
+    if out is None:
+        out = torch.empty((y_max, x_max), dtype=torch.uint8, device=points.device)
+    _device_u8(out, "bev_lidar plane")
+    assert tuple(out.shape) == (y_max, x_max)
+    m = (_lib.c_double * 12)(*[float(v) for v in np.asarray(velo_to_cam2, np.float64)[:3].reshape(-1)])
+    n = int(points.shape[0])
+    _lib.check(_lib.lib().srcnn_bev_lidar(points.data_ptr() if n else None, n, m, res, x_max, y_max, x_off, y_off, out.data_ptr(),
+                                          _lib.stream()), "srcnn_bev_lidar")
+    return out
+
+
+def render_overlay(left_u8, right_u8, record, p2, vis_thresh=0.7, bev_plane=None, bev=True, layers=7, rows_per_thread=0, out=None):
+    """The result picture of one pair, drawn on the device from its detection record (demo.py:225-333; csrc/overlay.hip,
+    include/srcnn_hip.h "result visualisation" states the drawing model and the rasterisation rule).  left_u8 / right_u8: uint8 RGB
+    (H, W, 3) device tensors; record: (max_det + 1, REC_COLS) float32 device tensor; p2: the 3x4 P2; bev_plane: bev_lidar's
+    plane or None = white; bev=False: no bird's-eye columns (the panel is (2 H, W, 3)).  Returns the uint8 RGB panel
+    (2 H, W + x_max, 3).  Raises ValueError where the reference's int(70 / res) is not 2 H: the reference's np.concatenate fails there."""
+    import numpy as np
+    for t, what in ((left_u8, "render_overlay left image"), (right_u8, "render_overlay right image")):
+        _device_u8(t, what)
+    if not record.is_cuda:
+        raise NotImplementedError("render_overlay on %s: the overlay kernels run on the GPU only" % record.device)
+    assert left_u8.dim() == 3 and left_u8.shape[2] == 3 and tuple(left_u8.shape) == tuple(right_u8.shape)
+    assert record.dtype == torch.float32 and record.is_contiguous() and record.dim() == 2 and record.shape[1] == _lib.REC_COLS
+    assert record.shape[0] >= 1
+    H, W = int(left_u8.shape[0]), int(left_u8.shape[1])
+    res, x_max, y_max, x_off, y_off = bev_geometry(H)
+    if not bev:
+        x_max, bev_plane = 0, None
+    elif y_max != 2 * H:
+        raise ValueError("int(70 / res) = %d is not 2 H = %d: the bird's-eye view cannot stand beside the two images" % (y_max, 2 * H))
+    if bev_plane is not None:
+        _device_u8(bev_plane, "render_overlay bev plane")
+        assert tuple(bev_plane.shape) == (y_max, x_max)
+    dev = left_u8.device
+    if out is None:
+        out = torch.empty((2 * H, W + x_max, 3), dtype=torch.uint8, device=dev)          # the kernel writes every byte
+    _device_u8(out, "render_overlay panel")
+    assert tuple(out.shape) == (2 * H, W + x_max, 3)
+    max_det = int(record.shape[0]) - 1
+    L = _lib.lib()
+    ws = _lib.workspace(L.srcnn_overlay_workspace_bytes(max_det), dev, "overlay")
+    p = (_lib.c_double * 12)(*[float(v) for v in np.asarray(p2, np.float64).reshape(-1)[:12]])
+    _lib.check(L.srcnn_render_overlay(left_u8.data_ptr(), right_u8.data_ptr(), H, W, record.data_ptr(), max_det, _lib.REC_COLS, p,
+                                      float(vis_thresh), bev_plane.data_ptr() if bev_plane is not None else None, res, x_max, y_max,
+                                      x_off, y_off, int(layers), int(rows_per_thread), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _lib.stream()), "srcnn_render_overlay")
+    return out
+
+
 def stem_pack(im_nchw, out, batch_offset=0, out_fmt=0):
     """NCHW image -> zero-bordered NHWC4 for the stem conv; out_fmt FMT_SPLIT16 writes the same buffer in the layout the
     DMA conv engine reads (pass x_fmt=FMT_SPLIT16 to conv2d)."""

@@ -1,7 +1,8 @@
 """Host-side KITTI helpers on the inference path - reference lib/model/utils/kitti_utils.py:
 `read_obj_calibration` (:97-159), `infer_boundary` (:398-437), `write_detection_results` (:440-460) -- and, for the training
 data loader (stereo_rcnn_amd/datasets/kitti.py), `Box2d` / `KittiObject` (:13-31), `E2R` (:57-76) and `read_obj_data` (:161-265).
-Pure host I/O / tiny numpy loops in the reference as well; lidar/visualisation helpers of that file are out of scope."""
+Pure host I/O / tiny numpy loops in the reference as well.  Of the lidar helpers `velo_to_cam2` is the matrix of
+`lidar_to_cam_frame` (:303-340); the per-point work of `get_point_cloud` and the drawing live in stereo_rcnn_amd/visualize.py."""
 import math
 import os
 
@@ -39,6 +40,22 @@ def read_obj_calibration(calib_path):
     c.r0_rect = np.reshape(_row(lines[4]), (3, 3))
     c.tr_velodyne_to_cam0 = np.reshape(_row(lines[5]), (3, 4))
     return c
+
+
+def velo_to_cam2(calib):
+    """The 4x4 float64 matrix that takes a homogeneous velodyne point into the camera-2 frame (kitti_utils.py:303-340,
+    lidar_to_cam_frame): translation by t_cam2_cam0, times R0_rect padded to 4x4, times Tr_velo_to_cam padded to 4x4, multiplied
+    in the reference's order (rectification . velodyne first).  The per-point product and the bird's-eye filter run on the
+    device (engine.bev_lidar)."""
+    rect = np.zeros((4, 4))
+    rect[:3, :3] = calib.r0_rect
+    rect[3, 3] = 1.0
+    velo = np.zeros((4, 4))
+    velo[:3, :4] = calib.tr_velodyne_to_cam0
+    velo[3, 3] = 1.0
+    shift = np.identity(4)
+    shift[0:3, 3] = calib.t_cam2_cam0
+    return np.dot(shift, np.dot(rect, velo))
 
 
 def infer_boundary(im_shape, boxes_left):
