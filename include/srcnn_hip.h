@@ -813,6 +813,56 @@ SRCNN_API int srcnn_sgd_step(float *const *p_host, const float *const *g_host, f
                    const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors, float momentum,
                    int first_step, const float *coef, srcnn_stream_t stream);
 
+/* ------------------------------------------------------------------ weight preparation
+ * What engine.prep_conv / prep_conv_shortcut / prep_stem / prep_deconv2x2 / prep_linear_stack, ConvW.split_f16x3 and
+ * engine.head_fragments do with eager torch ops, for a LIST of layers in one call, on the device, into destinations the caller
+ * supplies: the in-place refresh of an inference plan's weights from live (trained) parameters.  The descriptors are a HOST
+ * array and travel in the kernels' argument blocks (at most SRCNN_PREP_LAYERS_PER_LAUNCH layers per launch): nothing is
+ * uploaded, nothing is read back.  Every result is bit-equal to the eager path's.
+ *
+ * Per layer, sources float32 in nn.Module layout:
+ *   SRCNN_PREP_CONV       n_src (1..3) weights (cout[s], cin, kh, kw), concatenated along Cout (the RPN head, the stacked box
+ *                         heads; nn.Linear is kh = kw = 1) -> dst_w (sum cout, kh, kw, cin); dst_b = the sources' biases (all or
+ *                         none), or the folded BN's (n_src == 1 only)
+ *   SRCNN_PREP_SHORTCUT   w[0] (cout, cin, 1, 1) with BN 0 and w[1] (cout, cin2, 1, 1) with BN 1 -> dst_w (cout, cin + cin2)
+ *                         = [conv3 | downsample] along K; dst_b = float32(float64(b'0) + float64(b'1))
+ *   SRCNN_PREP_STEM       w[0] (cout, 3, 7, 7) with BN 0 -> dst_w (cout, 7 row taps, 8 pixels, 4): element (co, kh, p, c) =
+ *                         w'(co, c, kh, p) for p < 7 and c < 3, zero otherwise (the zeros are written)
+ *   SRCNN_PREP_DECONV2X2  w[0] (cin, cout, 2, 2), b[0] (cout) -> dst_w (4 cout, cin), rows ordered (i, j, co); dst_b = b[0]
+ * Frozen BN (bn_g / bn_b / bn_m / bn_v = weight, bias, running_mean, running_var; all NULL = none), float64, each operation
+ * rounded once, never contracted:  s = g / sqrt(v + 1e-5),  w' = float32(w s),  b' = float32(beta - mean s).
+ * m = max |w'| over the layer (a NaN wins, as in torch.max); k = floor(log2(16384 / m)) taken from m's exponent and mantissa,
+ * 0 for m == 0 or a non-finite m; k_out[i] = k (device int32, one per layer of the list).  With dst_hi / dst_lo (float16, the
+ * shape of dst_w): hi = f16(w' 2^k), lo = f16(w' 2^k - hi), round to nearest even.  With dst_frag (1x1, cin % 16 == 0; frag_rows
+ * = rows rounded up to a multiple of 8): the fused head's fragment layout (cin / 16, 2, 2, frag_rows, 8) of the same hi / lo,
+ * element (s, h, g, n, i) = W_h[n][16 s + 8 g + i], rows past Cout zero.
+ * alias_of >= 0: this layer shares dst_w / dst_b (and so m and k) with the EARLIER layer alias_of of the list, which writes
+ * them; the layer itself only writes its own dst_hi / dst_lo / dst_frag (two ConvW over one weight tensor).  -1 otherwise.
+ * Every destination element is written exactly once (pass uninitialised buffers); no float atomics: the max is an integer max
+ * of bit patterns, the same on every run.  The workspace holds one word per layer.
+ *
+ * Errors (SRCNN_ERR_ARG with "layer i: reason" in srcnn_last_error(), before any launch): a null array / k_out / workspace /
+ * dst_w / source, an unknown form, sizes that do not fit the form ("size mismatch", kernel size, cin2, n_src), half of a BN,
+ * hi without lo, misaligned pointers, a layer of 2^31 elements or more; SRCNN_ERR_WORKSPACE: a workspace smaller than
+ * srcnn_prep_weights_workspace_bytes. */
+#define SRCNN_PREP_LAYERS_PER_LAUNCH 16
+#define SRCNN_PREP_CONV 0
+#define SRCNN_PREP_SHORTCUT 1
+#define SRCNN_PREP_STEM 2
+#define SRCNN_PREP_DECONV2X2 3
+typedef struct srcnn_prep_layer {
+    int form, n_src, kh, kw, cin, cin2;
+    int cout[3];
+    int frag_rows, alias_of, pad_;
+    const float *w[3], *b[3];
+    const float *bn_g[2], *bn_b[2], *bn_m[2], *bn_v[2];
+    float *dst_w, *dst_b;
+    void *dst_hi, *dst_lo, *dst_frag;
+} srcnn_prep_layer;
+SRCNN_API size_t srcnn_prep_weights_workspace_bytes(int n_layers);
+SRCNN_API int srcnn_prep_weights(const srcnn_prep_layer *layers_host, int n_layers, int *k_out, void *workspace,
+                       size_t workspace_bytes, srcnn_stream_t stream);
+
 /* ------------------------------------------------------------------ training: batch assembly
  * The per-iteration half of the reference's data loader (lib/roi_data_layer/minibatch.py, roibatchLoader.py:72-110,
  * lib/model/utils/blob.py), for a whole batch of at most SRCNN_LOADER_MAX_BATCH slots per launch.  The per-slot descriptions

@@ -26,6 +26,8 @@ OPT_TENSORS_PER_LAUNCH = 64     # SRCNN_OPT_TENSORS_PER_LAUNCH: tensors one laun
 LOADER_MAX_BATCH = 16           # SRCNN_LOADER_MAX_BATCH: batch slots one launch of the batch assembly kernels carries in its arguments
 GT_COLS = 24                    # SRCNN_GT_COLS: floats of one object row of the ground-truth table (include/srcnn_hip.h lists the columns)
 GT_MAX_ROWS = 512               # SRCNN_GT_MAX_ROWS: objects of one roidb entry srcnn_gt_batch ranks
+PREP_LAYERS_PER_LAUNCH = 16     # SRCNN_PREP_LAYERS_PER_LAUNCH: layers one launch of the weight preparation kernels carries in its arguments
+PREP_CONV, PREP_SHORTCUT, PREP_STEM, PREP_DECONV2X2 = 0, 1, 2, 3     # SRCNN_PREP_*: the forms of srcnn_prep_weights
 OVERLAY_SLOTS_PER_ROW = 26      # SRCNN_OVERLAY_SLOTS_PER_ROW: segments srcnn_render_overlay keeps per record row (8 + 12 + 6)
 OVERLAY_BOXES, OVERLAY_WIREFRAMES, OVERLAY_BEV_BOXES = 1, 2, 4      # SRCNN_OVERLAY_*: the layers of srcnn_render_overlay
 
@@ -104,6 +106,15 @@ class GtSlot(ctypes.Structure):
 class TrainImage(ctypes.Structure):
     """struct srcnn_train_image (include/srcnn_hip.h)."""
     _fields_ = [("left", c_void_p), ("right", c_void_p), ("H", c_int), ("W", c_int), ("flipped", c_int), ("scale", c_double)]
+
+
+class PrepLayer(ctypes.Structure):
+    """struct srcnn_prep_layer (include/srcnn_hip.h)."""
+    _fields_ = [("form", c_int), ("n_src", c_int), ("kh", c_int), ("kw", c_int), ("cin", c_int), ("cin2", c_int),
+                ("cout", c_int * 3), ("frag_rows", c_int), ("alias_of", c_int), ("pad_", c_int),
+                ("w", c_void_p * 3), ("b", c_void_p * 3),
+                ("bn_g", c_void_p * 2), ("bn_b", c_void_p * 2), ("bn_m", c_void_p * 2), ("bn_v", c_void_p * 2),
+                ("dst_w", c_void_p), ("dst_b", c_void_p), ("dst_hi", c_void_p), ("dst_lo", c_void_p), ("dst_frag", c_void_p)]
 
 
 _SIGNATURES = {
@@ -239,6 +250,8 @@ _SIGNATURES = {
     "srcnn_sgd_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong),
                                ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int, c_float, c_int, c_void_p,
                                c_void_p]),
+    "srcnn_prep_weights_workspace_bytes": (c_size_t, [c_int]),
+    "srcnn_prep_weights": (c_int, [ctypes.POINTER(PrepLayer), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "srcnn_gt_batch": (c_int, [c_void_p, c_int, ctypes.POINTER(GtSlot), c_int, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_void_p]),
     "srcnn_preprocess_train": (c_int, [ctypes.POINTER(TrainImage), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "srcnn_overlay_workspace_bytes": (c_size_t, [c_int]),

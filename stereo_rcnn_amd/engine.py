@@ -116,6 +116,82 @@ def head_fragments(hcw):
     return hcw._frag
 
 
+class PrepSpec(object):
+    """One layer of srcnn_prep_weights (include/srcnn_hip.h, "weight preparation"): the sources in nn.Module layout (float32
+    contiguous device tensors) and the destination tensors, which the call overwrites where they are.
+    form: _lib.PREP_*; ws / bs: the source weights and biases (bs None or a list with None entries); bns: one frozen-BN dict
+    (weight, bias, running_mean, running_var) per folded source.  alias_of: index of an earlier spec of the same call whose
+    dst_w / dst_b this layer shares (it then writes only its own hi / lo / fragments)."""
+
+    def __init__(self, form, ws, bs=None, bns=(), dst_w=None, dst_b=None, dst_hi=None, dst_lo=None, dst_frag=None, frag_rows=0,
+                 alias_of=-1):
+        self.form, self.ws, self.bs, self.bns = form, list(ws), list(bs) if bs is not None else [None] * len(ws), list(bns)
+        self.dst_w, self.dst_b, self.dst_hi, self.dst_lo, self.dst_frag, self.frag_rows = dst_w, dst_b, dst_hi, dst_lo, dst_frag, frag_rows
+        self.alias_of = alias_of
+
+    @classmethod
+    def for_convw(cls, form, cw, ws, bs=None, bns=(), alias_of=-1):
+        """Into the tensors a ConvW already holds: weight, bias, and -- where they exist -- w_hi / w_lo and the fused head's fragments."""
+        frag, rows = getattr(cw, '_frag', None) or (None, 0)
+        return cls(form, ws, bs, bns, cw.weight, cw.bias, cw.w_hi, cw.w_lo, frag, rows, alias_of)
+
+    def fill(self, d):
+        w0 = self.ws[0]
+        d.form, d.n_src, d.alias_of, d.frag_rows = self.form, len(self.ws), self.alias_of, self.frag_rows
+        if self.form == _lib.PREP_DECONV2X2:
+            d.cin, d.cout[0], d.kh, d.kw = int(w0.shape[0]), int(w0.shape[1]), int(w0.shape[2]), int(w0.shape[3])
+        else:
+            d.cin = int(w0.shape[1])
+            d.kh, d.kw = (int(w0.shape[2]), int(w0.shape[3])) if w0.dim() == 4 else (1, 1)
+            if self.form == _lib.PREP_SHORTCUT:
+                d.cin2 = int(self.ws[1].shape[1])
+            for i, w in enumerate(self.ws):
+                d.cout[i] = int(w.shape[0])
+                assert self.form == _lib.PREP_SHORTCUT or tuple(w.shape[1:]) == tuple(w0.shape[1:]), "sources of one layer share Cin and the kernel size"
+        for i, (w, b) in enumerate(zip(self.ws, self.bs)):
+            d.w[i], d.b[i] = _prep_src(w, int(w.numel())), _prep_src(b, d.cout[i])
+        for i, bn in enumerate(self.bns):
+            if bn is not None:
+                d.bn_g[i], d.bn_b[i], d.bn_m[i], d.bn_v[i] = (_prep_src(bn[k], d.cout[i]) for k in ('weight', 'bias', 'running_mean', 'running_var'))
+        rows = 4 * d.cout[0] if self.form == _lib.PREP_DECONV2X2 else (sum(d.cout[:len(self.ws)]) if self.form == _lib.PREP_CONV else d.cout[0])
+        row_len = 224 if self.form == _lib.PREP_STEM else (d.cin + d.cin2) * (d.kh * d.kw if self.form == _lib.PREP_CONV else 1)
+        n_bias = d.cout[0] if self.form == _lib.PREP_DECONV2X2 else rows
+        for name, t, dt, n in (('dst_w', self.dst_w, torch.float32, rows * row_len), ('dst_b', self.dst_b, torch.float32, n_bias),
+                               ('dst_hi', self.dst_hi, torch.float16, rows * row_len), ('dst_lo', self.dst_lo, torch.float16, rows * row_len),
+                               ('dst_frag', self.dst_frag, torch.float16, 2 * self.frag_rows * row_len)):
+            if t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n, \
+                    "prep_weights_into: %s must be a contiguous %s device tensor of %d elements" % (name, dt, n)
+                setattr(d, name, t.data_ptr())
+
+
+def _prep_src(t, numel):
+    if t is None:
+        return None
+    assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == numel, \
+        "prep_weights_into: sources are contiguous float32 device tensors of the layer's sizes"
+    return t.data_ptr()
+
+
+def prep_weights_into(specs, k_out=None):
+    """srcnn_prep_weights over a list of PrepSpec on torch's current stream: BN fold, re-layout, max |w|, hi / lo split and head
+    fragments of every layer, written into the specs' destination tensors.  No host read.  Returns k_out, the device int32 vector of
+    the layers' power-of-two exponents k (inv_scale = 2^-k)."""
+    L = _lib.lib()
+    n = len(specs)
+    dev = specs[0].dst_w.device
+    if k_out is None:
+        k_out = torch.empty((n,), dtype=torch.int32, device=dev)
+    assert k_out.is_cuda and k_out.dtype == torch.int32 and k_out.numel() == n and k_out.is_contiguous()
+    descs = (_lib.PrepLayer * n)()
+    for d, s in zip(descs, specs):
+        s.fill(d)
+    with torch.cuda.device(dev):
+        ws = _lib.workspace(L.srcnn_prep_weights_workspace_bytes(n), dev, "prep_weights")
+        _lib.check(L.srcnn_prep_weights(descs, n, k_out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_prep_weights")
+    return k_out
+
+
 def conv_out_hw(h, w, k_h, k_w, stride, pad):
     return (h + 2 * pad - k_h) // stride + 1, (w + 2 * pad - k_w) // stride + 1
 

@@ -35,13 +35,66 @@ def _bn_dict(sd, prefix):
     return {k: sd[prefix + '.' + k] for k in ('weight', 'bias', 'running_mean', 'running_var')}
 
 
+def weight_table(keys):
+    """The prepared layers of a reference-schema state_dict with these keys, in build order: one dict per engine.ConvW --
+    `name`, `kind` (which engine.prep_* builds it) and the state_dict entries it is made of.  Weights.__init__ builds from
+    this list and Weights.refresh walks it again."""
+    t = [dict(name='stem', kind='stem', w='RCNN_layer0.0.weight', bn='RCNN_layer0.1')]
+    for li in (1, 2, 3, 4):
+        b = 0
+        while 'RCNN_layer%d.0.%d.conv1.weight' % (li, b) in keys:
+            p = 'RCNN_layer%d.0.%d' % (li, b)
+            n = 'layer%d.%d.' % (li, b)
+            stride = 2 if (b == 0 and li > 1) else 1          # stride on the first 1x1 (resnet.py:71)
+            t.append(dict(name=n + 'conv1', kind='conv', w=p + '.conv1.weight', bn=p + '.bn1', stride=stride, pad=0, relu=True))
+            t.append(dict(name=n + 'conv2', kind='conv', w=p + '.conv2.weight', bn=p + '.bn2', stride=1, pad=1, relu=True))
+            t.append(dict(name=n + 'conv3', kind='conv', w=p + '.conv3.weight', bn=p + '.bn3', stride=1, pad=0, relu=True))
+            if p + '.downsample.0.weight' in keys:
+                t.append(dict(name=n + 'down', kind='conv', w=p + '.downsample.0.weight', bn=p + '.downsample.1', stride=stride, pad=0,
+                              relu=False))
+                # conv3 and the projection shortcut as one GEMM over [conv2's output | the block's input] (SPLIT16 engine)
+                t.append(dict(name=n + 'conv3_down', kind='shortcut', w=p + '.conv3.weight', bn=p + '.bn3', w2=p + '.downsample.0.weight',
+                              bn2=p + '.downsample.1', stride=stride))
+            b += 1
+
+    def cb(name, key, stride=1, pad=0, relu=False):
+        t.append(dict(name=name, kind='conv', w=key + '.weight', b=key + '.bias', bn=None, stride=stride, pad=pad, relu=relu))
+
+    cb('toplayer', 'RCNN_toplayer')
+    for i in (1, 2, 3):
+        cb('smooth%d' % i, 'RCNN_smooth%d' % i, 1, 1)
+    for i in (1, 2, 3):
+        cb('lateral%d' % i, 'RCNN_latlayer%d' % i)
+    cb('rpn_conv', 'RCNN_rpn.RPN_Conv', 1, 1, True)
+    # the same weights as ONE launch over [left images | right images] that writes [left 512 | right 512] per pixel
+    t.append(dict(name='rpn_conv_pair', kind='pair', of='rpn_conv'))
+    t.append(dict(name='rpn_head', kind='cat', ws=['RCNN_rpn.RPN_cls_score.weight', 'RCNN_rpn.RPN_bbox_pred_left_right.weight'],
+                  bs=['RCNN_rpn.RPN_cls_score.bias', 'RCNN_rpn.RPN_bbox_pred_left_right.bias']))
+    # box head: 7x7/7 conv over the (7,7,512) NHWC roi tile == one GEMM row of 25088 (resnet.py:256-263)
+    t.append(dict(name='top0', kind='top0', w='RCNN_top.0.weight', b='RCNN_top.0.bias'))
+    cb('top3', 'RCNN_top.3', 1, 0, True)
+    t.append(dict(name='fc', kind='stack', ws=['RCNN_bbox_pred.weight', 'RCNN_dim_orien_pred.weight', 'RCNN_cls_score.weight'],
+                  bs=['RCNN_bbox_pred.bias', 'RCNN_dim_orien_pred.bias', 'RCNN_cls_score.bias']))
+    for i in (0, 2, 4, 6, 8, 10):
+        cb('kpts.%d' % i, 'RCNN_kpts.%d' % i, 1, 1, True)
+    t.append(dict(name='kpts_up', kind='deconv', w='RCNN_kpts.12.weight', b='RCNN_kpts.12.bias'))
+    cb('kpts_class', 'kpts_class')
+    return t
+
+
+class _Prepared(object):
+    """A Weights' layer table and the ConvW built from each entry."""
+
+    def __init__(self, table):
+        self.table, self.by_name = table, {}
+
+
 class Weights(object):
     """Engine-ready weights built from a reference-schema state_dict (CPU tensors)."""
 
     def __init__(self, sd, device):
         # re-layout / BN folding run on the device (load-time plumbing; float64 fold is cheap there)
-        sd = {k: v.detach().to(device=device, dtype=torch.float32) for k, v in sd.items()
-              if not k.endswith('num_batches_tracked')}
+        sd = self._on_device(sd, device)
         self.device = device
         # per-tensor power-of-two activation scales of the SPLIT16 engine: group name -> k (tensor stored x 2^k); empty until
         # Plan.calibrate() has seen one input (then fixed for the life of these weights, for every plan / slot)
@@ -51,57 +104,112 @@ class Weights(object):
         self.calib_epoch = 0           # bumped whenever the shifts change: plans drop their recorded programs / graphs
         # per layer: may the first block's conv3 take the block input as its second operand (both must carry one scale)
         self.fuse_shortcut = [True, True, True, True]
-        self.stem = engine.prep_stem(sd['RCNN_layer0.0.weight'], _bn_dict(sd, 'RCNN_layer0.1'), device)
+        self.prepared = _Prepared(weight_table(sd))      # the table and its ConvW by name (refresh walks them again)
+        cw = self.prepared.by_name
+        for e in self.prepared.table:
+            cw[e['name']] = self._build(e, sd, device)
+        self.stem = cw['stem']
         self.layers = []
         for li in (1, 2, 3, 4):
             blocks = []
             b = 0
-            while 'RCNN_layer%d.0.%d.conv1.weight' % (li, b) in sd:
-                p = 'RCNN_layer%d.0.%d' % (li, b)
-                stride = 2 if (b == 0 and li > 1) else 1          # stride on the first 1x1 (resnet.py:71)
-                blk = {
-                    'conv1': engine.prep_conv(sd[p + '.conv1.weight'], None, stride, 0, True, _bn_dict(sd, p + '.bn1'), device),
-                    'conv2': engine.prep_conv(sd[p + '.conv2.weight'], None, 1, 1, True, _bn_dict(sd, p + '.bn2'), device),
-                    'conv3': engine.prep_conv(sd[p + '.conv3.weight'], None, 1, 0, True, _bn_dict(sd, p + '.bn3'), device),
-                    'down': None,
-                }
-                if p + '.downsample.0.weight' in sd:
-                    blk['down'] = engine.prep_conv(sd[p + '.downsample.0.weight'], None, stride, 0, False,
-                                                   _bn_dict(sd, p + '.downsample.1'), device)
-                    # conv3 and the projection shortcut as one GEMM over [conv2's output | the block's input] (SPLIT16 engine)
-                    blk['conv3_down'] = engine.prep_conv_shortcut(sd[p + '.conv3.weight'], _bn_dict(sd, p + '.bn3'),
-                                                                  sd[p + '.downsample.0.weight'], _bn_dict(sd, p + '.downsample.1'),
-                                                                  stride, device)
+            while 'layer%d.%d.conv1' % (li, b) in cw:
+                n = 'layer%d.%d.' % (li, b)
+                blk = {'conv1': cw[n + 'conv1'], 'conv2': cw[n + 'conv2'], 'conv3': cw[n + 'conv3'], 'down': cw.get(n + 'down')}
+                if blk['down'] is not None:
+                    blk['conv3_down'] = cw[n + 'conv3_down']
                 blocks.append(blk)
                 b += 1
             self.layers.append(blocks)
-
-        def cb(name, stride=1, pad=0, relu=False):
-            return engine.prep_conv(sd[name + '.weight'], sd[name + '.bias'], stride, pad, relu, None, device)
-
-        self.toplayer = cb('RCNN_toplayer')
-        self.smooth = [cb('RCNN_smooth%d' % i, 1, 1) for i in (1, 2, 3)]
-        self.lateral = [cb('RCNN_latlayer%d' % i) for i in (1, 2, 3)]
-        self.rpn_conv = cb('RCNN_rpn.RPN_Conv', 1, 1, True)
-        # the same weights as ONE launch over [left images | right images] that writes [left 512 | right 512] per pixel
-        self.rpn_conv_pair = engine.ConvW(self.rpn_conv.weight, self.rpn_conv.bias, 3, 3, 1, 1, True, mode=2)
-        hw = torch.cat((sd['RCNN_rpn.RPN_cls_score.weight'], sd['RCNN_rpn.RPN_bbox_pred_left_right.weight']), 0)
-        hb = torch.cat((sd['RCNN_rpn.RPN_cls_score.bias'], sd['RCNN_rpn.RPN_bbox_pred_left_right.bias']), 0)
-        self.rpn_head = engine.prep_conv(hw, hb, 1, 0, False, None, device)
-        # box head: 7x7/7 conv over the (7,7,512) NHWC roi tile == one GEMM row of 25088 (resnet.py:256-263)
-        w0 = sd['RCNN_top.0.weight']                                  # (2048, 512, 7, 7)
-        self.top0 = engine.ConvW(w0.permute(0, 2, 3, 1).contiguous().view(w0.shape[0], 1, 1, -1).to(device),
-                                 sd['RCNN_top.0.bias'].to(device), 1, 1, 1, 0, True)
-        self.top3 = cb('RCNN_top.3', 1, 0, True)
-        self.fc = engine.prep_linear_stack(
-            [sd['RCNN_bbox_pred.weight'], sd['RCNN_dim_orien_pred.weight'], sd['RCNN_cls_score.weight']],
-            [sd['RCNN_bbox_pred.bias'], sd['RCNN_dim_orien_pred.bias'], sd['RCNN_cls_score.bias']], device)
+        self.toplayer = cw['toplayer']
+        self.smooth = [cw['smooth%d' % i] for i in (1, 2, 3)]
+        self.lateral = [cw['lateral%d' % i] for i in (1, 2, 3)]
+        self.rpn_conv = cw['rpn_conv']
+        self.rpn_conv_pair = cw['rpn_conv_pair']
+        self.rpn_head = cw['rpn_head']
+        self.top0 = cw['top0']
+        self.top3 = cw['top3']
+        self.fc = cw['fc']
         self.n_bbox = int(sd['RCNN_bbox_pred.weight'].shape[0])
         self.n_dim = int(sd['RCNN_dim_orien_pred.weight'].shape[0])
         self.n_cls = int(sd['RCNN_cls_score.weight'].shape[0])
-        self.kpts = [cb('RCNN_kpts.%d' % i, 1, 1, True) for i in (0, 2, 4, 6, 8, 10)]
-        self.kpts_up = engine.prep_deconv2x2(sd['RCNN_kpts.12.weight'], sd['RCNN_kpts.12.bias'], True, device)
-        self.kpts_class = cb('kpts_class')
+        self.kpts = [cw['kpts.%d' % i] for i in (0, 2, 4, 6, 8, 10)]
+        self.kpts_up = cw['kpts_up']
+        self.kpts_class = cw['kpts_class']
+
+    @staticmethod
+    def _on_device(sd, device):
+        return {k: v.detach().to(device=device, dtype=torch.float32) for k, v in sd.items() if not k.endswith('num_batches_tracked')}
+
+    def _build(self, e, sd, device):
+        """The eager build of one table entry (engine.prep_*)."""
+        kind = e['kind']
+        if kind == 'stem':
+            return engine.prep_stem(sd[e['w']], _bn_dict(sd, e['bn']), device)
+        if kind == 'conv':
+            return engine.prep_conv(sd[e['w']], sd[e['b']] if e.get('b') else None, e['stride'], e['pad'], e['relu'],
+                                    _bn_dict(sd, e['bn']) if e['bn'] else None, device)
+        if kind == 'shortcut':
+            return engine.prep_conv_shortcut(sd[e['w']], _bn_dict(sd, e['bn']), sd[e['w2']], _bn_dict(sd, e['bn2']), e['stride'], device)
+        if kind == 'pair':
+            of = self.prepared.by_name[e['of']]
+            return engine.ConvW(of.weight, of.bias, 3, 3, 1, 1, True, mode=2)
+        if kind == 'cat':
+            hw = torch.cat([sd[k] for k in e['ws']], 0)
+            hb = torch.cat([sd[k] for k in e['bs']], 0)
+            return engine.prep_conv(hw, hb, 1, 0, False, None, device)
+        if kind == 'top0':
+            w0 = sd[e['w']]                                  # (2048, 512, 7, 7)
+            return engine.ConvW(w0.permute(0, 2, 3, 1).contiguous().view(w0.shape[0], 1, 1, -1).to(device), sd[e['b']].to(device), 1, 1, 1, 0, True)
+        if kind == 'stack':
+            return engine.prep_linear_stack([sd[k] for k in e['ws']], [sd[k] for k in e['bs']], device)
+        assert kind == 'deconv', kind
+        return engine.prep_deconv2x2(sd[e['w']], sd[e['b']], True, device)
+
+    def _spec(self, e, sd, index):
+        """The device-side form of _build: the same sources into the tensors the entry's ConvW holds."""
+        kind, cw = e['kind'], self.prepared.by_name[e['name']]
+        src = lambda k: sd[k].contiguous()
+        bn = lambda p: {k: v.contiguous() for k, v in _bn_dict(sd, p).items()}
+        S, L = engine.PrepSpec.for_convw, _lib
+        if kind == 'stem':
+            return S(L.PREP_STEM, cw, [src(e['w'])], None, [bn(e['bn'])])
+        if kind == 'conv':
+            return S(L.PREP_CONV, cw, [src(e['w'])], [src(e['b'])] if e.get('b') else None, [bn(e['bn'])] if e['bn'] else ())
+        if kind == 'shortcut':
+            return S(L.PREP_SHORTCUT, cw, [src(e['w']), src(e['w2'])], None, [bn(e['bn']), bn(e['bn2'])])
+        if kind == 'pair':
+            of = next(x for x in self.prepared.table if x['name'] == e['of'])
+            return S(L.PREP_CONV, cw, [src(of['w'])], [src(of['b'])], (), alias_of=index[e['of']])
+        if kind in ('cat', 'stack'):
+            return S(L.PREP_CONV, cw, [src(k) for k in e['ws']], [src(k) for k in e['bs']])
+        if kind == 'top0':
+            return S(L.PREP_CONV, cw, [src(e['w'])], [src(e['b'])])
+        assert kind == 'deconv', kind
+        return S(L.PREP_DECONV2X2, cw, [src(e['w'])], [src(e['b'])])
+
+    def refresh(self, model_or_state_dict):
+        """Overwrites every prepared tensor (weight, bias, and where a layer has them w_hi / w_lo, the fused heads' fragments and
+        the pre-scaled bias copies) from live parameters, on the device and in place: ONE srcnn_prep_weights call over the table
+        __init__ built from, bit-equal to a new Weights of the same state_dict, every device pointer unchanged.  A layer that was
+        never split stays so (its first f16x3 launch splits the refreshed weight).  One host read: the vector of the layers'
+        exponents k, because inv_scale = 2^-k is a host float in the launch descriptors.
+        Returns the names of the layers whose inv_scale changed."""
+        sd = model_or_state_dict.state_dict() if hasattr(model_or_state_dict, 'state_dict') else model_or_state_dict
+        sd = self._on_device(sd, self.device)
+        index = {e['name']: i for i, e in enumerate(self.prepared.table)}
+        specs = [self._spec(e, sd, index) for e in self.prepared.table]
+        with torch.no_grad():
+            k = engine.prep_weights_into(specs).cpu().tolist()          # the refresh's one host read
+            changed = []
+            for e, ki in zip(self.prepared.table, k):
+                cw = self.prepared.by_name[e['name']]
+                if cw.w_hi is not None and cw.inv_scale != 2.0 ** (-ki):
+                    cw.inv_scale = 2.0 ** (-ki)
+                    changed.append(e['name'])
+                for shift, t in getattr(cw, '_bias_shifted', {}).items():   # engine.conv2d's copies of the bias x 2^out_shift
+                    torch.mul(cw.bias, 2.0 ** shift, out=t)
+        return changed
 
 
 class Plan(object):
@@ -773,6 +881,36 @@ class Plan(object):
         self.programs[self.program_key(precision, kpts)] = (prog, refs)
         return prog
 
+    def _drop_recorded(self):
+        """Forget the recorded launch programs and captured graphs: their launches carry scales by value."""
+        for prog, _ in self.programs.values():
+            _lib.lib().srcnn_program_destroy(prog)
+        self.programs, self.graphs = {}, {}
+
+    def refresh(self, model, recalibrate=True):
+        """Take the model's (or state_dict's) current parameters into this plan's weights, in place and on the device
+        (Weights.refresh: one srcnn_prep_weights call, one host read): buffers, device pointers, tuned conv plans and -- where no
+        scale moved -- the recorded launch programs are kept, and the next run computes what a plan newly built from the same
+        parameters computes, bit for bit.
+          * A layer whose weight scale (inv_scale, a host float inside the launch descriptors) changed makes the recorded programs
+            and graphs stale: they are dropped here, and for every other plan on these weights at its next run.
+          * The SPLIT16 activation scales were calibrated for the old parameters: with `recalibrate` the next f16x3 run calibrates
+            again, as a new plan's first run does, and drops the programs then if a scale moved.  recalibrate=False keeps the
+            scales (the range guard still watches them) -- for weights that moved little.
+        Returns {'scale_changed': [layer names], 'programs_dropped': bool, 'recalibrate': bool}."""
+        w = self.w
+        changed = w.refresh(model)
+        if changed:
+            w.calib_epoch += 1              # every plan on these weights checks it in run()
+            self._drop_recorded()
+            self._epoch = (w.calib_epoch, engine.tune_mode_key(), engine.PLAN_EPOCH)
+        again = bool(recalibrate and w.calibrated)
+        if again:
+            w.calibrated = False
+            w.guard_trips = 0               # (pipeline's range-guard bookkeeping belongs to the old calibration)
+            w.__dict__.pop('first_shifts', None)
+        return {'scale_changed': changed, 'programs_dropped': bool(changed), 'recalibrate': again}
+
     def program_key(self, precision, kpts, par=None):
         """Key of a recorded launch program in self.programs: one list per (engine, keypoint branch, branches on side streams,
         chained bottlenecks)."""
@@ -787,9 +925,8 @@ class Plan(object):
                 self.calibrate()               # once per weights: the scales of every SPLIT16 tensor group, from this first input
             epoch = (self.w.calib_epoch, engine.tune_mode_key(), engine.PLAN_EPOCH)
             if self._epoch != epoch:      # the scales, or the tuner's objective (= the plan set), changed since this plan recorded its launch lists
-                for prog, _ in self.programs.values():
-                    _lib.lib().srcnn_program_destroy(prog)
-                self.programs, self.graphs, self._epoch = {}, {}, epoch
+                self._drop_recorded()
+                self._epoch = epoch
             if use_program and not use_graph:
                 # the stem input is packed here, eagerly, from wherever the inputs are (set_inputs keeps references instead of
                 # copying; set_images wrote `packed` itself); the recorded list starts at the stem conv

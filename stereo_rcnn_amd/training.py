@@ -26,8 +26,9 @@ reference's configuration) has to be set to 8192 or less for any image with more
 The rest of an iteration of trainval_net.py:207-227 is here too: make_optimizer builds the reference's parameter groups on
 stereo_rcnn_amd.optim.SGD, and train_step runs zero-grad, forward_train, the multi-task loss, backward() and the clipped SGD step
 (csrc/optim.hip: one norm pass over the gradients, one fused update) as one call without a further host read.  After training, an
-inference plan's prepared weights (plan.py, engine.prep_*) are copies made from the parameters as they were: rebuild the plan
-from the updated parameters before running inference.
+inference plan's prepared weights (plan.py, engine.prep_*) are copies made from the parameters as they were: call
+Plan.refresh(model) before running inference -- it overwrites them in place on the device (csrc/prep_weights.hip) and keeps the
+plan's buffers and, where no weight scale moved, its recorded launch programs (trainval_net --val-split does so every epoch).
 
 The data side is stereo_rcnn_amd/datasets/kitti.py (annotations -> roidb, once) and stereo_rcnn_amd/data.py (TrainLoader: PNG
 decode in worker processes, batch assembly in csrc/loader.hip), and stereo_rcnn_amd/trainval_net.py is the reference's training

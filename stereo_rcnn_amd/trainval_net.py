@@ -8,6 +8,10 @@ SGD step) with training.make_optimizer's groups and the six log-variances `uncer
 net_utils.adjust_learning_rate at the decay epochs (:189-191), net_utils.save_checkpoint at each epoch's end (:248-254: 'epoch' is
 the NEXT epoch, 'model', 'optimizer', 'uncert').  Losses are read to the host only every --disp_interval iterations; in between
 nothing waits for the device.  --resume loads model, optimiser state and uncert back and continues at the stored epoch.
+--val-split FILE --val-label-dir DIR [--val-every N] [--val-precision f16x3|f32] (an extension: the reference has none): after
+every N-th epoch the model's inference weights are refreshed in place (plan.Plan.refresh), the split runs through the inference
+pipeline and kitti_eval, <save_dir>/ap_epoch<E>.json is written and the Car Moderate line logged (validation.py); training itself
+is bit-identical with and without it.
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -43,6 +47,12 @@ def parse_args(argv=None):
     p.add_argument('--pre_nms_top_n', default=None, type=int, help='sets cfg.TRAIN.RPN_PRE_NMS_TOP_N')
     p.add_argument('--no_flip', action='store_true', help='do not append the flipped copies (cfg.TRAIN.USE_FLIPPED)')
     p.add_argument('--seed', default=None, type=int, help='default: cfg.RNG_SEED')
+    p.add_argument('--val-split', dest='val_split', default=None,
+                   help='validate on this split (one frame id per line, frames under <kitti-path>/training) after every --val-every-th '
+                        'epoch: <save_dir>/ap_epoch<E>.json and a Car Moderate line in trainlog.txt')
+    p.add_argument('--val-label-dir', dest='val_label_dir', default=None, help='KITTI label_2 directory of the validation frames')
+    p.add_argument('--val-every', dest='val_every', default=1, type=int, help='unit: epoch')
+    p.add_argument('--val-precision', dest='val_precision', choices=['f16x3', 'f32'], default='f16x3')
     return p.parse_args(argv)
 
 
@@ -102,6 +112,13 @@ def main(argv=None):
     loader = data.TrainLoader(roidb, ratio_index, args.batch_size, dev, generator=gen_host, workers=args.num_workers,
                               prefetch=args.prefetch)
     iters_per_epoch = int(train_size / args.batch_size)
+    validate = None
+    if args.val_split:
+        if not args.val_label_dir:
+            raise SystemExit('--val-split needs --val-label-dir')
+        from . import validation              # (only here: a run without --val-split imports none of the inference drivers)
+        validate = validation.Validator(model, args.kitti_path, args.val_split, args.val_label_dir, args.save_dir,
+                                        precision=args.val_precision, device=dev, log=log_string)
     written = []
     try:
         for epoch in range(start_epoch, args.max_epochs + 1):
@@ -126,6 +143,8 @@ def main(argv=None):
             written.append(save_name)
             log_string('save model: {}'.format(save_name))
             log_string('time %.4f' % (time.time() - start))
+            if validate is not None and args.val_every > 0 and epoch % args.val_every == 0:
+                validate(epoch)
     finally:
         loader.close()
         log_info.close()
