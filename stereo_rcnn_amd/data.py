@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine
+from .images import DecodeWorkers, PinnedPairs, read_png_rgb
 from .model.utils.config import cfg
 
 
@@ -79,32 +80,6 @@ def keys_to_words(keys):
     return torch.from_numpy((keys.to(torch.int64).numpy() & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
 
 
-class _Pinned(object):
-    """A ring of page-locked uint8 image pairs the kernel reads where they are; an entry is rewritten only after the event of
-    the batch that last read it."""
-
-    def __init__(self, n):
-        self.bufs = [[None, None, None] for _ in range(n)]       # left, right, event of the last reader
-        self.next = 0
-
-    def take(self):
-        e = self.bufs[self.next]
-        self.next = (self.next + 1) % len(self.bufs)
-        if e[2] is not None:
-            e[2].synchronize()
-            e[2] = None
-        return e
-
-    @staticmethod
-    def put(e, k, arr):
-        arr = np.ascontiguousarray(arr, dtype=np.uint8)
-        if e[k] is None or e[k].numel() < arr.size:
-            e[k] = torch.empty(max(arr.size, 3 * 376 * 1242), dtype=torch.uint8, pin_memory=True)
-        view = e[k][:arr.size].view(*arr.shape)
-        np.copyto(view.numpy(), arr)
-        return view
-
-
 class TrainLoader(object):
     """Iterator over one epoch at a time: `for batch in loader` yields (im_left, im_right, im_info, gt_boxes_left, gt_boxes_right,
     gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes) -- images float32 (B, 3, H, W) and ground truth (B, MAX_NUM_GT_BOXES, 5|5|5|5|6)
@@ -126,7 +101,7 @@ class TrainLoader(object):
         self.offsets = offsets
         self.sampler = BatchSampler(len(roidb), self.batch_size, self.generator)
         self.depth = max(1, self.prefetch)
-        self.ring = _Pinned((2 * self.depth + 2) * self.batch_size)
+        self.ring, self.taken = PinnedPairs((2 * self.depth + 2) * self.batch_size, grow=True), 0
         self.side = torch.cuda.Stream(device=self.device)
         self.workers = self.pool = None
         self.visited = []
@@ -138,8 +113,7 @@ class TrainLoader(object):
     def _start_workers(self):
         if self.n_workers and self.workers is None:
             import concurrent.futures as cf
-            from .test_net import _DecodeWorkers
-            self.workers = _DecodeWorkers(self.n_workers)
+            self.workers = DecodeWorkers(self.n_workers)
             self.pool = cf.ThreadPoolExecutor(max_workers=self.n_workers)
 
     def close(self):
@@ -159,7 +133,6 @@ class TrainLoader(object):
     def _decode(self, entry, slot):
         paths = (entry['img_left'], entry['img_right'])
         if self.workers is None:
-            from .test_net import read_png_rgb
             return [self.ring.put(slot, k, read_png_rgb(p)) for k, p in enumerate(paths)]
         w, arrs = self.workers.decode(paths)          # this thread sleeps on the worker's pipe meanwhile
         try:
@@ -183,7 +156,8 @@ class TrainLoader(object):
                 keys = torch.randint(0, 2 ** 32, (n,), dtype=torch.int64, generator=self.generator)
             assert int(keys.numel()) == n, "one shuffle key per object"
             cursor += 1
-            slot = self.ring.take()
+            slot = self.ring.entry(self.taken)           # waits for the batch that last read this entry, if it is still running
+            self.taken += 1
             job = self.pool.submit(self._decode, e, slot) if self.pool is not None else self._decode(e, slot)
             items.append((idx, e, n, scales_cfg[si], keys_to_words(keys), slot, job))
         return items, cursor

@@ -18,16 +18,11 @@ import os
 
 import numpy as np
 
+from ..images import read_split
 from ..model.utils import kitti_utils
 
 CLASSES = ('__background__', 'Car')
 _CLASS_TO_IND = dict(zip(CLASSES, range(len(CLASSES))))
-
-
-def read_split(path):
-    """The frame ids of a split file, one per line (kitti.py:105-116 splits on newlines; blank lines are passed over here)."""
-    with open(path) as fh:
-        return [ln.strip() for ln in fh.read().split('\n') if ln.strip()]
 
 
 def image_paths(kitti_path, index):

@@ -15,9 +15,9 @@ import time
 import torch
 
 from . import pipeline
-from .model.stereo_rcnn.resnet import resnet
+from .images import read_png_rgb
+from .model.stereo_rcnn.resnet import load_checkpoint, resnet
 from .model.utils import kitti_utils
-from .test_net import read_png_rgb
 
 
 def main(argv=None):
@@ -39,8 +39,7 @@ def main(argv=None):
     dev = torch.device('cuda:0')
     model = resnet(('__background__', 'Car'), 101, pretrained=False)
     model.create_architecture()
-    sd = torch.load(args.checkpoint, map_location='cpu')
-    model.load_state_dict(sd['model'] if 'model' in sd else sd)
+    load_checkpoint(model, args.checkpoint)
     model.cuda()
     model.eval()
     model.precision = args.precision

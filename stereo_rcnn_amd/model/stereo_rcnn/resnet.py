@@ -6,6 +6,7 @@ The modules below exist to reproduce the reference's state_dict keys and shapes
 `load_state_dict(checkpoint['model'])`.  They are never executed: the forward runs in the
 HIP library (see plan.py).
 """
+import torch
 import torch.nn as nn
 
 from ..utils.config import cfg
@@ -81,3 +82,10 @@ class resnet(_StereoRCNN):
         for p in self.parameters():
             p.requires_grad = False
         nn.Module.train(self, False)
+
+
+def load_checkpoint(model, path):
+    """Loads a checkpoint with a 'model' state_dict (reference schema) or a bare state_dict into `model`; returns what the file held."""
+    sd = torch.load(path, map_location='cpu')
+    model.load_state_dict(sd['model'] if 'model' in sd else sd)
+    return sd

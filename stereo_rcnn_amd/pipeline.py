@@ -51,7 +51,7 @@ HOST_SOLVER_THREADS = 0          # srcnn_solve_*_records_host: <= 0 = one thread
 # 8 and first measured with the KITTI loop's 16 PNG decoders as threads of this interpreter -- the loop thread's busy time per pair
 # fell 3.55 -> 2.14 ms and the throughput did not move (configs[3] 138.1 -> 136.7 pairs/s, 123 at six in flight: workers, decoders
 # and loop on one GIL; profiles/flow3d_async_host_r06.txt), so it stayed off.  With the decoders in processes of their own
-# (test_net._DecodeWorkers) the same switch gives configs[3] 155.6-163.4 -> 169.7-170.0 pairs/s on one box and leaves the
+# (images.DecodeWorkers) the same switch gives configs[3] 155.6-163.4 -> 169.7-170.0 pairs/s on one box and leaves the
 # tensor-fed flow where it was (GPU-bound at 5.7 ms per pair: 175.2 vs 175.5) -- profiles/config3_host_side_r06.txt.
 ASYNC_HOST_PHASES = os.environ.get('SRCNN_ASYNC_HOST', '1') != '0'
 # host-side accounting of the record flow (bench.py --config 3): a dict {'solve_s', 'gpu_wait_s'} that step_3d / collect_3d add

@@ -1,8 +1,8 @@
-"""PNG decode worker PROCESS of the KITTI loop (test_net.run_split): run as a script, never imported by the package.
+"""PNG decode worker PROCESS of the KITTI loops (started by images.DecodeWorkers): run as a script, never imported by the package.
 
     python png_worker.py <shared file> <slot> <entry bytes>
 
-Reads one JSON request per line on stdin ({"paths": [left.png, right.png]}), decodes each file exactly as test_net.read_png_rgb does
+Reads one JSON request per line on stdin ({"paths": [left.png, right.png]}), decodes each file exactly as images.read_png_rgb does
 (PIL, RGB, uint8) into its slot of the shared file (slot * 2 entries of `entry bytes`), and answers one JSON line ({"shapes": [[H, W, 3],
 [H, W, 3]]} or {"error": ...}).  Sixteen decoder THREADS inside the loop's process cost the streamed flow 1.1 ms per pair -- not their CPU
 time (21 ms per pair, spread over 16 threads) but their hundreds of GIL hand-overs per image against the loop thread's launches

@@ -12,7 +12,7 @@ import argparse
 import os
 import sys
 
-from . import kitti_eval, test_net
+from . import images, kitti_eval, test_net
 
 
 def main(argv=None):
@@ -33,7 +33,7 @@ def main(argv=None):
     if int(os.environ.get('RANK', 0)) == 0:
         import torch
         device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-        return kitti_eval.evaluate_split(args.label_dir, args.result_dir, test_net.read_split(args.split), device,
+        return kitti_eval.evaluate_split(args.label_dir, args.result_dir, images.read_split(args.split), device,
                                          log=lambda s: print(s, flush=True))
     return None
 

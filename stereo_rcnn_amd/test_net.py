@@ -14,12 +14,12 @@ import argparse
 import os
 import time
 
-import numpy as np
 import torch
 
 from . import engine, pipeline
 from .distributed import shard_indices
-from .model.stereo_rcnn.resnet import resnet
+from .images import PinnedPairs, decode_workers, read_png_rgb, read_split
+from .model.stereo_rcnn.resnet import load_checkpoint, resnet
 from .model.utils import kitti_utils
 from .model.utils.config import cfg
 
@@ -30,110 +30,6 @@ DECODE_PROCESSES = os.environ.get('SRCNN_DECODE_PROCESSES', '1') != '0'
 
 # result files + records on a writer thread (SRCNN_WRITER_THREAD=0: written by the loop thread between two launches)
 WRITER_THREAD = os.environ.get('SRCNN_WRITER_THREAD', '1') != '0'
-
-
-class _DecodeWorkers(object):
-    """`n` png_worker.py processes and the shared file they decode into (one slot of two images per worker).  decode() hands a
-    request to an idle worker and blocks the calling THREAD on its answer (a pipe read: no GIL held), then returns views of the
-    worker's slot and the worker itself -- the caller copies the pixels out (into the page-locked ring) and release()s it."""
-
-    def __init__(self, n, nbytes=3 * 512 * 1408):
-        import mmap
-        import queue
-        import subprocess
-        import sys
-        import tempfile
-        self.n, self.nbytes = n, nbytes
-        base = '/dev/shm' if os.path.isdir('/dev/shm') and os.access('/dev/shm', os.W_OK) else tempfile.gettempdir()
-        fd, self.path = tempfile.mkstemp(prefix='srcnn_png_', dir=base)
-        os.ftruncate(fd, n * 2 * nbytes)
-        self.mm = mmap.mmap(fd, 0)
-        os.close(fd)
-        self.view = np.frombuffer(self.mm, dtype=np.uint8)
-        script = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'png_worker.py')
-        self.procs, self.idle = [], queue.Queue()
-        try:
-            for i in range(n):
-                self.procs.append(subprocess.Popen([sys.executable, script, self.path, str(i), str(nbytes)], stdin=subprocess.PIPE,
-                                                   stdout=subprocess.PIPE, universal_newlines=True, bufsize=1))
-            for i, pr in enumerate(self.procs):
-                if pr.stdout.readline().strip() != 'ready':
-                    raise RuntimeError('PNG decode worker %d did not start (exit code %s)' % (i, pr.poll()))
-                self.idle.put(i)
-        except Exception:
-            self.close()
-            raise
-        os.unlink(self.path)              # every worker has it mapped: the file goes away with the last mapping
-        self.path = None
-
-    def decode(self, paths):
-        import json
-        i = self.idle.get()
-        pr = self.procs[i]
-        try:
-            pr.stdin.write(json.dumps({'paths': list(paths)}) + '\n')
-            pr.stdin.flush()
-            line = pr.stdout.readline()
-            if not line:
-                raise RuntimeError('PNG decode worker %d died (exit code %s)' % (i, pr.poll()))
-            reply = json.loads(line)
-            if 'error' in reply:
-                raise RuntimeError('PNG decode worker: %s' % reply['error'])
-        except Exception:
-            self.idle.put(i)
-            raise
-        base, out = i * 2 * self.nbytes, []
-        for k, shape in enumerate(reply['shapes']):
-            nb = int(np.prod(shape))
-            out.append(self.view[base + k * self.nbytes: base + k * self.nbytes + nb].reshape(shape))
-        return i, out
-
-    def release(self, i):
-        self.idle.put(i)
-
-    def close(self):
-        for pr in self.procs:
-            try:
-                pr.stdin.close()
-            except Exception:
-                pass
-        for pr in self.procs:
-            try:
-                pr.wait(timeout=5)
-            except Exception:
-                pr.kill()
-        self.procs = []
-        if self.path:
-            try:
-                os.unlink(self.path)
-            except OSError:
-                pass
-            self.path = None
-
-
-_decode_workers = {}
-
-
-def decode_workers(n):
-    """The process-wide set of `n` decode workers (started on first use, reused by later splits, stopped at exit)."""
-    w = _decode_workers.get(n)
-    if w is None:
-        import atexit
-        w = _decode_workers[n] = _DecodeWorkers(n)
-        atexit.register(w.close)
-    return w
-
-
-def read_split(path):
-    with open(path) as fh:
-        return [ln.strip() for ln in fh if ln.strip()]
-
-
-def read_png_rgb(path):
-    """uint8 (H, W, 3) RGB.  (The reference reads BGR with cv2 and flips; the device preprocessing takes RGB.)"""
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert('RGB'), dtype=np.uint8)
 
 
 # A/B switch: SRCNN_ZERO_COPY_IMAGES=0 = round 5's path (decoded images copied to the device with hipMemcpyAsync from a pinned pool)
@@ -167,33 +63,6 @@ class _PinnedPool(object):
         return dev_t
 
 
-class _PinnedRing(object):
-    """Page-locked image buffers the DEVICE reads where they are (round 6): the decode thread of frame j copies its two decoded
-    images into ring entry j % n, and the fused preprocessing kernel reads them over the bus -- no hipMemcpy in any stream.  An
-    asynchronous H2D copy per image looked free (0.35 ms of the loop thread per pair) and cost the streamed flow 1.0 ms per pair
-    (profiles/flow3d_input_path_r06.txt: 5.9 ms with device-resident images or zero-copy, 6.9 with two H2D copies per frame, 8.5
-    with the copies on a stream of their own) -- the copies, not their bytes.  Entry j % n is rewritten when frame j + n is
-    decoded, `prefetch` frames before it is consumed; frame j's pair has been collected by then if n >= prefetch + slots + 1."""
-
-    def __init__(self, n, nbytes=3 * 512 * 1408):
-        self.n, self.nbytes = n, nbytes
-        self.bufs = [None] * n
-
-    def put(self, j, left, right):
-        e = self.bufs[j % self.n]
-        if e is None:
-            e = self.bufs[j % self.n] = (torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True),
-                                         torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True))
-        out = []
-        for buf, arr in zip(e, (left, right)):
-            arr = np.ascontiguousarray(arr, dtype=np.uint8)
-            assert arr.nbytes <= self.nbytes, "image larger than the staging ring's entries"
-            view = buf[:arr.nbytes].view(*arr.shape)
-            np.copyto(view.numpy(), arr)
-            out.append(view)
-        return out
-
-
 def run_split(model, kitti_root, ids, result_dir, device, pool=None, read_image=read_png_rgb, log=None, prefetch=4,
               solver='host', slots=4, detect_stream=None, records=None, timers=None):
     """Processes `ids` (already this rank's shard).  Returns (frames, objects written, seconds).
@@ -217,7 +86,9 @@ def run_split(model, kitti_root, ids, result_dir, device, pool=None, read_image=
             timers.setdefault(k, 0.0)
 
     zero_copy = detect_stream is None and solver in ('device', 'host') and ZERO_COPY_IMAGES
-    ring = _PinnedRing(max(1, prefetch) + max(1, slots) + 4) if zero_copy else None
+    # entry j % n is rewritten when frame j + n is decoded, `prefetch` frames before it is consumed; frame j's pair has been
+    # collected by then if n >= prefetch + slots + 1, so the ring's length is the rule and no reader event is ever set
+    ring = PinnedPairs(max(1, prefetch) + max(1, slots) + 4) if zero_copy else None
     # decode in worker processes: the default reader on the zero-copy path (a custom `read_image` runs on the prefetch threads)
     workers = None
     if ring is not None and read_image is read_png_rgb and DECODE_PROCESSES:
@@ -227,20 +98,24 @@ def run_split(model, kitti_root, ids, result_dir, device, pool=None, read_image=
             import warnings
             warnings.warn('PNG decode workers unavailable (%s): decoding on %d threads of this process' % (e, max(1, prefetch)))
 
+    def pin(j, pair):
+        e = ring.entry(j)
+        return [ring.put(e, k, arr) for k, arr in enumerate(pair)]
+
     def load(j, frame):
         td = time.perf_counter()
         paths = (os.path.join(kitti_root, 'image_2', frame + '.png'), os.path.join(kitti_root, 'image_3', frame + '.png'))
         if workers is not None:
-            w, (left, right) = workers.decode(paths)            # this thread sleeps on the worker's pipe meanwhile
+            w, pair = workers.decode(paths)                     # this thread sleeps on the worker's pipe meanwhile
             try:
-                left, right = ring.put(j, left, right)          # out of the worker's slot into the page-locked ring
+                left, right = pin(j, pair)                      # out of the worker's slot into the page-locked ring
             finally:
                 workers.release(w)
         else:
             left, right = read_image(paths[0]), read_image(paths[1])
         calib = kitti_utils.read_obj_calibration(os.path.join(kitti_root, 'calib', frame + '.txt'))
         if ring is not None and workers is None:
-            left, right = ring.put(j, left, right)              # page-locked views the preprocessing kernel reads directly
+            left, right = pin(j, (left, right))                 # page-locked views the preprocessing kernel reads directly
         if timers is not None:
             timers['decode_s'] += time.perf_counter() - td        # (float += under the GIL: good enough for a per-pair average)
         return (left, right, calib)
@@ -355,8 +230,7 @@ def main(argv=None):
     device = torch.device('cuda', local)
     model = resnet(('__background__', 'Car'), 101, pretrained=False)
     model.create_architecture()
-    sd = torch.load(args.checkpoint, map_location='cpu')
-    model.load_state_dict(sd['model'] if 'model' in sd else sd)
+    load_checkpoint(model, args.checkpoint)
     model.cuda()
     model.eval()
     model.precision = args.precision

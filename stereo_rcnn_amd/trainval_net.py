@@ -61,7 +61,7 @@ def main(argv=None):
     args = parse_args(argv)
     from . import data, training
     from .datasets import kitti
-    from .model.stereo_rcnn.resnet import resnet
+    from .model.stereo_rcnn.resnet import load_checkpoint, resnet
     from .model.utils import net_utils
     from .model.utils.config import cfg
 
@@ -90,8 +90,7 @@ def main(argv=None):
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
-        sd = torch.load(args.init, map_location='cpu')
-        model.load_state_dict(sd['model'] if 'model' in sd else sd)
+        load_checkpoint(model, args.init)
     model.to(dev)
     lr = cfg.TRAIN.LEARNING_RATE if args.lr is None else args.lr
     uncert = torch.full((6,), -1.0, dtype=torch.float32, device=dev, requires_grad=True)

@@ -12,14 +12,14 @@ import os
 
 import torch
 
-from . import kitti_eval, test_net
+from . import images, kitti_eval, test_net
 
 
 class Validator(object):
     def __init__(self, model, kitti_path, split, label_dir, save_dir, precision='f16x3', device=None, log=print):
         self.model, self.label_dir, self.save_dir, self.precision, self.log = model, label_dir, save_dir, precision, log
         self.root = os.path.join(kitti_path, 'training')
-        self.ids = test_net.read_split(split)
+        self.ids = images.read_split(split)
         self.device = device
         self.reports = []
 

@@ -21,7 +21,7 @@ import sys
 import numpy as np
 import torch
 
-from . import pipeline, test_net, visualize
+from . import images, pipeline, test_net, visualize
 from .distributed import objects_to_record, shard_indices
 
 
@@ -132,7 +132,7 @@ def main(argv=None):
     args, rest = ap.parse_known_args(argv)
     rest += ['--kitti-root', args.kitti_root, '--split', args.split]          # everything but the two picture options goes to test_net
     rank, world, local = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
-    ids = test_net.read_split(args.split)
+    ids = images.read_split(args.split)
     mine = [ids[i] for i in shard_indices(len(ids), rank, world)]             # test_net.main's own sharding
     with pictures(torch.device('cuda', local), args.vis_dir, mine, args.kitti_root, args.vis_thresh) as writer:
         test_net.main(rest)

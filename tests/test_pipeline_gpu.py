@@ -76,7 +76,7 @@ def test_kitti_split_driver_writes_result_files(dev, tmp_path):
     this rank's shard gets a result file whose lines parse as KITTI detections."""
     from PIL import Image
     from oracle.dense_align import KITTI_DEMO_CALIB as c            # calibration constants only
-    from stereo_rcnn_amd import fixture, pipeline, test_net
+    from stereo_rcnn_amd import fixture, images, pipeline, test_net
     from stereo_rcnn_amd.distributed import shard_indices
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
     root = tmp_path / 'training'
@@ -114,7 +114,7 @@ def test_kitti_split_driver_writes_result_files(dev, tmp_path):
     for f in written:
         assert (tmp_path / 'result2' / 'data' / f).read_text() == (tmp_path / 'result' / 'data' / f).read_text()
     # PNG decode on threads of this process (round 5's form) instead of the worker processes: the same pixels, the same files
-    assert test_net.DECODE_PROCESSES and test_net._decode_workers
+    assert test_net.DECODE_PROCESSES and images._decode_workers
     test_net.DECODE_PROCESSES = False
     try:
         test_net.run_split(m, str(root), ids, str(tmp_path / 'result_threads'), dev)

@@ -136,7 +136,7 @@ s5 = rep(s5, "* 3-D stage (`pipeline.py`)", '''* **More than one convolution per
   streams of `pipeline.detect_3d_stream` + the null stream were nine streams on eight queues, two of the slots' forwards shared one, and the
   3-D flow INSIDE `bench.py` ran at 6.8-7.1 ms per pair where the same flow alone in a process took 5.7-5.9 (bisected with a hook inside
   `bench.py`: fast until the headline streams had been used once; `flow3d_queue_sharing_r06.txt`).  `full_3d_flow` 146.6 -> 176.7 pairs/s.
-* **No `hipMemcpyAsync` in the image path** (round 6; `test_net._PinnedRing`, `plan.set_images`).  Two asynchronous H2D copies of 1.4 MB per
+* **No `hipMemcpyAsync` in the image path** (round 6; `images.PinnedPairs`, `plan.set_images`).  Two asynchronous H2D copies of 1.4 MB per
   frame cost the streamed flow 1.0 ms per pair -- 6.9 ms against 5.9 with device-resident images; 8.5 with the copies on a stream of their
   own -- although issuing them took the loop thread 0.35 ms: the copies, not their bytes (`flow3d_input_path_r06.txt`).  The PNG decoder
   threads now write into a ring of page-locked buffers and the fused preprocessing kernel reads them over the bus where they are (5.94 ms):
@@ -145,7 +145,7 @@ s5 = rep(s5, "* 3-D stage (`pipeline.py`)", '''* **More than one convolution per
 * **One interpreter, one job** (round 6, second pass; `config3_host_side_r06.txt`).  The KITTI loop still lost 1.2 ms per pair against the
   same flow fed tensors, and taking the PNG decode out (images served from memory) gave it back: 16 decoder THREADS are not short of cores
   (21 ms of CPU per pair), they are hundreds of GIL hand-overs per image against a loop thread that makes ~300 ctypes launches per pair.
-  The decoders are worker PROCESSES now (`stereo_rcnn_amd/png_worker.py`: numpy + PIL only; each decodes into its slot of a shared file, the
+  The decoders are worker PROCESSES now (`images.DecodeWorkers`, `stereo_rcnn_amd/png_worker.py`: numpy + PIL only; each decodes into its slot of a shared file, the
   prefetch thread that sleeps on its pipe copies the pixels into the page-locked ring): loop thread busy 2.97 -> 2.36 ms.  With the
   interpreter to themselves the two switches that had bought nothing earlier in the round pay: result files + records on a writer thread
   (144-151 -> 154-156 pairs/s) and the host phases of every pair in flight on a worker thread (156-163 -> 170; default on now, the
