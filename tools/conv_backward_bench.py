@@ -13,14 +13,8 @@ and a smooth conv, RPN_Conv and the 24-channel RPN head on P2, RCNN_top and the 
   * fwd   : the exact-fp32 forward (srcnn_conv2d, precision 0, heuristic plan) of the same layer, the second yardstick.
 FLOPs: 2 M N K for the forward, twice that for the backward (dgrad + wgrad), whatever zeros a stride multiplies.
 One process, 10 untimed runs of each first; hip and torch ALTERNATE; every run is timed with device events; medians of --reps.
-The parent runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
-import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+Runner and timer: tools/benchlib.py."""
+import benchlib
 
 # name, B, H, W, Cin, Cout, k, stride, pad
 LAYERS = [
@@ -44,12 +38,9 @@ LAYERS = [
 
 
 def child(reps):
-    import numpy as np
     import torch
-    from stereo_rcnn_amd import _lib, engine
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    from stereo_rcnn_amd import engine
+    dev = benchlib.device()
     aten = torch.ops.aten
     print('%-30s %9s %6s %7s | %9s %7s | %9s %7s | %9s %7s' % ('layer', 'M', 'N', 'K', 'hip us', 'TF/s', 'torch us', 'TF/s', 'hip/torch', 'fwd TF/s'))
     for name, B, H, W, cin, cout, k, s, p in LAYERS:
@@ -82,17 +73,8 @@ def child(reps):
         agree = [float((a - b).abs().max() / b.abs().max()) for a, b in
                  ((out['dx'].permute(0, 3, 1, 2), ref[0]), (out['dw'].permute(0, 3, 1, 2), ref[1]), (out['db'], ref[2]))]
         assert max(agree) < 1e-3, (name, agree)            # the two compute the same thing (the tests hold the real bound)
-        times = {'hip': [], 'torch': [], 'fwd': []}
-        for rep in range(reps + 10):
-            for key, fn in (('hip', hip), ('torch', eager), ('fwd', fwd)):          # alternating
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                if rep >= 10:
-                    times[key].append(e0.elapsed_time(e1) * 1e3)
-        med = {k_: float(np.median(v)) for k_, v in times.items()}
+        times = benchlib.alternating([('hip', hip), ('torch', eager), ('fwd', fwd)], reps, warmup=10)
+        med = {k_: benchlib.stats(v)[0] * 1e3 for k_, v in times.items()}
         M, K = B * OH * OW, k * k * cin
         fl = 2.0 * M * cout * K
         print('%-30s %9d %6d %7d | %9.1f %7.1f | %9.1f %7.1f | %9.2f %7.1f'
@@ -103,23 +85,8 @@ def child(reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'conv_backward_bench.txt'))
-    ap.add_argument('--reps', type=int, default=50)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=420)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/conv_backward_bench.py --reps %d   (see the tool for what each column measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='conv_backward_bench.txt', reps=50, timeout=420,
+                  header='# python tools/conv_backward_bench.py --reps %(reps)d   (see the tool for what each column measures)')
 
 
 if __name__ == '__main__':

@@ -17,16 +17,12 @@
 3. training.train_step on the same box: R-101, one 600 x 1987 pair from that loader, cfg.TRAIN.RPN_PRE_NMS_TOP_N = 8192, 2 untimed
    and 5 timed steps, host clock around steps that end in a synchronise.  The last line says whether the loader with a no-op
    consumer outruns it.
-The parent runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
+Runner and timer: tools/benchlib.py."""
 import os
-import subprocess
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 HBM_COPY_CEILING_TBS = 6.3
 H, W, TARGET = 375, 1242, 600
@@ -90,22 +86,20 @@ def eager_batch(pairs, flipped, scale, table, slots, keys, K):
     return blobs, outs
 
 
-def child(reps, pairs_n):
+def child(reps, pairs):
     import numpy as np
     import torch
     from stereo_rcnn_amd import _lib, data, engine, fixture, training
     from stereo_rcnn_amd.datasets import kitti
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
     from stereo_rcnn_amd.model.utils.config import cfg
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     K = int(cfg.MAX_NUM_GT_BOXES)
     with tempfile.TemporaryDirectory() as root:
-        split = write_dataset(root, pairs_n)
+        split = write_dataset(root, pairs)
         roidb, _, ratio_index = kitti.build_roidb(root, split)
         print('%d synthetic %d x %d PNG pairs, %d roidb entries (flipped copies included), %d objects each'
-              % (pairs_n, H, W, len(roidb), len(roidb[0]['boxes_left'])))
+              % (pairs, H, W, len(roidb), len(roidb[0]['boxes_left'])))
         table_np, off = data.pack_gt_table(roidb)
         table = torch.from_numpy(table_np).to(dev)
         scale = float(TARGET) / H
@@ -123,21 +117,11 @@ def child(reps, pairs_n):
             routes = {'fused': lambda: (engine.preprocess_train(imgs, flipped, [scale] * B, 2484), engine.gt_batch(table, slots, keys, K)),
                       'eager': lambda: eager_batch(imgs, flipped, scale, table, slots, keys, K)}
             nbytes = 2 * B * (3 * 600 * 1987 * 4 + H * W * 3) + sum(n) * _lib.GT_COLS * 4 + B * K * 26 * 4
-            times = {k: [] for k in routes}
-            for rep in range(reps + 5):
-                for k, fn in routes.items():
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    fn()
-                    e1.record()
-                    e1.synchronize()
-                    if rep >= 5:
-                        times[k].append(e0.elapsed_time(e1) * 1e3)
+            times = benchlib.alternating(list(routes.items()), reps, warmup=5, sync_before=True)
             for k in routes:
-                med = float(np.median(times[k]))
+                med, lo, hi = (t * 1e3 for t in benchlib.stats(times[k]))
                 gbs = nbytes / (med * 1e-6) / 1e9
-                print('%-3d %-6s %10.1f %10.1f %10.1f %14d %8.0f %.1f %%' % (B, k, med, min(times[k]), max(times[k]), nbytes, gbs,
+                print('%-3d %-6s %10.1f %10.1f %10.1f %14d %8.0f %.1f %%' % (B, k, med, lo, hi, nbytes, gbs,
                                                                             100.0 * gbs / (HBM_COPY_CEILING_TBS * 1e3)))
             print('    least time for those bytes at the copy ceiling: %.1f us' % (nbytes / (HBM_COPY_CEILING_TBS * 1e12) * 1e6))
 
@@ -189,24 +173,8 @@ def child(reps, pairs_n):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'loader_bench.txt'))
-    ap.add_argument('--reps', type=int, default=40)
-    ap.add_argument('--pairs', type=int, default=32)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=420)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps, a.pairs)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps),
-                        '--pairs', str(a.pairs)], stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/loader_bench.py --reps %d --pairs %d   (see the tool for what each line measures)\n' % (a.reps, a.pairs))
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='loader_bench.txt', reps=40, timeout=420, extra=[('--pairs', dict(type=int, default=32))],
+                  header='# python tools/loader_bench.py --reps %(reps)d --pairs %(pairs)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

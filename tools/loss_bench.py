@@ -12,14 +12,8 @@ the gradients of the prediction tensors (upstream gradients on the device).
     three `float(torch.sum(w)) < 1` reads that make the host wait.
 One process, warm (10 untimed runs of each); the two versions ALTERNATE, every run is timed with device events and ends in a
 synchronise; medians of --reps runs are reported, with min and max.  The two versions' losses are compared before timing.
-The parent process runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
-import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+Runner and timer: tools/benchlib.py."""
+import benchlib
 
 MAPS = [(150, 497), (75, 249), (38, 125), (19, 63), (10, 32)]
 ANCHORS = 3 * sum(h * w for h, w in MAPS)
@@ -111,13 +105,9 @@ def make_inputs(dev, seed=0):
 
 
 def child(reps):
-    import numpy as np
     import torch
-    from stereo_rcnn_amd import _lib
     from stereo_rcnn_amd.model.stereo_rcnn import losses
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     rpn, rcnn = make_inputs(dev)
     cases = [
         ('rpn_losses, %d anchors (1 image), 256 labelled' % ANCHORS, rpn, ('cls', 'box'), losses.rpn_losses, eager_rpn),
@@ -143,42 +133,15 @@ def child(reps):
         print('  losses fused %s | eager %s' % (' '.join('%.6f' % float(v) for v in a), ' '.join('%.6f' % float(v) for v in b)))
         print('  largest |gradient difference| / largest |eager gradient|: %s'
               % ' '.join('%.1e' % (float((x.grad - y.grad).abs().max()) / max(float(y.grad.abs().max()), 1e-30)) for x, y in zip(la, lb)))
-        versions = [('fused', fused_fn), ('eager', eager_fn)]
-        times = {name: [] for name, _ in versions}
-        for rep in range(reps + 10):
-            for name, fn in versions:                                               # alternating
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                step(fn)
-                e1.record()
-                e1.synchronize()
-                if rep >= 10:                                                       # warm
-                    times[name].append(e0.elapsed_time(e1))
-        med = {k: float(np.median(v)) for k, v in times.items()}
-        for name, _ in versions:
-            print('  %s forward + backward: median %.3f ms (min %.3f, max %.3f, %d runs)'
-                  % (name, med[name], min(times[name]), max(times[name]), reps))
-        print('  fused / eager = %.2f' % (med['fused'] / med['eager']))
+        times = benchlib.alternating([('fused', lambda: step(fused_fn)), ('eager', lambda: step(eager_fn))], reps, warmup=10)
+        for name, t in times.items():
+            print('  %s forward + backward: median %.3f ms (min %.3f, max %.3f, %d runs)' % ((name,) + benchlib.stats(t) + (reps,)))
+        print('  fused / eager = %.2f' % (benchlib.stats(times['fused'])[0] / benchlib.stats(times['eager'])[0]))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'loss_bench.txt'))
-    ap.add_argument('--reps', type=int, default=60)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=300)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/loss_bench.py --reps %d   (see the tool for what each line measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='loss_bench.txt', reps=60, timeout=300,
+                  header='# python tools/loss_bench.py --reps %(reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

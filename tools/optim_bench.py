@@ -17,15 +17,8 @@ weight decay), fused = 24 N (norm: read g 4; step: read p, g, m, write p, m 20).
 the 6.3 TB/s copy ceiling of the MI355X (achievable of 8 TB/s HBM: the peak stereo_rcnn_amd/layer_table.py uses).
 One process, warm (5 untimed runs of each); the versions ALTERNATE, every run is timed with device events around the whole call
 and ends in a synchronise; medians of --reps runs with min and max.  The fused and eager parameters after the same three steps
-are compared before timing.  The parent process runs the measurement in a child under a time limit of its own and stops at a
-non-zero exit."""
-import argparse
-import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+are compared before timing.  Runner and timer: tools/benchlib.py."""
+import benchlib
 
 CLIP = 10.0
 HBM_COPY_CEILING_TBS = 6.3
@@ -68,13 +61,10 @@ def groups_of(names, tensors, uncert):
 
 
 def child(reps):
-    import numpy as np
     import torch
-    from stereo_rcnn_amd import _lib, optim
+    from stereo_rcnn_amd import optim
     from stereo_rcnn_amd.model.utils.config import cfg
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     shapes = r101_shapes()
     names = [k for k, _ in shapes]
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -126,47 +116,21 @@ def child(reps):
         worst = max(float((a.detach() - b.detach()).abs().max() / b.detach().abs().max()) for a, b in zip(state['fused'][0], state[other][0]))
         print('after three steps, fused against %s: largest |parameter difference| / largest |parameter| of a tensor: %.2e' % (other, worst))
 
-    times = {k: [] for k in state}
-    warm = 5
-    for rep in range(reps + warm):
-        for kind in state:                                  # alternating
-            set_grads(kind)
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            run(kind)
-            e1.record()
-            e1.synchronize()
-            if rep >= warm:
-                times[kind].append(e0.elapsed_time(e1) * 1e3)
+    times = benchlib.alternating([(kind, lambda kind=kind: run(kind)) for kind in state], reps, warmup=5, before=set_grads, sync_before=True)
+    us = {k: tuple(t * 1e3 for t in benchlib.stats(v)) for k, v in times.items()}
     nbytes = {'eager': 56 * n_decay + 44 * (n_model - n_decay), 'foreach': 56 * n_decay + 44 * (n_model - n_decay), 'fused': 24 * n_model}
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    med = {k: v[0] for k, v in us.items()}
     print('%-8s %12s %12s %12s %14s %10s %s' % ('version', 'median us', 'min us', 'max us', 'bytes counted', 'GB/s', 'share of the %.1f TB/s copy ceiling' % HBM_COPY_CEILING_TBS))
     for k in state:
         gbs = nbytes[k] / (med[k] * 1e-6) / 1e9
-        print('%-8s %12.1f %12.1f %12.1f %14d %10.0f %.1f %%' % (k, med[k], min(times[k]), max(times[k]), nbytes[k], gbs, 100.0 * gbs / (HBM_COPY_CEILING_TBS * 1e3)))
+        print('%-8s %12.1f %12.1f %12.1f %14d %10.0f %.1f %%' % ((k,) + us[k] + (nbytes[k], gbs, 100.0 * gbs / (HBM_COPY_CEILING_TBS * 1e3))))
     print('fused / eager = %.3f, fused / foreach = %.3f (%d runs each)' % (med['fused'] / med['eager'], med['fused'] / med['foreach'], reps))
     print('least time for the fused bytes at the copy ceiling: %.1f us' % (nbytes['fused'] / (HBM_COPY_CEILING_TBS * 1e12) * 1e6))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'optim_bench.txt'))
-    ap.add_argument('--reps', type=int, default=40)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=300)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/optim_bench.py --reps %d   (see the tool for what each line measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='optim_bench.txt', reps=40, timeout=300,
+                  header='# python tools/optim_bench.py --reps %(reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

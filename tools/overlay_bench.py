@@ -14,16 +14,11 @@ first, medians of --reps runs with min and max:
 Bytes the device route has to move: the two images read (2 x 375 x 1242 x 3) + the points read (120 000 x 16) + the plane
 written and read (2 x 750 x 428) + the panel written (750 x 1670 x 3); GB/s = those bytes over the median, beside the 6.3 TB/s
 copy ceiling (layer_table.py's peak).  No ratio is claimed in advance: the file records what was measured.
-The parent runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
+Runner and timer: tools/benchlib.py."""
 import math
-import os
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 HBM_COPY_CEILING_TBS = 6.3
 H, W, OBJECTS, POINTS, MAX_DET = 375, 1242, 40, 120000, 300
@@ -96,9 +91,7 @@ def child(reps):
     import numpy as np
     import torch
     from stereo_rcnn_amd import _lib, engine, fixture
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     print('device: %s' % torch.cuda.get_device_name(0))
     left_np, right_np = fixture.synthetic_pair(7, H, W)
     rec_np = make_record(np)
@@ -115,31 +108,17 @@ def child(reps):
         engine.bev_lidar(pts, velo, H, out=plane)
         engine.render_overlay(left, right, rec, P2, 0.7, plane, out=panel)
 
-    def device_timed(fn):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3
-
-    def host_timed():
+    def host_clock(fn, inner, sync_before):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        host_panel(np, left.cpu().numpy(), right.cpu().numpy(), rec_np, pts_np)
-        return (time.perf_counter() - t0) * 1e6
+        fn()
+        return (time.perf_counter() - t0) * 1e3
 
-    routes = {'device': lambda: device_timed(device_route),
-              'lidar': lambda: device_timed(lambda: engine.bev_lidar(pts, velo, H, out=plane)),
-              'render': lambda: device_timed(lambda: engine.render_overlay(left, right, rec, P2, 0.7, plane, out=panel)),
-              'host': host_timed}
-    times = {k: [] for k in routes}
-    for rep in range(reps + 5):
-        for k, fn in routes.items():
-            t = fn()
-            if rep >= 5:
-                times[k].append(t)
+    routes = [('device', device_route),
+              ('lidar', lambda: engine.bev_lidar(pts, velo, H, out=plane)),
+              ('render', lambda: engine.render_overlay(left, right, rec, P2, 0.7, plane, out=panel)),
+              ('host', lambda: host_panel(np, left.cpu().numpy(), right.cpu().numpy(), rec_np, pts_np), host_clock)]
+    times = {k: [t * 1e3 for t in v] for k, v in benchlib.alternating(routes, reps, warmup=5, sync_before=True).items()}      # us
     got, want = panel.cpu().numpy(), host_panel(np, left_np, right_np, rec_np, pts_np)
     print('%d x %d pair, %d aligned objects of max_det %d (%d segment slots), %d lidar points, panel %d x %d'
           % (H, W, OBJECTS, MAX_DET, MAX_DET * _lib.OVERLAY_SLOTS_PER_ROW, POINTS, got.shape[0], got.shape[1]))
@@ -152,7 +131,7 @@ def child(reps):
     print('\nus per call (%d runs each, alternating; device routes between device events, host route on the host clock)' % reps)
     print('%-7s %10s %10s %10s %14s %8s %s' % ('route', 'median', 'min', 'max', 'bytes counted', 'GB/s',
                                                 'share of the %.1f TB/s copy ceiling' % HBM_COPY_CEILING_TBS))
-    for k in routes:
+    for k in times:
         med = float(np.median(times[k]))
         if k in nbytes:
             gbs = nbytes[k] / (med * 1e-6) / 1e9
@@ -165,23 +144,8 @@ def child(reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'overlay_bench.txt'))
-    ap.add_argument('--reps', type=int, default=40)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=240)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/overlay_bench.py --reps %d   (see the tool for what each line measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='overlay_bench.txt', reps=40, timeout=240,
+                  header='# python tools/overlay_bench.py --reps %(reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

@@ -7,29 +7,22 @@
 Whole calls, wall clock around a device synchronisation AND between device events, the sides alternating; the parameters move by a
 factor of 1 + 1e-4 before every measurement so that each side sees new values (no layer's scale crosses a power of two: the
 recorded program survives the refresh; the first run of (b) still re-calibrates the activation scales, as (a)'s does).
+Every call is timed, the first included, so there is no warm-up to discard.  Runner and device-event window: tools/benchlib.py.
 
     python tools/refresh_bench.py [--reps 3] [--out profiles/refresh_bench.txt]
 """
-import argparse
-import os
-import sys
 import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=3)
-    ap.add_argument('--out', default=None)
-    args = ap.parse_args(argv)
-    from stereo_rcnn_amd import _lib, engine
+def child(reps):
+    from stereo_rcnn_amd import engine
     from stereo_rcnn_amd.model.stereo_rcnn.plan import Plan, Weights
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
-    _lib.lib()
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     torch.manual_seed(3)
     model = resnet(('__background__', 'Car'), 101, pretrained=False)
     model.create_architecture()
@@ -45,13 +38,10 @@ def main(argv=None):
 
     def timed(fn):
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
-        e0.record()
-        fn()
-        e1.record()
+        devt = benchlib.window(fn)
         torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
+        return (time.perf_counter() - t0) * 1e3, devt
 
     def move():
         with torch.no_grad():
@@ -70,7 +60,7 @@ def main(argv=None):
     nbytes = elems * 8 + split * 4                    # float32 in, float32 out; hi and lo out
     rows = {'a': [], 'b': [], 'c': []}
     reports = []
-    for _ in range(args.reps):
+    for _ in range(reps):
         move()
         rows['a'].append(timed(lambda: first_run(Plan(Weights(model.state_dict(), dev), 1, H, W))))
         move()
@@ -82,7 +72,7 @@ def main(argv=None):
         rows['c'].append(timed(lambda: engine.prep_weights_into(specs)))
     med = lambda v: sorted(v)[len(v) // 2]
     lines = ['refresh_bench: R-101, 1 x 600 x 1987 pair, f16x3 engine with recorded program, %s, %d repetitions, sides alternating'
-             % (torch.cuda.get_device_name(0), args.reps),
+             % (torch.cuda.get_device_name(0), reps),
              'regime: one process, one stream, nothing else in flight; whole calls; wall = host clock around a device sync, dev = device events',
              '%d prepared layers, %.1f M weight elements, %.1f M of them split to hi / lo' % (len(specs), elems / 1e6, split / 1e6)]
     for key, what in (('a', 'rebuild: Weights + Plan + first run'), ('b', 'refresh: Plan.refresh + first run'), ('c', 'srcnn_prep_weights alone')):
@@ -92,12 +82,12 @@ def main(argv=None):
     lines.append('(c) moves %.1f MB compulsory -> %.0f GB/s = %.1f %% of the 6.3 TB/s copy ceiling' % (nbytes / 1e6, nbytes / t / 1e9, nbytes / t / 6.3e12 * 100))
     lines.append('refresh reports: %d scale changes, programs dropped in %d of %d' % (sum(len(r['scale_changed']) for r in reports),
                                                                                    sum(r['programs_dropped'] for r in reports), len(reports)))
-    text = '\n'.join(lines)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as fh:
-            fh.write(text + '\n')
+    print('\n'.join(lines))
+
+
+def main():
+    # the time limit: a run with the default arguments took 7 s on a warm box; the room is for a first run (train_step_bench's took six times as long)
+    benchlib.main(__file__, child, out=None, reps=3, timeout=300, header=None)
 
 
 if __name__ == '__main__':

@@ -10,15 +10,10 @@ every run is timed with HIP events; medians are reported.
     rois PLUS the hipMemsetAsync of the gradient maps it accumulates into.  It is handed the lattice gradient directly (the
     avg_pool2d backward in front of it is not charged to it);
   * compulsory bytes = gradient maps written once + grad_out read once, over the product's time.
-The parent process runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
+Runner and timer: tools/benchlib.py."""
 import ctypes
-import os
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib
 
 MAPS = [(150, 497), (75, 249), (38, 125), (19, 63)]
 IM_H, IM_W, C, N = 600.0, 1987.0, 256, 512
@@ -51,8 +46,8 @@ def child(reps):
     import torch
     from oracle import ref_ops
     from stereo_rcnn_amd import _lib
+    dev = benchlib.device()
     L = _lib.lib()
-    dev = torch.device('cuda:0')
     have_ref = ref_ops.available('fma')
     if have_ref:
         RL = ref_ops.lib('fma')
@@ -85,18 +80,8 @@ def child(reps):
                 RL.ROIAlignBackwardLaucher(ltop[l].data_ptr(), float(np.float32(h / IM_H)), 1, len(sel[l]), h, w, C, A + 1, A + 1,
                                            lrois[l].data_ptr(), rgrads[l].data_ptr(), ctypes.c_void_p(stream))
 
-        versions = [('product', product)] + ([('reference', reference)] if have_ref else [])
-        times = {name: [] for name, _ in versions}
-        for rep in range(reps + 5):
-            for name, fn in versions:                                                # alternating
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                if rep >= 5:                                                         # warm
-                    times[name].append(e0.elapsed_time(e1))
-        med = {k: float(np.median(v)) for k, v in times.items()}
+        times = benchlib.alternating([('product', product)] + ([('reference', reference)] if have_ref else []), reps, warmup=5)
+        med = {k: benchlib.stats(v)[0] for k, v in times.items()}
         nbytes = 4.0 * (sum(h * w for h, w in MAPS) * C + N * A * A * C)
         tbps = nbytes / (med['product'] * 1e-3) / 1e12
         print('A=%d fused NHWC backward (srcnn_pyramid_roi_align_backward): median %.3f ms (min %.3f, max %.3f, %d runs)'
@@ -113,22 +98,8 @@ def child(reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'roi_align_backward.txt'))
-    ap.add_argument('--reps', type=int, default=30)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=300)
-    a = ap.parse_args()
-    if a.child:
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    with open(a.out, 'w') as f:
-        f.write('# python tools/roi_align_backward_bench.py --reps %d   (see the tool for what each line measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='roi_align_backward.txt', reps=30, timeout=300,
+                  header='# python tools/roi_align_backward_bench.py --reps %(reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

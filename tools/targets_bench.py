@@ -14,14 +14,8 @@ R = 2000 rois + K = 30, 512 rois per image, foreground fraction 0.25; both at B 
             Python loop over every foreground roi (:92-100) is NOT reproduced (vectorised here, which favours the eager side).
 One process, warm (5 untimed runs of each); the two versions ALTERNATE, every run is timed with device events and ends in a
 synchronise; medians of --reps runs, with min and max.  The two versions' labels are compared before timing.
-The parent process runs the measurement in a child under a time limit of its own and stops at a non-zero exit."""
-import argparse
-import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+Runner and timer: tools/benchlib.py."""
+import benchlib
 
 MAPS = [(94, 311), (47, 156), (24, 78), (12, 39), (6, 20)]
 IM_H, IM_W, K, REAL, R = 375, 1242, 30, 8, 2000
@@ -176,13 +170,12 @@ def make_inputs(B, dev, seed=0):
 
 
 def child(reps):
+    global torch                                    # (the module's functions use it; the parent process does not load it)
     import numpy as np
-    from stereo_rcnn_amd import _lib
+    import torch
     from stereo_rcnn_amd.model.rpn import anchor_target_layer as atl, proposal_target_layer as ptl
     from stereo_rcnn_amd.model.utils.config import cfg
-    _lib.lib()
-    assert torch.cuda.is_available(), 'the measurement needs the GPU: no fallback'
-    dev = torch.device('cuda:0')
+    dev = benchlib.device()
     anchors = atl.pyramid_anchors(MAPS, dev)
     N = anchors.shape[0]
     batch, num_fg = cfg.TRAIN.RPN_BATCHSIZE, int(cfg.TRAIN.RPN_FG_FRACTION * cfg.TRAIN.RPN_BATCHSIZE)
@@ -208,43 +201,15 @@ def child(reps):
             print('  labels equal: %s   (foreground %d, background / other %d)'
                   % (bool(torch.equal(la, lb)), int((la > 0).sum()), int((la == 0).sum())))
             assert torch.equal(la, lb), 'the two versions disagree'
-            versions = [('hip', hip_fn), ('eager', eager_fn)]
-            times = {name: [] for name, _ in versions}
-            for rep in range(reps + 5):
-                for name, fn in versions:                                               # alternating
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    fn()
-                    e1.record()
-                    e1.synchronize()
-                    if rep >= 5:                                                        # warm
-                        times[name].append(e0.elapsed_time(e1))
-            med = {k_: float(np.median(v)) for k_, v in times.items()}
-            for name, _ in versions:
-                print('  %s: median %.3f ms (min %.3f, max %.3f, %d runs)' % (name, med[name], min(times[name]), max(times[name]), reps))
-            print('  hip / eager = %.3f' % (med['hip'] / med['eager']))
+            times = benchlib.alternating([('hip', hip_fn), ('eager', eager_fn)], reps, warmup=5)
+            for name, t in times.items():
+                print('  %s: median %.3f ms (min %.3f, max %.3f, %d runs)' % ((name,) + benchlib.stats(t) + (reps,)))
+            print('  hip / eager = %.3f' % (benchlib.stats(times['hip'])[0] / benchlib.stats(times['eager'])[0]))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'targets_bench.txt'))
-    ap.add_argument('--reps', type=int, default=40)
-    ap.add_argument('--child', action='store_true')
-    ap.add_argument('--timeout', type=int, default=300)
-    a = ap.parse_args()
-    if a.child:
-        global torch
-        import torch
-        return child(a.reps)
-    r = subprocess.run(['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--child', '--reps', str(a.reps)],
-                       stdout=subprocess.PIPE, universal_newlines=True, cwd=ROOT)      # (the child's stderr passes through: only results go to the profile)
-    sys.stdout.write(r.stdout)
-    if r.returncode != 0:
-        sys.exit(r.returncode)                  # nothing further is started on the GPU, and no profile is written
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write('# python tools/targets_bench.py --reps %d   (see the tool for what each line measures)\n' % a.reps)
-        f.write(r.stdout)
+    benchlib.main(__file__, child, out='targets_bench.txt', reps=40, timeout=300,
+                  header='# python tools/targets_bench.py --reps %(reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':

@@ -15,55 +15,19 @@
 Method (measuring-on-mi355x): warm-up first; the two sides ALTERNATE inside one loop; a timed window is `inner` back-to-back
 launches between two device events, `inner` chosen so that a window lasts milliseconds, not microseconds; the median, minimum
 and maximum of --reps windows are reported per launch.  The clocks rocm-smi shows are noted before and after.  No speed target.
+Runner and timer: tools/benchlib.py.
 
     python tools/train_step_bench.py [--reps 30] [--step-reps 10] [--skip-step] [--out profiles/train_step_bench.txt]
 """
-import argparse
-import os
-import statistics
-import subprocess
-import sys
-
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import benchlib
 
 
-def window(fn, inner):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(inner):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / inner
-
-
-def alternating(versions, reps, inner, warmup=3):
-    """versions: [(name, fn)] -> {name: (median, min, max)} ms per call; the versions take turns inside one loop."""
-    for _ in range(warmup):
-        for _, fn in versions:
-            window(fn, inner)
-    times = {name: [] for name, _ in versions}
-    for _ in range(reps):
-        for name, fn in versions:
-            times[name].append(window(fn, inner))
-    return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
-
-
-def clocks():
-    try:
-        txt = subprocess.run(['rocm-smi', '--showclocks'], capture_output=True, text=True, timeout=20).stdout
-        return ' | '.join(ln.strip() for ln in txt.splitlines() if 'sclk' in ln or 'mclk' in ln)[:400] or 'rocm-smi printed no clocks'
-    except Exception as e:                                                        # the tool is optional
-        return 'clocks not read (%s)' % type(e).__name__
-
-
-def _row(lines, name, shape, inner, r):
-    h, e = r['hip'], r['eager']
+def _row(lines, name, shape, inner, reps, hip, eager):
+    t = benchlib.alternating([('hip', hip), ('eager', eager)], reps, warmup=3, inner=inner)
+    h, e = benchlib.stats(t['hip']), benchlib.stats(t['eager'])
     lines.append('%-34s %-30s %5d   %8.4f %8.4f %8.4f   %8.4f %8.4f %8.4f   %5.2f'
                  % (name, shape, inner, h[0], h[1], h[2], e[0], e[1], e[2], e[0] / h[0]))
 
@@ -79,8 +43,7 @@ def kernels(dev, reps, lines):
         g = dy.permute(0, 3, 1, 2).contiguous()
         hip = lambda: _lib.check(L.srcnn_upsample_add_backward(dy.data_ptr(), B, H, W, C, d_top.data_ptr(), TH, TW, _lib.stream()))
         eager = lambda: torch.ops.aten.upsample_bilinear2d_backward(g, [H, W], [B, C, TH, TW], True, None, None)
-        _row(lines, 'srcnn_upsample_add_backward', '(%d,%d)->(%d,%d) x %d x %d' % (TH, TW, H, W, B, C), inner,
-             alternating([('hip', hip), ('eager', eager)], reps, inner))
+        _row(lines, 'srcnn_upsample_add_backward', '(%d,%d)->(%d,%d) x %d x %d' % (TH, TW, H, W, B, C), inner, reps, hip, eager)
     B, H, W, C = 2, 19, 63, 256
     dy, dx = torch.randn(B, 10, 32, C, device=dev), torch.empty(B, H, W, C, device=dev)
     hip = lambda: _lib.check(L.srcnn_subsample2_backward(dy.data_ptr(), B, 10, 32, C, dx.data_ptr(), H, W, _lib.stream()))
@@ -88,7 +51,7 @@ def kernels(dev, reps, lines):
     def eager_sub():
         z = torch.zeros(B, H, W, C, device=dev)
         z[:, ::2, ::2] = dy
-    _row(lines, 'srcnn_subsample2_backward', '(%d,%d,%d,%d)' % (B, H, W, C), 400, alternating([('hip', hip), ('eager', eager_sub)], reps, 400))
+    _row(lines, 'srcnn_subsample2_backward', '(%d,%d,%d,%d)' % (B, H, W, C), 400, reps, hip, eager_sub)
     for M, inner in ((128, 100), (512, 30)):
         x = torch.randn(M, 14, 14, 1024, device=dev)
         for inverse in (False, True):
@@ -98,8 +61,7 @@ def kernels(dev, reps, lines):
                 eager = lambda: src.reshape(M, 14, 2, 14, 2, 256).permute(0, 1, 3, 2, 4, 5).contiguous()
             else:
                 eager = lambda: src.reshape(M, 14, 14, 2, 2, 256).permute(0, 1, 3, 2, 4, 5).contiguous()
-            _row(lines, 'srcnn_pixel_shuffle2 inverse=%d' % inverse, '(%d,14,14,4x256)' % M, inner,
-                 alternating([('hip', hip), ('eager', eager)], reps, inner))
+            _row(lines, 'srcnn_pixel_shuffle2 inverse=%d' % inverse, '(%d,14,14,4x256)' % M, inner, reps, hip, eager)
 
 
 # ---------------------------------------------------------------------------------------- the same graph from eager torch ops
@@ -256,7 +218,7 @@ def step(dev, reps, lines):
     eager()
     torch.cuda.synchronize()
     mem_e = torch.cuda.max_memory_allocated() / 2.0 ** 30
-    r = alternating([('hip', product), ('eager', eager)], reps, 1, warmup=2)
+    r = {k: benchlib.stats(v) for k, v in benchlib.alternating([('hip', product), ('eager', eager)], reps, warmup=2).items()}
     lines.append('forward + backward of the training step, ResNet-101, 600 x 1987, B = 1, %d alternating runs, ms: median (min, max)' % reps)
     lines.append('  forward_train (exact-fp32 engine, target and proposal layers included): %.1f (%.1f, %.1f); peak memory %.2f GiB'
                  % (r['hip'] + (mem_p,)))
@@ -264,26 +226,23 @@ def step(dev, reps, lines):
                  % (r['eager'] + (mem_e,)))
 
 
+def child(reps, step_reps, skip_step):
+    # torch starts HIP with this line, before the library loads: the process keeps the hardware-queue count of its environment
+    lines = ['device: %s; the two sides alternate; a window is `inner` launches between two device events' % torch.cuda.get_device_name(0)]
+    dev = benchlib.device()
+    lines.append('clocks before: ' + benchlib.clocks())
+    kernels(dev, reps, lines)
+    if not skip_step:
+        step(dev, step_reps, lines)
+    lines.append('clocks after: ' + benchlib.clocks())
+    print('\n'.join(lines))
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=30)
-    ap.add_argument('--step-reps', type=int, default=10)
-    ap.add_argument('--skip-step', action='store_true')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_step_bench.txt'))
-    a = ap.parse_args()
-    dev = torch.device('cuda:0')
-    lines = ['# python tools/train_step_bench.py --reps %d --step-reps %d   (see the tool for what each line measures)' % (a.reps, a.step_reps),
-             'device: %s; the two sides alternate; a window is `inner` launches between two device events' % torch.cuda.get_device_name(0),
-             'clocks before: ' + clocks()]
-    kernels(dev, a.reps, lines)
-    if not a.skip_step:
-        step(dev, a.step_reps, lines)
-    lines.append('clocks after: ' + clocks())
-    txt = '\n'.join(lines) + '\n'
-    print(txt)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, 'w') as f:
-        f.write(txt)
+    # the time limit: a run with the default arguments took 10 to 12 s, and 68 s as the first of its kind on a box
+    benchlib.main(__file__, child, out='train_step_bench.txt', reps=30, timeout=300,
+                  extra=[('--step-reps', dict(type=int, default=10)), ('--skip-step', dict(action='store_true'))],
+                  header='# python tools/train_step_bench.py --reps %(reps)d --step-reps %(step_reps)d   (see the tool for what each line measures)')
 
 
 if __name__ == '__main__':
