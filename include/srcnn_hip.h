@@ -526,7 +526,12 @@ SRCNN_API size_t srcnn_dense_align_workspace_bytes(int H, int W, int R, int max_
  *   offsets[1], [2], [3] = coarse stage: float depth_enum[50][R], float cost[50][R] (sum over pixels and channels of |L - R|,
  *                          workgroup-reduced in a fixed order), float best_depth[R] (first minimum)
  *   offsets[4], [5], [6] = fine stage: depth_enum[20][R] (rows 20..49 unused), cost[20][R], best_depth[R]
- * n_offsets must be >= 7. */
+ * n_offsets must be >= 7.  With n_offsets >= 11 the stages BEFORE the search are located too (stage-level parity tests):
+ *   offsets[7], [8] = float up_left[3][2H][2W], up_right[3][2H][2W]: the 2x upsampled images
+ *   offsets[9]      = float uvz[R][max_pixels][3]: (u, v, dz) of every valid lattice pixel, compacted in row-major lattice order;
+ *                     rows cnt[r].. of an object are never written
+ *   offsets[10]     = float left_val[R][max_pixels][3]: the left image's taps at (u, v), per channel
+ * A caller passing 7..10 gets offsets[0..6] only, as before. */
 SRCNN_API int srcnn_dense_align_workspace_layout(int H, int W, int R, int max_pixels, size_t *offsets, int n_offsets);
 SRCNN_API int srcnn_dense_align(const float *im_left, const float *im_right, int H, int W, double scale,
                       double p2_00, double p2_02, double p2_12, double p2_03_minus_p3_03,

@@ -378,13 +378,19 @@ size_t srcnn_dense_align_workspace_bytes(int H, int W, int R, int max_pixels)
 int srcnn_dense_align_workspace_layout(int H, int W, int R, int max_pixels, size_t *offsets, int n_offsets)
 {
     using namespace srcnn;
-    SRCNN_REQUIRE(offsets && n_offsets >= 7 && H > 1 && W > 1 && R > 0 && max_pixels > 0, "7 offsets; positive sizes");
+    SRCNN_REQUIRE(offsets && n_offsets >= 7 && H > 1 && W > 1 && R > 0 && max_pixels > 0, "7 or 11 offsets; positive sizes");
     const DaLayout L = da_layout(H, W, R, max_pixels);
     offsets[0] = L.cnt;
     for (int stage = 0; stage < 2; ++stage) {
         offsets[1 + 3 * stage] = L.depth_enum[stage];
         offsets[2 + 3 * stage] = L.cost[stage];
         offsets[3 + 3 * stage] = L.best[stage];
+    }
+    if (n_offsets >= 11) {                                       // the stages before the search (stage-level parity tests)
+        offsets[7] = L.up_l;
+        offsets[8] = L.up_r;
+        offsets[9] = L.uvz;
+        offsets[10] = L.left_val;
     }
     return SRCNN_OK;
 }

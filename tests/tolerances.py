@@ -36,6 +36,19 @@ DECODED_PX = 2.5e-4
 KITTI_BEV_EXACT = {'near': 6.6e-11, 'far': 7.2e-11}
 KITTI_BEV_REFERENCE_MEASURED = {'near': 1.63e-11, 'far': 1.79e-11}
 
+# Dense-alignment stages (tests/test_dense_align_stages_gpu.py) against the float64 references of tests/dense_align_ref.py, on
+# the scenes of tests/dense_align_scenes.py.  As for KITTI_BEV_EXACT: FOUR TIMES the largest deviation of the float32 ORACLE
+# (oracle/dense_align.py on the CPU) from the float64 reference over the same scenes, measured and held by
+# tests/test_dense_align_ref_cpu.py -- a correct float32 evaluation cannot be asked to beat another one by much.
+#   DZ:  the depth offset of a lattice pixel's ray / box intersection (uvz[:, 2], metres)
+#   TAP: a left-image tap at a lattice point (grey levels of the mean-subtracted network input; the float32 `unnorm` round trip
+#        moves the tap coordinate by some 1e-5 px, which the image gradient turns into this)
+#   oracle vs float64, measured on the CPU: dz 4.42e-6 m (objects at 3..25 m), taps 1.61e-4 (values up to 150)
+DENSE_ALIGN_DZ_REFERENCE_MEASURED = 4.5e-6
+DENSE_ALIGN_TAP_REFERENCE_MEASURED = 1.61e-4
+DENSE_ALIGN_DZ = 4 * DENSE_ALIGN_DZ_REFERENCE_MEASURED
+DENSE_ALIGN_TAP = 4 * DENSE_ALIGN_TAP_REFERENCE_MEASURED
+
 _measured = {}
 
 
