@@ -327,13 +327,45 @@ typedef struct srcnn_conv_bwd_desc {
     int KH, KW, stride, pad;
     int y_cstride, y_coffset;
     int relu;
-    int mode, precision;                   /* must be 0 */
+    int mode, precision;                   /* mode 0; precision 0 for srcnn_conv2d_backward, 1 for srcnn_conv2d_backward_f16x3 */
     int x_format, y_format;                /* must be SRCNN_FMT_F32 */
     int tile_mr, tile_nr, splits;          /* 0 = heuristic */
     const void *head_w, *head_wf, *x2, *up_top;   /* must be NULL */
 } srcnn_conv_bwd_desc;
 SRCNN_API size_t srcnn_conv2d_backward_workspace_bytes(const srcnn_conv_bwd_desc *d);
 SRCNN_API int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+
+/* ------------------------------------------------- convolution backward, 3 x f16 split (training; opt-in)
+ * The same gradients from the same descriptor, definitions (db, dx, dw, g_out), layouts and NULL-output rules, with the two GEMMs on
+ * v_mfma_f32_32x32x16_f16 (fp32 accumulation).  desc.precision must be 1 here ("precision"); every other refusal is the fp32
+ * call's, before the first launch.  srcnn_conv2d_backward itself keeps refusing precision != 0: neither call replaces the other.
+ *
+ * SCHEME.  Every product is  a b ~ (a_hi b_hi + a_hi b_lo + a_lo b_hi) / (s_a s_b),  t = s v, hi = f16(t), lo = f16(t - hi) (t and
+ * t - hi are exact in fp32; lo lo is dropped): fp32-class results, a relative error of about 3 * 2^-22 per product plus the
+ * fp32 accumulation.  SCALES: s is one power of two per operand tensor -- the masked gradient g, the weights w, and x for dw --
+ * s = 2^(14 - floor(log2 max|v|)) with the exponent clamped to +-126, so the tensor's largest element lands in [2^14, 2^15)
+ * whatever its range (gradients of 1e-6 and below would otherwise sit in the f16 subnormals).  What is left of a tensor's
+ * dynamic range: an element below 2^-28 of its tensor's maximum has a subnormal hi and is carried with an absolute error of
+ * up to 2^-39 of the maximum.  max|v| is found on the device (its float bits under an integer atomicMax, which no order can
+ * change): for g in the mask / bias pass, for w and x in one read-only pass each; the words live in the workspace, are cleared
+ * by the call's first kernel, and are read by the kernels that split.  Nothing is read back by the host.  Scaling dy (or x, or
+ * w) by a power of two scales the results by exactly that power, bit for bit, as long as nothing leaves the fp32 range.  An
+ * all-zero tensor gives exact zeros.
+ * (1) The fp32 call's mask / bias pass -- the same code: g_out and db are bit-equal to srcnn_conv2d_backward's, db with the
+ * same defined order -- always runs and writes g as fp32 (M, Cp) rows.  (2) dx: max|w|; the re-layout kernel writes w as two f16
+ * planes hi, lo of (Cin, KH, KW, Cp); the implicit GEMM in gather form splits g while staging it into LDS; every element of dx is
+ * stored once, zeros included.  (3) dw: max|x|; g and x are split and transposed (K = pixels must be contiguous per MFMA
+ * lane) in registers while they are staged; split-K and its reduction are the fp32 call's.
+ *
+ * DEFINED SUMMATION ORDER (run-to-run bit-equal for a given descriptor, tile_mr, tile_nr and splits included).
+ *   dx: K tiles over taps in (kh, kw) row-major order, inside a tap over the 32-channel tiles of Cp ascending; a K tile is two
+ *     matrix steps of 16 channels.  Per step and element: cross += lo hi, main += hi hi, cross += hi lo (two fp32 accumulators;
+ *     the 16 products of a step are summed by the matrix unit in its own fixed order).  Result (main + cross) / s_g / s_w.
+ *   dw: per K slice (the fp32 call's slices) K tiles of 32 pixels in ascending m, two steps of 16 pixels each, the same two
+ *     accumulators; (main + cross) / s_g / s_x per slice, slices added in ascending order by the reduction kernel.
+ * The workspace query grows by the scale words; the re-laid weights take the same bytes as in the fp32 call. */
+SRCNN_API size_t srcnn_conv2d_backward_f16x3_workspace_bytes(const srcnn_conv_bwd_desc *d);
+SRCNN_API int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
 /* ------------------------------------------------- training: remaining adjoints
  * The three differentiable operators of the reference's training branch that are neither a convolution, a ROIAlign nor a loss:

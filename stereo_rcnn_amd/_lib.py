@@ -150,6 +150,8 @@ _SIGNATURES = {
     "srcnn_conv2d_group": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
     "srcnn_conv2d_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
     "srcnn_conv2d_backward": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
+    "srcnn_conv2d_backward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
+    "srcnn_conv2d_backward_f16x3": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
     "srcnn_upsample_add_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_subsample2_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_pixel_shuffle2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

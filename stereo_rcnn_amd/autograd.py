@@ -3,7 +3,9 @@
 Every learnable layer of the network goes through the conv engine (the ResNet and FPN convs, RPN_Conv and its heads, RCNN_top,
 the linear heads, the keypoint tower).  These functions are that engine with a backward: the forward is `engine.conv2d(...,
 precision='f32')`, the backward `engine.conv2d_backward` (srcnn_conv2d_backward: dx, dw, db on the fp32 MFMA; include/srcnn_hip.h
-states the sums and their order).  Tensors are NCHW at the edge and NHWC inside, like the ROIAlign modules.  Nothing here waits for
+states the sums and their order) or, with backward_precision='f16x3', srcnn_conv2d_backward_f16x3 (the same gradients by the
+error-compensated 3 x f16 split; the forward stays the exact-fp32 engine: an f16x3 forward needs its weight-scale exponent on the
+host, a host read per layer and step).  Tensors are NCHW at the edge and NHWC inside, like the ROIAlign modules.  Nothing here waits for
 the device.  CPU tensors raise NotImplementedError, as the project's other ops.
 
 conv2d_nhwc is the same convolution NHWC to NHWC: a graph of many layers (stereo_rcnn_amd.training) stays in the engine's layout
@@ -27,7 +29,10 @@ class _Conv2dNHWC(torch.autograd.Function):
     (B, OH, OW, Cout) or None; all contiguous float32 on the device."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, stride, pad, relu):
+    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32'):
+        if backward_precision not in ('f32', 'f16x3'):
+            raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
+        ctx.backward_precision = backward_precision
         B, H, W, cin = (int(v) for v in x.shape)
         cout, kh, kw = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         cw = engine.ConvW(weight.detach(), None if bias is None else bias.detach(), kh, kw, stride, pad, relu)
@@ -52,8 +57,8 @@ class _Conv2dNHWC(torch.autograd.Function):
         res = {}
         if want or g_out is not None:
             cw = engine.ConvW(weight, None, kh, kw, stride, pad, relu)
-            res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out)
-        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None, None, None, None)
+            res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out, precision=ctx.backward_precision)
+        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None, None, None, None, None)
 
 
 def _check(x, weight):
@@ -97,21 +102,22 @@ def _fold(weight_eng, bias, bn):
     return w, b
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None):
+def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32'):
     """relu?(bn?(conv2d(x, weight) + bias) + residual) on the exact-fp32 engine, differentiable with respect to x, weight, bias
     and residual.  x (B, Cin, H, W) with Cin a multiple of 32, weight (Cout, Cin, KH, KW) as nn.Conv2d holds it, residual
     (B, Cout, OH, OW); bn: a dict with 'weight', 'bias', 'running_mean', 'running_var' -- the frozen BatchNorm that follows the
-    convolution (no gradient reaches it).  Returns (B, Cout, OH, OW)."""
+    convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients (the forward is
+    the exact-fp32 engine either way).  Returns (B, Cout, OH, OW)."""
     _check(x, weight)
     if int(x.shape[1]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[1]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     r = None if residual is None else _ToNHWC.apply(residual)
-    y = _Conv2dNHWC.apply(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu))
+    y = _Conv2dNHWC.apply(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision)
     return _ToNCHW.apply(y)
 
 
-def linear(x, weight, bias=None, relu=False):
+def linear(x, weight, bias=None, relu=False, backward_precision='f32'):
     """relu?(x @ weight.T + bias) as a 1x1 convolution over an (n, 1, 1, K) tensor: x (n, K), weight (out, K) as nn.Linear holds
     it.  K must be a multiple of 32."""
     _check(x, weight)
@@ -119,11 +125,12 @@ def linear(x, weight, bias=None, relu=False):
     if K % 32 != 0:
         raise ValueError("linear: K must be a multiple of 32 (got %d)" % K)
     out = int(weight.shape[0])
-    y = _Conv2dNHWC.apply(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu))
+    y = _Conv2dNHWC.apply(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu),
+                          backward_precision)
     return y.view(n, out)
 
 
-def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None):
+def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32'):
     """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
     (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back)."""
     _check(x, weight)
@@ -131,7 +138,7 @@ def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     return _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
-                             int(stride), int(padding), bool(relu))
+                             int(stride), int(padding), bool(relu), backward_precision)
 
 
 def _check_nhwc(x, what):
@@ -235,7 +242,7 @@ class _PixelShuffle2(torch.autograd.Function):
         return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
 
 
-def conv_transpose2x2(x, weight, bias=None, relu=False):
+def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'):
     """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
     nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
     engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
@@ -249,5 +256,5 @@ def conv_transpose2x2(x, weight, bias=None, relu=False):
         raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
     w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
     b = None if bias is None else bias.repeat(4)
-    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu))
+    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision)
     return _PixelShuffle2.apply(y, cout)

@@ -16,84 +16,10 @@
 //                            global rows -- is read back with ds_read_b32 at consecutive addresses over the 32 lanes of a half
 //                            wave: conflict-free (the two halves are served separately) and no padding is needed.
 //   wgrad_reduce_kernel      split-K partials -> dw, ascending slice order
-#include "conv_tile_4w.h"
-#include <cstdint>
+// (the mask / bias pass, the two reductions and the call's layout are in conv_backward_common.h: the f16x3 backward shares them)
+#include "conv_backward_common.h"
 
 namespace srcnn {
-
-struct BwdArgs {
-    const float *x, *w, *y, *dy;
-    float *dx, *dw, *db, *g_out;
-    const float *g;            // what the GEMMs read: gp, or dy in place
-    int gcs, gco;              // its pixel stride and channel offset; it has Cp channels
-    float *gp;                 // workspace: masked gradient (M, Cp), or nullptr
-    float *db_part;            // workspace: bias partials (nq, Cp)
-    float *wt;                 // workspace: weights (Cin, taps, Cp)
-    float *partial;            // workspace: wgrad slices (splits, Cout, Kw)
-    int H, W, Cin, xcs;
-    int OH, OW, Cout, Cp;
-    int KH, KW, stride, pad;
-    int ycs, yco, relu;
-    int M, Min;                // output pixels B OH OW, input pixels B H W
-    int taps, Kw;              // KH KW, taps * Cin
-    int d_ctiles, d_nkt, d_mtiles, d_ntiles;                // dgrad: Cp / 32, taps * d_ctiles, tile counts
-    int w_nkt, w_kt_per_split, w_mtiles, w_ntiles;          // wgrad: ceil(M / 32), K tiles per slice, tile counts
-};
-
-struct BwdPlan {
-    bool pass;                 // the mask / bias pass runs
-    int d_mr, d_nr, w_mr, w_nr, splits, nq;
-    size_t off_gp, off_db, off_wt, off_part, bytes;
-};
-
-__global__ __launch_bounds__(256) void bwd_mask_bias_kernel(const BwdArgs p)
-{
-    __shared__ float red[8][32];
-    const int t = threadIdx.x, c = t & 31, r = t >> 5;
-    const int n = blockIdx.y * 32 + c;          // < Cp
-    const bool nok = n < p.Cout;
-    const int m_base = blockIdx.x * 256;
-    float s = 0.f;
-    for (int i = 0; i < 32; ++i) {
-        const int m = m_base + r + 8 * i;
-        if (m >= p.M) break;
-        float v = 0.f;
-        if (nok) {
-            const size_t o = (size_t)m * p.ycs + p.yco + n;
-            v = p.dy[o];
-            if (p.relu && !(p.y[o] > 0.f)) v = 0.f;
-            if (p.g_out) p.g_out[(size_t)m * p.Cout + n] = v;
-        }
-        if (p.gp) p.gp[(size_t)m * p.Cp + n] = v;
-        s += v;
-    }
-    if (!p.db) return;
-    red[r][c] = s;
-    __syncthreads();
-    if (r == 0) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a += red[k][c];
-        p.db_part[(size_t)blockIdx.x * p.Cp + n] = a;
-    }
-}
-
-__global__ __launch_bounds__(256) void bwd_bias_reduce_kernel(const BwdArgs p, int nq)
-{
-    __shared__ float red[8][32];
-    const int t = threadIdx.x, c = t & 31, r = t >> 5;
-    const int n = blockIdx.x * 32 + c;          // < Cp
-    float s = 0.f;
-    for (int q = r; q < nq; q += 8) s += p.db_part[(size_t)q * p.Cp + n];
-    red[r][c] = s;
-    __syncthreads();
-    if (r == 0 && n < p.Cout) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a += red[k][c];
-        p.db[n] = a;
-    }
-}
 
 // grid (Cin / 32, Cp / 32, taps), block (32, 8): one 32 x 32 transpose per block through LDS, both sides coalesced
 __global__ __launch_bounds__(256) void bwd_weight_relayout(const BwdArgs p)
@@ -301,103 +227,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const BwdArgs p)
     for_each_c(acc, g, n0, j0, p.Cout, p.Kw, [&](int row, int col, float v) { out[(size_t)row * p.Kw + col] = v; });
 }
 
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const BwdArgs p, int splits)
-{
-    const size_t total = (size_t)p.Cout * p.Kw;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        float v = 0.f;
-        for (int s = 0; s < splits; ++s) v += p.partial[(size_t)s * total + idx];
-        p.dw[idx] = v;
-    }
-}
-
-// Validates the descriptor and lays out the call: kernel arguments (workspace pointers as OFFSETS from nullptr until the caller
-// binds them), tiles, slices and the workspace size.
-static int bwd_prepare(const srcnn_conv_bwd_desc *d, BwdArgs &a, BwdPlan &pl)
-{
-    SRCNN_REQUIRE(d != nullptr, "null descriptor");
-    SRCNN_REQUIRE(d->dy != nullptr, "null pointer: dy");
-    SRCNN_REQUIRE(d->dx || d->dw || d->db || d->g_out, "null pointer: no output requested");
-    SRCNN_REQUIRE(!d->dw || d->x, "null pointer: dw needs x");
-    SRCNN_REQUIRE(!d->dx || d->w, "null pointer: dx needs w");
-    SRCNN_REQUIRE(!d->relu || d->y, "null pointer: relu needs the saved output y");
-    SRCNN_REQUIRE(d->mode == 0, "mode 0 only (ConvTranspose2d and the RPN pair mode have no backward)");
-    SRCNN_REQUIRE(d->precision == 0, "precision must be 0 (the exact fp32 engine)");
-    SRCNN_REQUIRE(d->x_format == SRCNN_FMT_F32 && d->y_format == SRCNN_FMT_F32, "format must be SRCNN_FMT_F32");
-    SRCNN_REQUIRE(!d->head_w && !d->head_wf, "a fused head has no backward");
-    SRCNN_REQUIRE(!d->x2, "a second input has no backward");
-    SRCNN_REQUIRE(!d->up_top, "the fused upsample-add has no backward");
-    SRCNN_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->Cin > 0, "bad shape: sizes must be positive");
-    SRCNN_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "bad shape: kernel, stride > 0 and pad >= 0");
-    SRCNN_REQUIRE(d->H + 2 * d->pad >= d->KH && d->W + 2 * d->pad >= d->KW &&
-                      d->OH == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
-                  "bad shape: OH / OW are not the forward's output size");
-    SRCNN_REQUIRE(d->Cin % BK == 0, "Cin must be a positive multiple of 32");
-    SRCNN_REQUIRE(d->x_cstride >= d->Cin && d->x_cstride % 4 == 0, "x_cstride: a stride of at least Cin floats, a multiple of 4");
-    SRCNN_REQUIRE(d->y_coffset >= 0 && d->y_cstride >= d->y_coffset + d->Cout, "y_cstride: a stride of at least y_coffset + Cout floats");
-    SRCNN_REQUIRE(!d->dw || (reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "x must be 16-byte aligned (stride-4 vector loads)");
-    SRCNN_REQUIRE((unsigned)d->tile_mr <= 2 && (unsigned)d->tile_nr <= 2, "tile_mr / tile_nr must be 0, 1 or 2");
-    SRCNN_REQUIRE(d->splits >= 0, "splits must be >= 0");
-    const long long M = (long long)d->B * d->OH * d->OW, Min = (long long)d->B * d->H * d->W;
-    const long long Kw = (long long)d->KH * d->KW * d->Cin;
-    SRCNN_REQUIRE(M < (1LL << 31) && Min < (1LL << 31) && Kw < (1LL << 31) && d->Cout < (1 << 20) && d->KH < 256 && d->KW < 256,
-                  "bad shape: tensor too large");
-
-    a.x = d->x; a.w = d->w; a.y = d->y; a.dy = d->dy;
-    a.dx = d->dx; a.dw = d->dw; a.db = d->db; a.g_out = d->g_out;
-    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
-    a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.ycs = d->y_cstride; a.yco = d->y_coffset; a.relu = d->relu ? 1 : 0;
-    a.M = (int)M; a.Min = (int)Min; a.taps = d->KH * d->KW; a.Kw = (int)Kw;
-    const bool gemm = d->dx || d->dw;
-    pl.pass = d->relu || d->db || d->g_out || d->Cout % BK != 0 || d->y_cstride % 4 != 0 || d->y_coffset % 4 != 0 ||
-              (reinterpret_cast<uintptr_t>(d->dy) & 15) != 0;
-    pl.nq = cdiv(a.M, 256);
-
-    // dgrad tile: the forward's rule -- the largest tile that still gives two workgroups per CU
-    choose_tile_4w(a.Min, a.Cin, &pl.d_mr, &pl.d_nr);
-    // wgrad tile: M x N is small and K long, so the tile is as large as the matrix allows and split-K fills the chip
-    pl.w_mr = a.Cout > 64 ? 2 : 1;
-    pl.w_nr = a.Kw > 64 ? 2 : 1;
-    if (d->tile_mr > 0 && d->tile_nr > 0) {
-        pl.d_mr = pl.w_mr = d->tile_mr;
-        pl.d_nr = pl.w_nr = d->tile_nr;
-    }
-    a.d_ctiles = a.Cp / BK;
-    a.d_nkt = a.taps * a.d_ctiles;
-    a.d_mtiles = cdiv(a.Min, 64 * pl.d_mr);
-    a.d_ntiles = cdiv(a.Cin, 64 * pl.d_nr);
-    SRCNN_REQUIRE((long long)a.d_mtiles * a.d_ntiles < (1LL << 31), "bad shape: tensor too large");
-    a.w_nkt = cdiv(a.M, BK);
-    a.w_mtiles = cdiv(a.Cout, 64 * pl.w_mr);
-    a.w_ntiles = cdiv(a.Kw, 64 * pl.w_nr);
-    SRCNN_REQUIRE((long long)a.w_mtiles * a.w_ntiles < (1LL << 31), "bad shape: tensor too large");
-    int s = d->splits;
-    if (s <= 0) {
-        const long blocks = (long)a.w_mtiles * a.w_ntiles;
-        s = (int)min(64L, (512 + blocks - 1) / blocks);
-        s = min(s, max(1, a.w_nkt / 8));
-    }
-    s = max(1, min(min(s, a.w_nkt), 65535));
-    a.w_kt_per_split = cdiv(a.w_nkt, s);
-    pl.splits = cdiv(a.w_nkt, a.w_kt_per_split);
-
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        const size_t at = off;
-        off += align_up(floats * sizeof(float), 256);
-        return at;
-    };
-    pl.off_gp = pl.off_db = pl.off_wt = pl.off_part = 0;
-    if (pl.pass && gemm) pl.off_gp = take((size_t)a.M * a.Cp);
-    if (d->db) pl.off_db = take((size_t)pl.nq * a.Cp);
-    if (d->dx) pl.off_wt = take((size_t)a.Cin * a.taps * a.Cp);
-    if (d->dw && pl.splits > 1) pl.off_part = take((size_t)pl.splits * a.Cout * a.Kw);
-    pl.bytes = off > 256 ? off : 256;
-    return SRCNN_OK;
-}
-
 }  // namespace srcnn
 
 extern "C" {
@@ -407,7 +236,7 @@ size_t srcnn_conv2d_backward_workspace_bytes(const srcnn_conv_bwd_desc *d)
     using namespace srcnn;
     BwdArgs a;
     BwdPlan pl;
-    if (bwd_prepare(d, a, pl) != SRCNN_OK) return 0;
+    if (bwd_prepare(d, a, pl, false) != SRCNN_OK) return 0;
     return pl.bytes;
 }
 
@@ -416,7 +245,7 @@ int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t 
     using namespace srcnn;
     BwdArgs a;
     BwdPlan pl;
-    int rc = bwd_prepare(d, a, pl);
+    int rc = bwd_prepare(d, a, pl, false);
     if (rc != SRCNN_OK) return rc;
     if (!workspace || workspace_bytes < pl.bytes) {
         set_error("srcnn_conv2d_backward: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
@@ -435,7 +264,7 @@ int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t 
     }
     hipStream_t st = as_stream(stream);
     if (pl.pass) {
-        SRCNN_LAUNCH(bwd_mask_bias_kernel, dim3(pl.nq, a.Cp / BK), dim3(256), 0, st, a);
+        SRCNN_LAUNCH(bwd_mask_bias_kernel<false>, dim3(pl.nq, a.Cp / BK), dim3(256), 0, st, a, (unsigned *)nullptr);
         if (d->db) SRCNN_LAUNCH(bwd_bias_reduce_kernel, dim3(a.Cp / BK), dim3(256), 0, st, a, pl.nq);
     }
     if (d->dx) {

@@ -692,8 +692,10 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
 
 
 def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), splits=0, x_cstride=None, y_cstride=None, y_coffset=0,
-                    relu=None, g_out=None, out=None, tile=None):
+                    relu=None, g_out=None, out=None, tile=None, precision='f32'):
     """Gradients of conv2d(cw, x, ..., precision='f32') (srcnn_conv2d_backward; include/srcnn_hip.h states the sums' orders).
+    precision: 'f32', that exact fp32 backward, or 'f16x3', srcnn_conv2d_backward_f16x3 -- the same gradients by the 3 x f16 split
+    with per-tensor power-of-two scales found on the device; the one asked for runs, never the other in its place.
     x (B, H, W, *) and dy / y (B, OH, OW, *) are raw NHWC device tensors with the forward's strides; y is the saved forward output
     (needed when relu, else may be None); relu defaults to cw.relu.  want: which of 'dx' (like x: pixel stride x_cstride), 'dw'
     (Cout, KH, KW, Cin) and 'db' (Cout) to compute -- the others are neither computed nor allocated.  g_out: optional dense
@@ -701,6 +703,9 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     to write into instead of fresh tensors (every element is overwritten).  splits: K slices of the weight gradient (0 = the
     library's choice); tile: (tile_mr, tile_nr).  Returns {name: tensor} for the names in want."""
     L = _lib.lib()
+    if precision not in ('f32', 'f16x3'):
+        raise ValueError("conv2d_backward: precision must be 'f32' or 'f16x3' (got %r)" % (precision,))
+    entry = 'srcnn_conv2d_backward' if precision == 'f32' else 'srcnn_conv2d_backward_f16x3'
     assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a backward"
     unknown = set(want) - {'dx', 'dw', 'db'}
     assert not unknown, unknown
@@ -727,11 +732,12 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     d.y_coffset = y_coffset
     d.relu = cw.relu if relu is None else int(relu)
     d.splits = int(splits)
+    d.precision = 0 if precision == 'f32' else 1
     if tile is not None:
         d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
-    nbytes = L.srcnn_conv2d_backward_workspace_bytes(ctypes.byref(d))
+    nbytes = getattr(L, entry + '_workspace_bytes')(ctypes.byref(d))
     ws = _lib.workspace(nbytes, dy.device, "conv_backward")
-    _lib.check(L.srcnn_conv2d_backward(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_backward")
+    _lib.check(getattr(L, entry)(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), entry)
     return res
 
 

@@ -12,6 +12,8 @@ nothing waits for the device.  --resume loads model, optimiser state and uncert 
 every N-th epoch the model's inference weights are refreshed in place (plan.Plan.refresh), the split runs through the inference
 pipeline and kitti_eval, <save_dir>/ap_epoch<E>.json is written and the Car Moderate line logged (validation.py); training itself
 is bit-identical with and without it.
+--backward-precision f32|f16x3 (default f32; logged in trainlog.txt): the engine of the convolution gradients
+(training.train_step's backward_precision).
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -53,6 +55,8 @@ def parse_args(argv=None):
     p.add_argument('--val-label-dir', dest='val_label_dir', default=None, help='KITTI label_2 directory of the validation frames')
     p.add_argument('--val-every', dest='val_every', default=1, type=int, help='unit: epoch')
     p.add_argument('--val-precision', dest='val_precision', choices=['f16x3', 'f32'], default='f16x3')
+    p.add_argument('--backward-precision', dest='backward_precision', choices=['f32', 'f16x3'], default='f32',
+                   help='engine of the convolution gradients: the exact fp32 backward, or the 3 x f16 split (the forward is fp32 either way)')
     return p.parse_args(argv)
 
 
@@ -87,6 +91,7 @@ def main(argv=None):
         print(s)
 
     log_string('{:d} roidb entries'.format(train_size))
+    log_string('backward precision: %s' % args.backward_precision)
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
@@ -129,7 +134,8 @@ def main(argv=None):
             for step, batch in enumerate(loader):
                 if step >= iters_per_epoch:              # trainval_net.py:183,194: the leftover samples are not trained on
                     break
-                res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev)
+                res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
+                                          backward_precision=args.backward_precision)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))

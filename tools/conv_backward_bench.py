@@ -1,6 +1,7 @@
 """Convolution backward (dx + dw + db in one srcnn_conv2d_backward call) against torch's own fp32 convolution backward.
 
     python tools/conv_backward_bench.py [--out profiles/conv_backward_bench.txt] [--reps 50]
+    python tools/conv_backward_bench.py --precision f16x3 --out profiles/conv_backward_f16x3_bench.txt
 
 Shapes: the trainable trunk and head at B = 1, one 600 x 1987 image (pyramid maps 150x497, 75x249, 38x125, 19x63) -- the (M, N, K)
 of the per-layer table (stereo_rcnn_amd/layer_table.py) for a representative bottleneck of layer2 / layer3 / layer4, an FPN lateral
@@ -11,6 +12,8 @@ and a smooth conv, RPN_Conv and the 24-channel RPN head on P2, RCNN_top and the 
   * torch : aten.convolution_backward (dx, dw, db) on the same values in NCHW float32 plus the ReLU's threshold_backward, i.e.
             what torch.autograd runs for relu(conv(x)) on this device;
   * fwd   : the exact-fp32 forward (srcnn_conv2d, precision 0, heuristic plan) of the same layer, the second yardstick.
+--precision f16x3 adds a column: srcnn_conv2d_backward_f16x3 (the 3 x f16 split; its clear / max / split passes included) on the
+same layers, alternating with the fp32 backward inside every round -- the yardstick is that fp32 column -- and f16x3 / hip.
 FLOPs: 2 M N K for the forward, twice that for the backward (dgrad + wgrad), whatever zeros a stride multiplies.
 One process, 10 untimed runs of each first; hip and torch ALTERNATE; every run is timed with device events; medians of --reps.
 Runner and timer: tools/benchlib.py."""
@@ -37,12 +40,14 @@ LAYERS = [
 ]
 
 
-def child(reps):
+def child(reps, precision='f32'):
     import torch
     from stereo_rcnn_amd import engine
     dev = benchlib.device()
     aten = torch.ops.aten
-    print('%-30s %9s %6s %7s | %9s %7s | %9s %7s | %9s %7s' % ('layer', 'M', 'N', 'K', 'hip us', 'TF/s', 'torch us', 'TF/s', 'hip/torch', 'fwd TF/s'))
+    f16 = precision == 'f16x3'
+    print('%-30s %9s %6s %7s | %9s %7s | %9s %7s | %9s %7s' % ('layer', 'M', 'N', 'K', 'hip us', 'TF/s', 'torch us', 'TF/s', 'hip/torch', 'fwd TF/s')
+          + (' | %9s %7s %9s' % ('f16x3 us', 'TF/s', 'f16x3/hip') if f16 else ''))
     for name, B, H, W, cin, cout, k, s, p in LAYERS:
         gen = torch.Generator().manual_seed(1)
         OH, OW = engine.conv_out_hw(H, W, k, k, s, p)
@@ -61,6 +66,11 @@ def child(reps):
         def hip():
             engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, out=out)
 
+        out3 = {k_: torch.empty_like(v) for k_, v in out.items()}
+
+        def hip3():
+            engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, out=out3, precision='f16x3')
+
         def eager():
             g = aten.threshold_backward(dyn, yn, 0)
             return aten.convolution_backward(g, xn, wn, [cout], [s, s], [p, p], [1, 1], False, [0, 0], 1, [True, True, True])
@@ -73,20 +83,29 @@ def child(reps):
         agree = [float((a - b).abs().max() / b.abs().max()) for a, b in
                  ((out['dx'].permute(0, 3, 1, 2), ref[0]), (out['dw'].permute(0, 3, 1, 2), ref[1]), (out['db'], ref[2]))]
         assert max(agree) < 1e-3, (name, agree)            # the two compute the same thing (the tests hold the real bound)
-        times = benchlib.alternating([('hip', hip), ('torch', eager), ('fwd', fwd)], reps, warmup=10)
+        versions = [('hip', hip), ('torch', eager), ('fwd', fwd)]
+        if f16:
+            hip3()
+            torch.cuda.synchronize()
+            agree3 = [float((out3[k_] - out[k_]).abs().max() / out[k_].abs().max()) for k_ in ('dx', 'dw', 'db')]
+            assert max(agree3) < 1e-4, (name, agree3)
+            versions.append(('f16x3', hip3))
+        times = benchlib.alternating(versions, reps, warmup=10)
         med = {k_: benchlib.stats(v)[0] * 1e3 for k_, v in times.items()}
         M, K = B * OH * OW, k * k * cin
         fl = 2.0 * M * cout * K
         print('%-30s %9d %6d %7d | %9.1f %7.1f | %9.1f %7.1f | %9.2f %7.1f'
               % (name, M, cout, K, med['hip'], 2 * fl / med['hip'] / 1e6, med['torch'], 2 * fl / med['torch'] / 1e6,
-                 med['hip'] / med['torch'], fl / med['fwd'] / 1e6), flush=True)
+                 med['hip'] / med['torch'], fl / med['fwd'] / 1e6)
+              + (' | %9.1f %7.1f %9.2f' % (med['f16x3'], 2 * fl / med['f16x3'] / 1e6, med['f16x3'] / med['hip']) if f16 else ''), flush=True)
     print('(times are medians of %d runs in us, event-timed one call at a time, launch overhead of the 3 to 6 launches of a call included;'
           ' TF/s = 4 M N K / time for the backward, 2 M N K / time for the forward)' % reps)
 
 
 def main():
     benchlib.main(__file__, child, out='conv_backward_bench.txt', reps=50, timeout=420,
-                  header='# python tools/conv_backward_bench.py --reps %(reps)d   (see the tool for what each column measures)')
+                  header='# python tools/conv_backward_bench.py --reps %(reps)d --precision %(precision)s   (see the tool for what each column measures)',
+                  extra=[('--precision', dict(choices=['f32', 'f16x3'], default='f32'))])
 
 
 if __name__ == '__main__':

@@ -164,7 +164,7 @@ def eager_step(model, im_left, im_right, im_height, taps, fixed_blocks):
     return list(rpn_losses) + list(rcnn_losses)
 
 
-def step(dev, reps, lines):
+def step(dev, reps, lines, f16x3=False):
     from stereo_rcnn_amd import fixture, training
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
     from stereo_rcnn_amd.model.utils.config import cfg
@@ -202,6 +202,10 @@ def step(dev, reps, lines):
         clear()
         sum(training.forward_train(model, *args, generator=gen)[8:14]).backward()
 
+    def product_f16x3():
+        clear()
+        sum(training.forward_train(model, *args, generator=gen, backward_precision='f16x3')[8:14]).backward()
+
     def eager():
         clear()
         sum(eager_step(model, im_l, im_r, float(Hh), data, cfg.RESNET.FIXED_BLOCKS)).backward()
@@ -218,22 +222,26 @@ def step(dev, reps, lines):
     eager()
     torch.cuda.synchronize()
     mem_e = torch.cuda.max_memory_allocated() / 2.0 ** 30
-    r = {k: benchlib.stats(v) for k, v in benchlib.alternating([('hip', product), ('eager', eager)], reps, warmup=2).items()}
+    versions = [('hip', product), ('eager', eager)] + ([('f16x3', product_f16x3)] if f16x3 else [])
+    r = {k: benchlib.stats(v) for k, v in benchlib.alternating(versions, reps, warmup=2).items()}
     lines.append('forward + backward of the training step, ResNet-101, 600 x 1987, B = 1, %d alternating runs, ms: median (min, max)' % reps)
     lines.append('  forward_train (exact-fp32 engine, target and proposal layers included): %.1f (%.1f, %.1f); peak memory %.2f GiB'
                  % (r['hip'] + (mem_p,)))
     lines.append('  eager torch ops (differentiable graph only, targets handed over as data): %.1f (%.1f, %.1f); peak memory %.2f GiB'
                  % (r['eager'] + (mem_e,)))
+    if f16x3:
+        lines.append('  forward_train, backward_precision=f16x3 (same forward; conv gradients by the 3 x f16 split): %.1f (%.1f, %.1f); '
+                     'f16x3 / fp32 backward step: %.3f' % (r['f16x3'] + (r['f16x3'][0] / r['hip'][0],)))
 
 
-def child(reps, step_reps, skip_step):
+def child(reps, step_reps, skip_step, f16x3=False):
     # torch starts HIP with this line, before the library loads: the process keeps the hardware-queue count of its environment
     lines = ['device: %s; the two sides alternate; a window is `inner` launches between two device events' % torch.cuda.get_device_name(0)]
     dev = benchlib.device()
     lines.append('clocks before: ' + benchlib.clocks())
     kernels(dev, reps, lines)
     if not skip_step:
-        step(dev, step_reps, lines)
+        step(dev, step_reps, lines, f16x3)
     lines.append('clocks after: ' + benchlib.clocks())
     print('\n'.join(lines))
 
@@ -241,7 +249,8 @@ def child(reps, step_reps, skip_step):
 def main():
     # the time limit: a run with the default arguments took 10 to 12 s, and 68 s as the first of its kind on a box
     benchlib.main(__file__, child, out='train_step_bench.txt', reps=30, timeout=300,
-                  extra=[('--step-reps', dict(type=int, default=10)), ('--skip-step', dict(action='store_true'))],
+                  extra=[('--step-reps', dict(type=int, default=10)), ('--skip-step', dict(action='store_true')),
+                         ('--f16x3', dict(action='store_true'))],     # the whole step also with backward_precision='f16x3', alternating
                   header='# python tools/train_step_bench.py --reps %(reps)d --step-reps %(step_reps)d   (see the tool for what each line measures)')
 
 
