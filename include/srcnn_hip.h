@@ -367,6 +367,55 @@ SRCNN_API int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspac
 SRCNN_API size_t srcnn_conv2d_backward_f16x3_workspace_bytes(const srcnn_conv_bwd_desc *d);
 SRCNN_API int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
+/* ------------------------------------------------- convolution forward, 3 x f16 split with device-found scales (training; opt-in)
+ *   y = relu?(conv(x, w) + bias + residual)
+ * for weights that change every step: fp32 x and w in, fp32 y out, the GEMM on v_mfma_f32_32x32x16_f16 (fp32 accumulation) with
+ * srcnn_conv2d_backward_f16x3's arithmetic and scales.  It is not srcnn_conv2d with precision 1 (prepared hi / lo weights, a
+ * host-known weight exponent, SPLIT16 activations), which stays as it is; neither call replaces the other.
+ * Layouts: x (B, H, W, *) NHWC with pixel stride x_cstride, channels [0, Cin) read and nothing behind them; w (Cout, KH, KW, Cin)
+ * fp32, BN already folded; y written at channels [y_coffset, y_coffset + Cout) of pixels of y_cstride floats, nothing else of y
+ * touched; bias (Cout) or NULL; residual dense (B, OH, OW, Cout) or NULL.
+ *
+ * SCHEME.  Every product is  a b ~ (a_hi b_hi + a_hi b_lo + a_lo b_hi) / (s_x s_w),  t = s v, hi = f16(t), lo = f16(t - hi), with
+ * one power of two per operand tensor, s = 2^(14 - floor(log2 max|v|)), exponent clamped to +-126.  Passes, one stream, in order:
+ * (1) the two max words in the workspace are cleared; (2) max|w| and (3) max|x| as float bits under an integer atomicMax; (4) w
+ * is split into two f16 planes (Cp, KH, KW, Cin), Cp = Cout rounded up to 32, rows beyond Cout zero -- K is already contiguous,
+ * nothing is transposed; (5) the implicit GEMM: rows = the B OH OW output pixels, columns = Cout, K = (kh, kw, 32-channel tiles of
+ * Cin).  x stays fp32 in memory and is split while it is staged into LDS; taps outside the image and rows beyond M enter as exact
+ * zeros.  Epilogue per element, every operation rounded once: (main + cross) * (1 / s_x) * (1 / s_w), + bias, + residual, ReLU;
+ * each element of y is stored exactly once.  No atomics other than the two max words, nothing read back by the host, no
+ * device-scope fence; the call can be captured into a graph.
+ * Scaling x or w by a power of two scales the GEMM's result by exactly that power, bit for bit (as long as nothing leaves the
+ * normal fp32 range); an all-zero x gives y = relu?(bias + residual) exactly.
+ *
+ * DEFINED SUMMATION ORDER (a function of the geometry alone: run-to-run bit-equal, and bit-equal across tile_mr / tile_nr, since K
+ * is never split and an element's K order does not depend on the tile that holds it).  K tiles over taps in (kh, kw) row-major
+ * order, inside a tap over the 32-channel tiles of Cin ascending; a K tile is two matrix steps of 16 channels.  Per step and
+ * element: cross += lo hi, main += hi hi, cross += hi lo (two fp32 accumulators; the 16 products of a step are summed by the
+ * matrix unit in its own fixed order).
+ * tile_mr / tile_nr in {1, 2} choose the (64 tile_mr) x (64 tile_nr) workgroup tile (0 = heuristic); any other value is an error.
+ *
+ * Errors, all before the first launch (SRCNN_ERR_ARG with the reason in srcnn_last_error(); SRCNN_ERR_WORKSPACE for a workspace
+ * smaller than srcnn_conv2d_forward_f16x3_workspace_bytes, which returns 0 for a descriptor the call would refuse): a null desc /
+ * x / w / y ("null"); non-positive sizes or OH, OW that are not the forward's ("shape"); Cin not a multiple of 32; strides too
+ * small or x_cstride not a multiple of 4 ("stride"); x or w not 16-byte aligned ("aligned"); a non-F32 format ("format"); a tile
+ * outside {0, 1, 2} ("tile").  The struct has no fused-head, second-input or upsample fields. */
+typedef struct srcnn_conv_fwd_f16x3_desc {
+    const float *x, *w;
+    const float *bias;         /* (Cout) or NULL */
+    const float *residual;     /* dense (B, OH, OW, Cout) or NULL */
+    float *y;
+    int B, H, W, Cin, x_cstride;
+    int OH, OW, Cout;
+    int KH, KW, stride, pad;
+    int y_cstride, y_coffset;
+    int relu;
+    int x_format, y_format;    /* must be SRCNN_FMT_F32 */
+    int tile_mr, tile_nr;      /* 0 = heuristic */
+} srcnn_conv_fwd_f16x3_desc;
+SRCNN_API size_t srcnn_conv2d_forward_f16x3_workspace_bytes(const srcnn_conv_fwd_f16x3_desc *d);
+SRCNN_API int srcnn_conv2d_forward_f16x3(const srcnn_conv_fwd_f16x3_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+
 /* ------------------------------------------------- training: remaining adjoints
  * The three differentiable operators of the reference's training branch that are neither a convolution, a ROIAlign nor a loss:
  * _upsample_add (stereo_rcnn.py:91-108), MaxPool2d(1, stride 2) (stereo_rcnn.py:39,168) and the layout step of

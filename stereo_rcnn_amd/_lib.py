@@ -67,6 +67,17 @@ class ConvBwdDesc(ctypes.Structure):
                 ("head_w", c_void_p), ("head_wf", c_void_p), ("x2", c_void_p), ("up_top", c_void_p)]
 
 
+class ConvFwdF16x3Desc(ctypes.Structure):
+    """struct srcnn_conv_fwd_f16x3_desc (include/srcnn_hip.h)."""
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("residual", c_void_p), ("y", c_void_p),
+                ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_cstride", c_int),
+                ("OH", c_int), ("OW", c_int), ("Cout", c_int),
+                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
+                ("y_cstride", c_int), ("y_coffset", c_int), ("relu", c_int),
+                ("x_format", c_int), ("y_format", c_int),
+                ("tile_mr", c_int), ("tile_nr", c_int)]
+
+
 class KittiSplit(ctypes.Structure):
     """struct srcnn_kitti_split (include/srcnn_hip.h): a ragged batch of frames, device pointers."""
     _fields_ = [("n_frames", c_int), ("max_det_per_frame", c_int),
@@ -152,6 +163,8 @@ _SIGNATURES = {
     "srcnn_conv2d_backward": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
     "srcnn_conv2d_backward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
     "srcnn_conv2d_backward_f16x3": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
+    "srcnn_conv2d_forward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvFwdF16x3Desc)]),
+    "srcnn_conv2d_forward_f16x3": (c_int, [ctypes.POINTER(ConvFwdF16x3Desc), c_void_p, c_size_t, c_void_p]),
     "srcnn_upsample_add_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_subsample2_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_pixel_shuffle2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

@@ -4,8 +4,10 @@ Every learnable layer of the network goes through the conv engine (the ResNet an
 the linear heads, the keypoint tower).  These functions are that engine with a backward: the forward is `engine.conv2d(...,
 precision='f32')`, the backward `engine.conv2d_backward` (srcnn_conv2d_backward: dx, dw, db on the fp32 MFMA; include/srcnn_hip.h
 states the sums and their order) or, with backward_precision='f16x3', srcnn_conv2d_backward_f16x3 (the same gradients by the
-error-compensated 3 x f16 split; the forward stays the exact-fp32 engine: an f16x3 forward needs its weight-scale exponent on the
-host, a host read per layer and step).  Tensors are NCHW at the edge and NHWC inside, like the ROIAlign modules.  Nothing here waits for
+error-compensated 3 x f16 split).  forward_precision='f16x3' runs the forward as `engine.conv2d_train_f16x3`
+(srcnn_conv2d_forward_f16x3): the same split with the scales of x and w found on the device inside the call, so no exponent is
+read by the host; the two precisions are independent, and the backward reads the saved x, w and the forward's own y (the ReLU
+mask) whichever engine wrote it.  Tensors are NCHW at the edge and NHWC inside, like the ROIAlign modules.  Nothing here waits for
 the device.  CPU tensors raise NotImplementedError, as the project's other ops.
 
 conv2d_nhwc is the same convolution NHWC to NHWC: a graph of many layers (stereo_rcnn_amd.training) stays in the engine's layout
@@ -29,17 +31,21 @@ class _Conv2dNHWC(torch.autograd.Function):
     (B, OH, OW, Cout) or None; all contiguous float32 on the device."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32'):
+    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32', forward_precision='f32'):
         if backward_precision not in ('f32', 'f16x3'):
             raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
+        _check_forward_precision(forward_precision)
         ctx.backward_precision = backward_precision
         B, H, W, cin = (int(v) for v in x.shape)
         cout, kh, kw = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         cw = engine.ConvW(weight.detach(), None if bias is None else bias.detach(), kh, kw, stride, pad, relu)
         OH, OW = engine.conv_out_hw(H, W, kh, kw, stride, pad)
         y = torch.empty((B, OH, OW, cout), dtype=torch.float32, device=x.device)
-        engine.conv2d(cw, x.detach(), B, H, W, y, OH, OW, residual=None if residual is None else residual.detach(),
-                      precision='f32', plan=(0, 0, 0, 0, 0))
+        res = None if residual is None else residual.detach()
+        if forward_precision == 'f16x3':
+            engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res)
+        else:
+            engine.conv2d(cw, x.detach(), B, H, W, y, OH, OW, residual=res, precision='f32', plan=(0, 0, 0, 0, 0))
         ctx.save_for_backward(x, weight, y if relu else None)
         ctx.geom = (B, H, W, OH, OW, kh, kw, stride, pad, bool(relu), bias is not None, residual is not None)
         return y
@@ -58,7 +64,12 @@ class _Conv2dNHWC(torch.autograd.Function):
         if want or g_out is not None:
             cw = engine.ConvW(weight, None, kh, kw, stride, pad, relu)
             res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out, precision=ctx.backward_precision)
-        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None, None, None, None, None)
+        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None, None, None, None, None, None)
+
+
+def _check_forward_precision(forward_precision):
+    if forward_precision not in ('f32', 'f16x3'):
+        raise ValueError("forward_precision must be 'f32' or 'f16x3' (got %r)" % (forward_precision,))
 
 
 def _check(x, weight):
@@ -102,43 +113,46 @@ def _fold(weight_eng, bias, bn):
     return w, b
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32'):
+def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32'):
     """relu?(bn?(conv2d(x, weight) + bias) + residual) on the exact-fp32 engine, differentiable with respect to x, weight, bias
     and residual.  x (B, Cin, H, W) with Cin a multiple of 32, weight (Cout, Cin, KH, KW) as nn.Conv2d holds it, residual
     (B, Cout, OH, OW); bn: a dict with 'weight', 'bias', 'running_mean', 'running_var' -- the frozen BatchNorm that follows the
-    convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients (the forward is
-    the exact-fp32 engine either way).  Returns (B, Cout, OH, OW)."""
+    convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients; forward_precision:
+    'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError).  Returns (B, Cout, OH, OW)."""
+    _check_forward_precision(forward_precision)
     _check(x, weight)
     if int(x.shape[1]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[1]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     r = None if residual is None else _ToNHWC.apply(residual)
-    y = _Conv2dNHWC.apply(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision)
+    y = _Conv2dNHWC.apply(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision, forward_precision)
     return _ToNCHW.apply(y)
 
 
-def linear(x, weight, bias=None, relu=False, backward_precision='f32'):
+def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32'):
     """relu?(x @ weight.T + bias) as a 1x1 convolution over an (n, 1, 1, K) tensor: x (n, K), weight (out, K) as nn.Linear holds
     it.  K must be a multiple of 32."""
+    _check_forward_precision(forward_precision)
     _check(x, weight)
     n, K = int(x.shape[0]), int(x.shape[1])
     if K % 32 != 0:
         raise ValueError("linear: K must be a multiple of 32 (got %d)" % K)
     out = int(weight.shape[0])
     y = _Conv2dNHWC.apply(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu),
-                          backward_precision)
+                          backward_precision, forward_precision)
     return y.view(n, out)
 
 
-def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32'):
+def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32'):
     """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
     (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back)."""
+    _check_forward_precision(forward_precision)
     _check(x, weight)
     if int(x.shape[3]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     return _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
-                             int(stride), int(padding), bool(relu), backward_precision)
+                             int(stride), int(padding), bool(relu), backward_precision, forward_precision)
 
 
 def _check_nhwc(x, what):
@@ -242,12 +256,13 @@ class _PixelShuffle2(torch.autograd.Function):
         return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
 
 
-def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'):
+def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32'):
     """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
     nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
     engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
     with the shuffle and stays in the convolution's epilogue.  Backward: the inverse shuffle of dy, then the convolution's
     backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups."""
+    _check_forward_precision(forward_precision)
     _check(x, weight)
     cin, cout = int(weight.shape[0]), int(weight.shape[1])
     if tuple(weight.shape[2:]) != (2, 2) or int(x.shape[3]) != cin:
@@ -256,5 +271,5 @@ def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'
         raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
     w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
     b = None if bias is None else bias.repeat(4)
-    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision)
+    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision, forward_precision)
     return _PixelShuffle2.apply(y, cout)

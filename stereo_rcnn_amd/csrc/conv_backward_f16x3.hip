@@ -47,70 +47,18 @@
 //   dw: K tiles of 32 pixels in ascending m inside the slice, the same two accumulators, main + cross, * 1/s_g, * 1/s_x; the
 //       slices' (already rescaled) sums are added in ascending slice order by wgrad_reduce_kernel.
 //   Inside one MFMA step the 16 products are summed by the matrix unit in its own fixed order.
+//
+// pow2_scale, split_f16, f16x3_clear_scales, absmax_kernel and the K tile's MFMA loop live in conv_f16x3_scaled.h, shared with the
+// training forward (conv_forward_f16x3.hip).
 #include "conv_backward_common.h"
+#include "conv_f16x3_scaled.h"
 
 namespace srcnn {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-
-constexpr int HROW = BK;           // halves per LDS row (64 B; 16-byte chunks XOR-swizzled with (row >> 2) & 3)
-constexpr int F16X3_TOP = 14;      // a tensor's largest |element| is scaled into [2^14, 2^15): below f16's 65504 after rounding
 
 struct F16x3Args {
     _Float16 *wt_hi, *wt_lo;       // workspace: re-laid weights (Cin, taps, Cp), hi and lo plane
     unsigned *amax;                // workspace: float bits of max|g|, max|w|, max|x|
 };
-
-struct Pow2 {
-    float s, inv;
-};
-
-// s = 2^(TOP - floor(log2 max)) and 1 / s, exponent clamped to +-126 so that both are normal floats; a zero (or subnormal) max
-// gives the clamp
-__device__ __forceinline__ Pow2 pow2_scale(unsigned maxbits)
-{
-    const int e = (int)(maxbits >> 23) - 127;
-    const int sh = min(max(F16X3_TOP - e, -126), 126);
-    Pow2 r;
-    r.s = __uint_as_float((unsigned)(127 + sh) << 23);
-    r.inv = __uint_as_float((unsigned)(127 - sh) << 23);
-    return r;
-}
-
-__device__ __forceinline__ void split_f16(float v, float s, _Float16 &hi, _Float16 &lo)
-{
-    const float t = v * s;              // exact: a power of two
-    hi = (_Float16)t;                   // round to nearest even
-    lo = (_Float16)(t - (float)hi);     // the residual is exact in fp32
-}
-
-__global__ void f16x3_clear_scales(unsigned *amax)
-{
-    if (threadIdx.x < 4) amax[threadIdx.x] = 0u;
-}
-
-// max |v| over `rows` rows of `len` floats at a stride of `stride` floats.  VEC: len, stride multiples of 4 and a 16-byte aligned base
-template <bool VEC>
-__global__ __launch_bounds__(256) void absmax_kernel(const float *v, long long rows, int len, long long stride, unsigned *word)
-{
-    const int per_row = VEC ? len / 4 : len;
-    const long long total = rows * per_row;
-    float mx = 0.f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long r = i / per_row;
-        const float *ptr = v + r * stride + (i - r * per_row) * (VEC ? 4 : 1);
-        if (VEC) {
-            const float4 f = *reinterpret_cast<const float4 *>(ptr);
-            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(f.x), fabsf(f.y))), fmaxf(fabsf(f.z), fabsf(f.w)));
-        } else {
-            mx = fmaxf(mx, fabsf(*ptr));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(word, __float_as_uint(mx));
-}
 
 // bwd_weight_relayout with the split: grid (Cin / 32, Cp / 32, taps), block (32, 8)
 __global__ __launch_bounds__(256) void bwd_weight_relayout_split(const BwdArgs p, const F16x3Args q)
@@ -133,42 +81,6 @@ __global__ __launch_bounds__(256) void bwd_weight_relayout_split(const BwdArgs p
         const size_t o = ((size_t)c * p.taps + tap) * p.Cp + n0 + tx;
         q.wt_hi[o] = hi;
         q.wt_lo[o] = lo;
-    }
-}
-
-// One K tile out of an LDS buffer of four panels [A_hi | A_lo | B_hi | B_lo] of swizzled 64-byte rows (conv_f16x3_kernel's layout):
-// two MFMA steps; the cross terms go into accx, hi hi into acc, so consecutive MFMAs never share an accumulator.
-template <int MR, int NR>
-__device__ __forceinline__ void f16x3_ktile(const _Float16 *buf, const WaveGeom &g, floatx16 (&acc)[MR][NR], floatx16 (&accx)[MR][NR])
-{
-    constexpr int PANEL_A = 64 * MR * HROW, PANEL_B = 64 * NR * HROW;
-    const int r_sw = (g.lg ^ ((g.li >> 2) & 3)) << 3;     // chunk kk * 2 + lg swizzled; kk = 1 flips bit 4 (halves)
-    const _Float16 *sah = buf + (g.wm * 32 * MR + g.li) * HROW + r_sw;
-    const _Float16 *sal = sah + PANEL_A;
-    const _Float16 *sbh = buf + 2 * PANEL_A + (g.wn * 32 * NR + g.li) * HROW + r_sw;
-    const _Float16 *sbl = sbh + PANEL_B;
-#pragma unroll
-    for (int kk = 0; kk < BK / 16; ++kk) {
-        const int ko = kk ? ((r_sw ^ 16) - r_sw) : 0;
-        half8 ah[MR], al[MR], bh[NR], bl[NR];
-#pragma unroll
-        for (int i = 0; i < MR; ++i) {
-            ah[i] = *reinterpret_cast<const half8 *>(sah + i * 32 * HROW + ko);
-            al[i] = *reinterpret_cast<const half8 *>(sal + i * 32 * HROW + ko);
-        }
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            bh[j] = *reinterpret_cast<const half8 *>(sbh + j * 32 * HROW + ko);
-            bl[j] = *reinterpret_cast<const half8 *>(sbl + j * 32 * HROW + ko);
-        }
-#pragma unroll
-        for (int i = 0; i < MR; ++i)
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], accx[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], accx[i][j], 0, 0, 0);
-            }
     }
 }
 
@@ -412,15 +324,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16x3_kernel(const BwdArgs 
             }
         }
     }
-}
-
-static void launch_absmax(const float *v, long long rows, int len, long long stride, unsigned *word, hipStream_t st)
-{
-    const bool vec = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && len % 4 == 0 && stride % 4 == 0;
-    const long long total = rows * (vec ? len / 4 : len);
-    const unsigned blocks = (unsigned)min(1024LL, (total + 255) / 256);
-    if (vec) SRCNN_LAUNCH(absmax_kernel<true>, dim3(blocks), dim3(256), 0, st, v, rows, len, stride, word);
-    else SRCNN_LAUNCH(absmax_kernel<false>, dim3(blocks), dim3(256), 0, st, v, rows, len, stride, word);
 }
 
 }  // namespace srcnn

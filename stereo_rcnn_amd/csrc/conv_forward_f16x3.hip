@@ -1,0 +1,292 @@
+// Training forward, error-compensated 3 x f16 form: y = relu?(conv(x, w) + bias + residual) on the f16 matrix pipe
+// (v_mfma_f32_32x32x16_f16, fp32 accumulation) with the scales of conv_backward_f16x3.hip -- one power of two per operand tensor,
+// found on the device -- so that weights that change every step need no prepared planes, no calibrated activation scale and no
+// exponent on the host.  include/srcnn_hip.h states the definitions; nothing here is derived from the reference (it calls cuDNN).
+// The inference f16x3 engine (conv_f16x3.hip, conv_f16s*) is another thing: prepared weights, host-known exponents, SPLIT16.
+//
+// ARITHMETIC.  conv_backward_f16x3.hip's, from the same header (conv_f16x3_scaled.h): t = s v, hi = f16(t), lo = f16(t - hi), every
+// product hi hi + hi lo + lo hi, s = 2^(14 - floor(log2 max|v|)) with the exponent clamped to +-126; one s for x, one for w.
+//
+//   f16x3_clear_scales       the max words <- 0
+//   absmax_kernel            max|w|, max|x| (x: channels [0, Cin) of every pixel; floats behind Cin are not read)
+//   fwd_weight_split         w (Cout, taps, Cin) fp32 -> w_hi, w_lo (Cp, taps, Cin) f16, rows [Cout, Cp) zero.  K is already
+//                            contiguous in the engine's layout: no transpose
+//   conv_fwd_f16x3_kernel    conv_dgrad_f16x3_kernel's tile, panels and MFMA loop with the forward's gather: rows = the B OH OW
+//                            output pixels, columns = Cout.  x stays fp32 in memory and is split while it is staged into LDS;
+//                            taps outside the image and rows beyond M are staged as zeros, whose halves are exact zeros.
+//
+// SUMMATION ORDER (fixed by the geometry alone: never split, and an element's K order does not depend on the tile it falls in).
+//   K tiles over taps in (kh, kw) row-major order, inside a tap the 32-channel tiles of Cin ascending; a K tile is two MFMA steps
+//   of 16 channels.  Per step cross += lo hi, main += hi hi, cross += hi lo; at the end (main + cross) * 1/s_x * 1/s_w, + bias,
+//   + residual, ReLU, each rounded once.  Inside one MFMA step the 16 products are summed by the matrix unit in its own fixed order.
+//
+// No atomics other than the two max words (whose result no order can change), no host read, no device-scope fence: every kernel
+// reads what an earlier kernel of the same stream completed.
+#include "conv_f16x3_scaled.h"
+
+namespace srcnn {
+
+struct FwdArgs {
+    const float *x, *w, *bias, *res;
+    float *y;
+    _Float16 *w_hi, *w_lo;         // workspace: the weights' hi and lo plane (Cp, Kw)
+    unsigned *amax;                // workspace: float bits of max|x|, max|w|
+    int H, W, Cin, xcs;
+    int OH, OW, Cout, Cp;
+    int KH, KW, stride, pad;
+    int ycs, yco, relu;
+    int M, Min;                    // output pixels B OH OW, input pixels B H W
+    int taps, Kw;                  // KH KW, taps * Cin
+    int ctiles, nkt, mtiles, ntiles;
+};
+
+struct FwdPlan {
+    int mr, nr;
+    size_t off_hi, off_lo, off_scale, bytes;
+};
+
+// one thread per 4 consecutive k of one row of the (Cp, Kw) planes
+__global__ __launch_bounds__(256) void fwd_weight_split(const FwdArgs p)
+{
+    const int per_row = p.Kw / 4;
+    const long long total = (long long)p.Cp * per_row;
+    const float s = pow2_scale(p.amax[1]).s;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int n = (int)(i / per_row);
+        float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n < p.Cout) f = *reinterpret_cast<const float4 *>(p.w + i * 4);
+        const float v[4] = {f.x, f.y, f.z, f.w};
+        half4 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            _Float16 h, l;
+            split_f16(v[e], s, h, l);
+            hi[e] = h;
+            lo[e] = l;
+        }
+        *reinterpret_cast<half4 *>(p.w_hi + i * 4) = hi;
+        *reinterpret_cast<half4 *>(p.w_lo + i * 4) = lo;
+    }
+}
+
+template <int MR, int NR>
+__global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
+{
+    constexpr int BM = 64 * MR, BN = 64 * NR;
+    constexpr int A_LD = BM / 32;   // float4 loads per thread per tile (A, fp32)
+    constexpr int B_LD = BN / 64;   // uint4 loads per thread per tile and per panel (B, f16)
+    constexpr int PANEL_A = BM * HROW, PANEL_B = BN * HROW;
+    __shared__ __attribute__((aligned(16))) _Float16 smem[2][2 * PANEL_A + 2 * PANEL_B];
+
+    const int t = threadIdx.x;
+    const int logical = xcd_logical_tile(blockIdx.x, p.mtiles * p.ntiles);
+    const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
+    const int m0 = mt * BM, n0 = nt * BN;
+    const Pow2 sx = pow2_scale(p.amax[0]), sw = pow2_scale(p.amax[1]);
+
+    // A: the forward's gather (rows = output pixels); a row beyond M never passes the image test
+    const int lrow = t >> 3, lcol = (t & 7) * 4;
+    int ih0[A_LD], iw0[A_LD], pix0[A_LD];
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+        const int m = m0 + lrow + 32 * i;
+        if (m < p.M) {
+            const int ohw = p.OH * p.OW;
+            const int b = m / ohw;
+            const int rem = m - b * ohw;
+            const int oh = rem / p.OW;
+            ih0[i] = oh * p.stride - p.pad;
+            iw0[i] = (rem - oh * p.OW) * p.stride - p.pad;
+            pix0[i] = (b * p.H + ih0[i]) * p.W + iw0[i];
+        } else {
+            ih0[i] = -(1 << 28);
+            iw0[i] = 0;
+            pix0[i] = 0;
+        }
+    }
+    // B: two f16 panels (rows = output channels of the Cp-row planes, K = taps * Cin contiguous)
+    const int brow = t >> 2, bcol = (t & 3) * 8;
+    const _Float16 *bh_ptr[B_LD], *bl_ptr[B_LD];
+    bool b_ok[B_LD];
+#pragma unroll
+    for (int i = 0; i < B_LD; ++i) {
+        const int n = n0 + brow + 64 * i;
+        b_ok[i] = n < p.Cp;
+        const size_t off = (size_t)(b_ok[i] ? n : 0) * p.Kw + bcol;
+        bh_ptr[i] = p.w_hi + off;
+        bl_ptr[i] = p.w_lo + off;
+    }
+    const int a_sw = ((((t & 7) >> 1) ^ ((lrow >> 2) & 3)) << 3) + ((t & 1) << 2);
+    const int b_sw = ((t & 3) ^ ((brow >> 2) & 3)) << 3;
+
+    float4 ra[A_LD];
+    uint4 rbh[B_LD], rbl[B_LD];
+    auto load_tile = [&](int kt) {
+        const int tap = kt / p.ctiles;
+        const int c0 = (kt - tap * p.ctiles) * BK;
+        const int kh = tap / p.KW;
+        const int kw = tap - kh * p.KW;
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) {
+            const int ih = ih0[i] + kh, iw = iw0[i] + kw;
+            const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+            const int pix = ok ? pix0[i] + kh * p.W + kw : 0;
+            const float4 v = *reinterpret_cast<const float4 *>(p.x + (size_t)pix * p.xcs + c0 + lcol);
+            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const uint4 vh = *reinterpret_cast<const uint4 *>(bh_ptr[i] + (size_t)kt * BK);
+            const uint4 vl = *reinterpret_cast<const uint4 *>(bl_ptr[i] + (size_t)kt * BK);
+            rbh[i] = b_ok[i] ? vh : make_uint4(0, 0, 0, 0);
+            rbl[i] = b_ok[i] ? vl : make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto store_tile = [&](int buf) {
+        _Float16 *sah = smem[buf], *sal = smem[buf] + PANEL_A;
+        _Float16 *sbh = smem[buf] + 2 * PANEL_A, *sbl = sbh + PANEL_B;
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) {
+            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
+            half4 hi, lo;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                _Float16 h, l;
+                split_f16(v[e], sx.s, h, l);
+                hi[e] = h;
+                lo[e] = l;
+            }
+            const int o = (lrow + 32 * i) * HROW + a_sw;
+            *reinterpret_cast<half4 *>(sah + o) = hi;
+            *reinterpret_cast<half4 *>(sal + o) = lo;
+        }
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const int o = (brow + 64 * i) * HROW + b_sw;
+            *reinterpret_cast<uint4 *>(sbh + o) = rbh[i];
+            *reinterpret_cast<uint4 *>(sbl + o) = rbl[i];
+        }
+    };
+
+    const WaveGeom g(t);
+    floatx16 acc[MR][NR], accx[MR][NR];
+    zero_acc(acc);
+    zero_acc(accx);
+    ktile_pipeline(0, p.nkt, load_tile, store_tile, [&](int buf) { f16x3_ktile(smem[buf], g, acc, accx); });
+
+    // every (row, col) of the tile inside (M, Cout) is stored once; the 32 lanes of a row write 128 contiguous bytes
+#pragma unroll
+    for (int i = 0; i < MR; ++i) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int col = c_col<NR>(g, n0, j);
+            if (col >= p.Cout) continue;
+            const float bv = p.bias ? p.bias[col] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = c_row<MR>(g, m0, i, e);
+                if (row >= p.M) continue;
+                float v = (acc[i][j][e] + accx[i][j][e]) * sx.inv * sw.inv;
+                if (p.bias) v += bv;
+                if (p.res) v += p.res[(size_t)row * p.Cout + col];
+                if (p.relu) v = fmaxf(v, 0.f);
+                p.y[(size_t)row * p.ycs + p.yco + col] = v;
+            }
+        }
+    }
+}
+
+// Validates the descriptor and lays out the call (workspace pointers are bound by the caller)
+static int fwd_prepare(const srcnn_conv_fwd_f16x3_desc *d, FwdArgs &a, FwdPlan &pl)
+{
+    SRCNN_REQUIRE(d != nullptr, "null descriptor");
+    SRCNN_REQUIRE(d->x != nullptr, "null pointer: x");
+    SRCNN_REQUIRE(d->w != nullptr, "null pointer: w");
+    SRCNN_REQUIRE(d->y != nullptr, "null pointer: y");
+    SRCNN_REQUIRE(d->x_format == SRCNN_FMT_F32 && d->y_format == SRCNN_FMT_F32, "format must be SRCNN_FMT_F32");
+    SRCNN_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->Cin > 0, "bad shape: sizes must be positive");
+    SRCNN_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "bad shape: kernel, stride > 0 and pad >= 0");
+    SRCNN_REQUIRE(d->H + 2 * d->pad >= d->KH && d->W + 2 * d->pad >= d->KW &&
+                      d->OH == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
+                  "bad shape: OH / OW are not the forward's output size");
+    SRCNN_REQUIRE(d->Cin % BK == 0, "Cin must be a positive multiple of 32");
+    SRCNN_REQUIRE(d->x_cstride >= d->Cin && d->x_cstride % 4 == 0, "x_cstride: a stride of at least Cin floats, a multiple of 4");
+    SRCNN_REQUIRE(d->y_coffset >= 0 && d->y_cstride >= d->y_coffset + d->Cout, "y_cstride: a stride of at least y_coffset + Cout floats");
+    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "x must be 16-byte aligned (stride-4 vector loads)");
+    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(d->w) & 15) == 0, "w must be 16-byte aligned (vector loads)");
+    SRCNN_REQUIRE((unsigned)d->tile_mr <= 2 && (unsigned)d->tile_nr <= 2, "tile_mr / tile_nr must be 0, 1 or 2");
+    const long long M = (long long)d->B * d->OH * d->OW, Min = (long long)d->B * d->H * d->W;
+    const long long Kw = (long long)d->KH * d->KW * d->Cin;
+    SRCNN_REQUIRE(M < (1LL << 31) && Min < (1LL << 31) && Kw < (1LL << 31) && d->Cout < (1 << 20) && d->KH < 256 && d->KW < 256,
+                  "bad shape: tensor too large");
+
+    a.x = d->x; a.w = d->w; a.bias = d->bias; a.res = d->residual; a.y = d->y;
+    a.w_hi = a.w_lo = nullptr; a.amax = nullptr;
+    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
+    a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+    a.ycs = d->y_cstride; a.yco = d->y_coffset; a.relu = d->relu ? 1 : 0;
+    a.M = (int)M; a.Min = (int)Min; a.taps = d->KH * d->KW; a.Kw = (int)Kw;
+
+    // the engine's rule: the largest tile that still gives two workgroups per CU
+    choose_tile_4w(a.M, a.Cout, &pl.mr, &pl.nr);
+    if (d->tile_mr > 0 && d->tile_nr > 0) {
+        pl.mr = d->tile_mr;
+        pl.nr = d->tile_nr;
+    }
+    a.ctiles = a.Cin / BK;
+    a.nkt = a.taps * a.ctiles;
+    a.mtiles = cdiv(a.M, 64 * pl.mr);
+    a.ntiles = cdiv(a.Cout, 64 * pl.nr);
+    SRCNN_REQUIRE((long long)a.mtiles * a.ntiles < (1LL << 31), "bad shape: tensor too large");
+
+    const size_t plane = align_up((size_t)a.Cp * a.Kw * sizeof(_Float16), 256);
+    pl.off_hi = 0;
+    pl.off_lo = plane;
+    pl.off_scale = 2 * plane;
+    pl.bytes = 2 * plane + 256;
+    return SRCNN_OK;
+}
+
+}  // namespace srcnn
+
+extern "C" {
+
+size_t srcnn_conv2d_forward_f16x3_workspace_bytes(const srcnn_conv_fwd_f16x3_desc *d)
+{
+    using namespace srcnn;
+    FwdArgs a;
+    FwdPlan pl;
+    if (fwd_prepare(d, a, pl) != SRCNN_OK) return 0;
+    return pl.bytes;
+}
+
+int srcnn_conv2d_forward_f16x3(const srcnn_conv_fwd_f16x3_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
+{
+    using namespace srcnn;
+    FwdArgs a;
+    FwdPlan pl;
+    int rc = fwd_prepare(d, a, pl);
+    if (rc != SRCNN_OK) return rc;
+    if (!workspace || workspace_bytes < pl.bytes) {
+        set_error("srcnn_conv2d_forward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
+        return SRCNN_ERR_WORKSPACE;
+    }
+    char *ws = static_cast<char *>(workspace);
+    a.w_hi = reinterpret_cast<_Float16 *>(ws + pl.off_hi);
+    a.w_lo = reinterpret_cast<_Float16 *>(ws + pl.off_lo);
+    a.amax = reinterpret_cast<unsigned *>(ws + pl.off_scale);
+
+    hipStream_t st = as_stream(stream);
+    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, a.amax);
+    launch_absmax(a.w, a.Cout, a.Kw, a.Kw, a.amax + 1, st);
+    launch_absmax(a.x, a.Min, a.Cin, a.xcs, a.amax, st);
+    const long long groups = (long long)a.Cp * (a.Kw / 4);
+    SRCNN_LAUNCH(fwd_weight_split, dim3((unsigned)min(2048LL, (groups + 255) / 256)), dim3(256), 0, st, a);
+    dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
+        SRCNN_LAUNCH((conv_fwd_f16x3_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.mtiles * a.ntiles), dim3(256), 0, st, a);
+    });
+    return check_launch("srcnn_conv2d_forward_f16x3");
+}
+
+}  // extern "C"

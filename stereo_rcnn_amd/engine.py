@@ -741,6 +741,33 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     return res
 
 
+def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None, y_cstride=None, y_coffset=0, relu=None, tile=None):
+    """The training forward on the f16 matrix pipe (srcnn_conv2d_forward_f16x3): y = relu?(conv(x, w) + bias + residual) by the 3 x f16
+    split with one power-of-two scale for x and one for w, both found on the device inside the call -- the scheme of
+    conv2d_backward(precision='f16x3').  cw: an engine.ConvW holding the plain fp32 weights (Cout, KH, KW, Cin) (BN folded) and
+    bias, mode 0; no prepared planes, no host-side exponent.  x (B, H, W, *) and y (B, OH, OW, *) are raw NHWC float32 device
+    tensors; residual dense (B, OH, OW, Cout).  tile: (tile_mr, tile_nr).  It is not conv2d(precision='f16x3'), the inference
+    engine, and never runs in its place or lets it run in its own."""
+    L = _lib.lib()
+    assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a training forward"
+    d = _lib.ConvFwdF16x3Desc()
+    d.x, d.w, d.y = x.data_ptr(), cw.weight.data_ptr(), y.data_ptr()
+    d.bias = cw.bias.data_ptr() if cw.bias is not None else None
+    d.residual = residual.data_ptr() if residual is not None else None
+    d.B, d.H, d.W, d.Cin = B, H, W, cw.cin
+    d.x_cstride = cw.cin if x_cstride is None else x_cstride
+    d.OH, d.OW, d.Cout = OH, OW, cw.cout
+    d.KH, d.KW, d.stride, d.pad = cw.kh, cw.kw, cw.stride, cw.pad
+    d.y_cstride = cw.cout if y_cstride is None else y_cstride
+    d.y_coffset = y_coffset
+    d.relu = cw.relu if relu is None else int(relu)
+    if tile is not None:
+        d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
+    ws = _lib.workspace(L.srcnn_conv2d_forward_f16x3_workspace_bytes(ctypes.byref(d)), x.device, "conv_forward_f16x3")
+    _lib.check(L.srcnn_conv2d_forward_f16x3(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_forward_f16x3")
+    return y
+
+
 def chain_enabled():
     if BOTTLENECK_CHAIN == 'auto':
         from . import streams

@@ -14,6 +14,8 @@ pipeline and kitti_eval, <save_dir>/ap_epoch<E>.json is written and the Car Mode
 is bit-identical with and without it.
 --backward-precision f32|f16x3 (default f32; logged in trainlog.txt): the engine of the convolution gradients
 (training.train_step's backward_precision).
+--forward-precision f32|f16x3 (default f32; logged in trainlog.txt only when it is not the default): the engine of the forward of
+every convolution / linear layer that has a graph (training.train_step's forward_precision; srcnn_conv2d_forward_f16x3).
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -56,7 +58,10 @@ def parse_args(argv=None):
     p.add_argument('--val-every', dest='val_every', default=1, type=int, help='unit: epoch')
     p.add_argument('--val-precision', dest='val_precision', choices=['f16x3', 'f32'], default='f16x3')
     p.add_argument('--backward-precision', dest='backward_precision', choices=['f32', 'f16x3'], default='f32',
-                   help='engine of the convolution gradients: the exact fp32 backward, or the 3 x f16 split (the forward is fp32 either way)')
+                   help='engine of the convolution gradients: the exact fp32 backward, or the 3 x f16 split (independent of --forward-precision)')
+    p.add_argument('--forward-precision', dest='forward_precision', choices=['f32', 'f16x3'], default='f32',
+                   help='engine of the training forward of the layers that have a graph: the exact fp32 engine, or the 3 x f16 split '
+                        'with scales found on the device')
     return p.parse_args(argv)
 
 
@@ -92,6 +97,8 @@ def main(argv=None):
 
     log_string('{:d} roidb entries'.format(train_size))
     log_string('backward precision: %s' % args.backward_precision)
+    if args.forward_precision != 'f32':
+        log_string('forward precision: %s' % args.forward_precision)
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
@@ -135,7 +142,7 @@ def main(argv=None):
                 if step >= iters_per_epoch:              # trainval_net.py:183,194: the leftover samples are not trained on
                     break
                 res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
-                                          backward_precision=args.backward_precision)
+                                          backward_precision=args.backward_precision, forward_precision=args.forward_precision)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))

@@ -18,6 +18,10 @@ and maximum of --reps windows are reported per launch.  The clocks rocm-smi show
 Runner and timer: tools/benchlib.py.
 
     python tools/train_step_bench.py [--reps 30] [--step-reps 10] [--skip-step] [--out profiles/train_step_bench.txt]
+    python tools/train_step_bench.py --forward-f16x3 --out profiles/train_step_f16x3_forward_bench.txt
+
+--forward-f16x3 adds two legs that alternate with the fp32-forward step in the same rounds: forward_precision='f16x3' with the fp32
+backward, and with the f16x3 backward; their six losses are printed beside the fp32 forward's.
 """
 import torch
 import torch.nn.functional as F
@@ -164,7 +168,7 @@ def eager_step(model, im_left, im_right, im_height, taps, fixed_blocks):
     return list(rpn_losses) + list(rcnn_losses)
 
 
-def step(dev, reps, lines, f16x3=False):
+def step(dev, reps, lines, f16x3=False, forward_f16x3=False):
     from stereo_rcnn_amd import fixture, training
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
     from stereo_rcnn_amd.model.utils.config import cfg
@@ -206,6 +210,12 @@ def step(dev, reps, lines, f16x3=False):
         clear()
         sum(training.forward_train(model, *args, generator=gen, backward_precision='f16x3')[8:14]).backward()
 
+    def product_fwd16(bp):
+        def run():
+            clear()
+            sum(training.forward_train(model, *args, generator=gen, forward_precision='f16x3', backward_precision=bp)[8:14]).backward()
+        return run
+
     def eager():
         clear()
         sum(eager_step(model, im_l, im_r, float(Hh), data, cfg.RESNET.FIXED_BLOCKS)).backward()
@@ -213,6 +223,11 @@ def step(dev, reps, lines, f16x3=False):
     e_losses = eager_step(model, im_l, im_r, float(Hh), data, cfg.RESNET.FIXED_BLOCKS)
     lines.append('six losses, product (one draw of the dropout masks): ' + ' '.join('%.5f' % float(v.detach()) for v in first[8:14]))
     lines.append('six losses, eager  (its own dropout draw)          : ' + ' '.join('%.5f' % float(v.detach()) for v in e_losses))
+    if forward_f16x3:
+        gen16 = torch.Generator(device=dev).manual_seed(1)
+        first16 = training.forward_train(model, *args, generator=gen16, forward_precision='f16x3')
+        lines.append('six losses, product, forward_precision=f16x3 (same seed)  : ' + ' '.join('%.5f' % float(v.detach()) for v in first16[8:14]))
+        del first16
     del first, e_losses
     torch.cuda.reset_peak_memory_stats()
     product()
@@ -223,6 +238,8 @@ def step(dev, reps, lines, f16x3=False):
     torch.cuda.synchronize()
     mem_e = torch.cuda.max_memory_allocated() / 2.0 ** 30
     versions = [('hip', product), ('eager', eager)] + ([('f16x3', product_f16x3)] if f16x3 else [])
+    if forward_f16x3:
+        versions += [('fwd16', product_fwd16('f32')), ('fwd16_bwd16', product_fwd16('f16x3'))]
     r = {k: benchlib.stats(v) for k, v in benchlib.alternating(versions, reps, warmup=2).items()}
     lines.append('forward + backward of the training step, ResNet-101, 600 x 1987, B = 1, %d alternating runs, ms: median (min, max)' % reps)
     lines.append('  forward_train (exact-fp32 engine, target and proposal layers included): %.1f (%.1f, %.1f); peak memory %.2f GiB'
@@ -232,16 +249,21 @@ def step(dev, reps, lines, f16x3=False):
     if f16x3:
         lines.append('  forward_train, backward_precision=f16x3 (same forward; conv gradients by the 3 x f16 split): %.1f (%.1f, %.1f); '
                      'f16x3 / fp32 backward step: %.3f' % (r['f16x3'] + (r['f16x3'][0] / r['hip'][0],)))
+    if forward_f16x3:
+        lines.append('  forward_train, forward_precision=f16x3, fp32 backward (trainable convs and linears forward by the 3 x f16 split): '
+                     '%.1f (%.1f, %.1f); / fp32-forward step: %.3f' % (r['fwd16'] + (r['fwd16'][0] / r['hip'][0],)))
+        lines.append('  forward_train, forward_precision=f16x3, backward_precision=f16x3: %.1f (%.1f, %.1f); / fp32-forward step: %.3f'
+                     % (r['fwd16_bwd16'] + (r['fwd16_bwd16'][0] / r['hip'][0],)))
 
 
-def child(reps, step_reps, skip_step, f16x3=False):
+def child(reps, step_reps, skip_step, f16x3=False, forward_f16x3=False):
     # torch starts HIP with this line, before the library loads: the process keeps the hardware-queue count of its environment
     lines = ['device: %s; the two sides alternate; a window is `inner` launches between two device events' % torch.cuda.get_device_name(0)]
     dev = benchlib.device()
     lines.append('clocks before: ' + benchlib.clocks())
     kernels(dev, reps, lines)
     if not skip_step:
-        step(dev, step_reps, lines, f16x3)
+        step(dev, step_reps, lines, f16x3 or forward_f16x3, forward_f16x3)
     lines.append('clocks after: ' + benchlib.clocks())
     print('\n'.join(lines))
 
@@ -250,7 +272,8 @@ def main():
     # the time limit: a run with the default arguments took 10 to 12 s, and 68 s as the first of its kind on a box
     benchlib.main(__file__, child, out='train_step_bench.txt', reps=30, timeout=300,
                   extra=[('--step-reps', dict(type=int, default=10)), ('--skip-step', dict(action='store_true')),
-                         ('--f16x3', dict(action='store_true'))],     # the whole step also with backward_precision='f16x3', alternating
+                         ('--f16x3', dict(action='store_true')),      # the whole step also with backward_precision='f16x3', alternating
+                         ('--forward-f16x3', dict(action='store_true'))],     # ... and with forward_precision='f16x3', both backwards
                   header='# python tools/train_step_bench.py --reps %(reps)d --step-reps %(step_reps)d   (see the tool for what each line measures)')
 
 
