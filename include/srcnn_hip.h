@@ -383,8 +383,9 @@ SRCNN_API int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *wo
  * nothing is transposed; (5) the implicit GEMM: rows = the B OH OW output pixels, columns = Cout, K = (kh, kw, 32-channel tiles of
  * Cin).  x stays fp32 in memory and is split while it is staged into LDS; taps outside the image and rows beyond M enter as exact
  * zeros.  Epilogue per element, every operation rounded once: (main + cross) * (1 / s_x) * (1 / s_w), + bias, + residual, ReLU;
- * each element of y is stored exactly once.  No atomics other than the two max words, nothing read back by the host, no
- * device-scope fence; the call can be captured into a graph.
+ * each element of y is stored exactly once.  No atomics other than the max words -- the two of x and w and, in
+ * srcnn_conv2d_forward_f16x3_maxima, the third word y_amax, all integer maxima that no order can change -- nothing read back by the
+ * host, no device-scope fence; the call can be captured into a graph.
  * Scaling x or w by a power of two scales the GEMM's result by exactly that power, bit for bit (as long as nothing leaves the
  * normal fp32 range); an all-zero x gives y = relu?(bias + residual) exactly.
  *
@@ -415,6 +416,32 @@ typedef struct srcnn_conv_fwd_f16x3_desc {
 } srcnn_conv_fwd_f16x3_desc;
 SRCNN_API size_t srcnn_conv2d_forward_f16x3_workspace_bytes(const srcnn_conv_fwd_f16x3_desc *d);
 SRCNN_API int srcnn_conv2d_forward_f16x3(const srcnn_conv_fwd_f16x3_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+
+/* ------------------------------------------------- 3 x f16 training calls: max |x| handed from layer to layer
+ * A scale is a function of max|x| alone, and a maximum does not depend on who computed it: the three entries below let a training
+ * step find the maximum of an activation once and read it from a device word everywhere else.  The results keep the bits of the
+ * plain entries.  A word is one 4-byte aligned unsigned in device memory holding the float bits of a maximum (0 for an all-zero
+ * tensor; NaNs are dropped by fmaxf).  Nothing is read by the host and there is no device-scope fence: all three can be captured.
+ *
+ * srcnn_conv2d_forward_f16x3_maxima: srcnn_conv2d_forward_f16x3 (same descriptor, validation, messages and workspace query) with
+ *   x_amax: NULL, or the word of max|x| over channels [0, Cin) of ALL B H W input pixels -- what the call's own pass scans,
+ *     pixels a strided layer never reads included.  When given, the max|x| launch is not issued and the GEMM takes s_x from it.
+ *   y_amax: NULL, or a word the call OVERWRITES (it is cleared by the call's clear launch, whatever it held) with max|y| over
+ *     exactly the elements it stores: rows < M, columns < Cout, after bias, residual and ReLU.  Each thread of the GEMM's epilogue
+ *     keeps fmaxf(mx, |v|) of what it stores, a wave reduces it, and one integer atomicMax per wave with a non-zero maximum lands in
+ *     the word.  With y_amax NULL the GEMM kernel is the plain entry's.
+ *   Additional refusals, before any launch: a word that is not 4-byte aligned ("aligned"); x_amax == y_amax ("alias").
+ * srcnn_conv2d_backward_f16x3_maxima: srcnn_conv2d_backward_f16x3 with the weight gradient's max|x| launch replaced by the word
+ *   x_amax when it is not NULL (same definition as above: channels [0, Cin) of all B H W pixels of the saved x); the mask / bias
+ *   pass, max|g|, max|w|, dx, split-K and its reduction are unchanged, db and g_out stay bit-equal to the fp32 call's.
+ * srcnn_absmax: the calls' own scan behind an entry: *word is overwritten with the float bits of max|x| over `rows` rows of `len`
+ *   floats at a stride of `stride` >= len floats; floats behind len are never read.  For an activation that no f16x3 convolution
+ *   produced and that several calls consume.  Refused: null x / word, misaligned pointers, non-positive rows / len. */
+SRCNN_API int srcnn_conv2d_forward_f16x3_maxima(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax,
+                                                void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, void *workspace,
+                                                 size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_absmax(const float *x, long long rows, int len, long long stride, unsigned *word, srcnn_stream_t stream);
 
 /* ------------------------------------------------- training: remaining adjoints
  * The three differentiable operators of the reference's training branch that are neither a convolution, a ROIAlign nor a loss:

@@ -165,6 +165,9 @@ _SIGNATURES = {
     "srcnn_conv2d_backward_f16x3": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
     "srcnn_conv2d_forward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvFwdF16x3Desc)]),
     "srcnn_conv2d_forward_f16x3": (c_int, [ctypes.POINTER(ConvFwdF16x3Desc), c_void_p, c_size_t, c_void_p]),
+    "srcnn_conv2d_forward_f16x3_maxima": (c_int, [ctypes.POINTER(ConvFwdF16x3Desc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "srcnn_conv2d_backward_f16x3_maxima": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "srcnn_absmax": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
     "srcnn_upsample_add_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_subsample2_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "srcnn_pixel_shuffle2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

@@ -14,7 +14,20 @@ conv2d_nhwc is the same convolution NHWC to NHWC: a graph of many layers (stereo
 and pays no transpose per layer.  upsample_add, subsample2 and conv_transpose2x2 are the three remaining differentiable operators
 of the reference's training branch (_upsample_add, MaxPool2d(1, stride 2), ConvTranspose2d(k=2, s=2) + ReLU) over the adjoint
 kernels of csrc/train_ops.hip; they are NHWC on both sides.
+
+reuse_maxima (default True; it matters only where a precision is 'f16x3').  The f16x3 calls scale x by a power of two found from
+max |x|, and without help every call scans its input for it: the forward, the weight gradient over the same saved x again, and
+every further consumer of that tensor likewise.  With reuse_maxima a convolution whose forward is f16x3 has its epilogue leave
+max |y| in a device word (engine.conv2d_train_f16x3's y_amax), which is recorded for the tensor it returns; a convolution looks
+its input up in that record and hands the word on as x_amax, and a tensor the record does not know is scanned once
+(engine.absmax) and recorded, so that its second consumer hits.  The word used for x is kept on ctx and given to the f16x3
+backward.  When only the backward is f16x3 the scan therefore moves to the forward -- the same one pass for a tensor with one
+consumer, one pass instead of two for a block input that feeds conv1 and downsample -- and it is issued only where a weight
+gradient will want it (grad mode on and the weight requires grad).  A maximum does not depend on who computed it: every result
+keeps its bits.  engine.F16X3_MAXIMA counts the passes issued and the calls served by an older word.
 """
+import weakref
+
 import torch
 
 from . import _lib, engine
@@ -26,12 +39,59 @@ def _bn_scale_shift(bn, eps=1e-5):
     return s, bn['bias'].detach().double() - bn['running_mean'].detach().double() * s
 
 
+# id(tensor) -> (weak reference, _version, word): max |t| over all of t, recorded for that very tensor object at that version.
+# Tensor identity survives Function.apply in this torch for both the inputs forward() sees and the output apply() returns
+# (tests/test_f16x3_maxima_abi_cpu.py checks it); the record is nevertheless written on what apply() returned.
+_MAXIMA = {}
+
+
+def _record_maximum(t, word):
+    key = id(t)
+    _MAXIMA[key] = (weakref.ref(t, lambda _, key=key: _MAXIMA.pop(key, None)), t._version, word)
+
+
+def _known_maximum(t):
+    """The recorded word of max |t|, or None: a hit needs the very object the word was recorded for, unmodified since.  A view, a
+    slice, a torch.cat result or a tensor changed in place is another object or another version: a miss.  What torch's version
+    counter does not see -- a write through `.data`, or an engine call that fills an existing tensor through its raw pointer -- the
+    record does not see either: the tensors recorded here are the fresh outputs of this module's functions and their inputs, and a
+    caller that rewrites such a tensor behind torch's back passes reuse_maxima=False."""
+    hit = _MAXIMA.get(id(t))
+    if hit is None or hit[0]() is not t or hit[1] != t._version:
+        return None
+    return hit[2]
+
+
+def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, backward_precision, forward_precision, reuse_maxima):
+    """_Conv2dNHWC.apply with the record of maxima around it.  x is contiguous (B, H, W, Cin): the convolution reads the tensor's
+    full channel range (Cin = its last dimension = its pixel stride), which is what a recorded word covers."""
+    x_word = y_word = None
+    fresh = False
+    f16_fwd = forward_precision == 'f16x3'
+    f16_dw = backward_precision == 'f16x3' and torch.is_grad_enabled() and weight.requires_grad
+    if reuse_maxima and x.is_cuda and (f16_fwd or f16_dw):
+        x_word = _known_maximum(x)
+        if x_word is None:
+            x_word = engine.absmax(x.detach())
+            _record_maximum(x, x_word)
+            fresh = True
+        if f16_fwd:
+            y_word = torch.empty(1, dtype=torch.int32, device=x.device)
+    y = _Conv2dNHWC.apply(x, weight, bias, residual, stride, pad, relu, backward_precision, forward_precision, x_word, y_word, fresh)
+    if y_word is not None:
+        _record_maximum(y, y_word)
+    return y
+
+
 class _Conv2dNHWC(torch.autograd.Function):
     """x (B, H, W, Cin), weight (Cout, KH, KW, Cin) engine layout and already BN-folded, bias (Cout) or None, residual
     (B, OH, OW, Cout) or None; all contiguous float32 on the device."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32', forward_precision='f32'):
+    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32', forward_precision='f32',
+                x_word=None, y_word=None, x_word_fresh=False):
+        """x_word: the word of max |x| or None; y_word: a word to receive max |y| (f16x3 forward) or None; x_word_fresh: x_word was
+        scanned for this call, so its first use is not a scan avoided."""
         if backward_precision not in ('f32', 'f16x3'):
             raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
         _check_forward_precision(forward_precision)
@@ -43,10 +103,14 @@ class _Conv2dNHWC(torch.autograd.Function):
         y = torch.empty((B, OH, OW, cout), dtype=torch.float32, device=x.device)
         res = None if residual is None else residual.detach()
         if forward_precision == 'f16x3':
-            engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res)
+            engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res, x_amax=x_word, y_amax=y_word)
+            if x_word is not None:
+                engine.F16X3_MAXIMA['reused'] += 0 if x_word_fresh else 1
+                x_word_fresh = False
         else:
             engine.conv2d(cw, x.detach(), B, H, W, y, OH, OW, residual=res, precision='f32', plan=(0, 0, 0, 0, 0))
         ctx.save_for_backward(x, weight, y if relu else None)
+        ctx.x_word, ctx.x_word_fresh = x_word, x_word_fresh
         ctx.geom = (B, H, W, OH, OW, kh, kw, stride, pad, bool(relu), bias is not None, residual is not None)
         return y
 
@@ -63,8 +127,12 @@ class _Conv2dNHWC(torch.autograd.Function):
         res = {}
         if want or g_out is not None:
             cw = engine.ConvW(weight, None, kh, kw, stride, pad, relu)
-            res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out, precision=ctx.backward_precision)
-        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None, None, None, None, None, None)
+            x_word = ctx.x_word if ctx.backward_precision == 'f16x3' else None
+            res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out, precision=ctx.backward_precision,
+                                         x_amax=x_word)
+            if x_word is not None and need_w and not ctx.x_word_fresh:
+                engine.F16X3_MAXIMA['reused'] += 1
+        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None) + (None,) * 8
 
 
 def _check_forward_precision(forward_precision):
@@ -113,23 +181,26 @@ def _fold(weight_eng, bias, bn):
     return w, b
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32'):
+def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',
+           reuse_maxima=True):
     """relu?(bn?(conv2d(x, weight) + bias) + residual) on the exact-fp32 engine, differentiable with respect to x, weight, bias
     and residual.  x (B, Cin, H, W) with Cin a multiple of 32, weight (Cout, Cin, KH, KW) as nn.Conv2d holds it, residual
     (B, Cout, OH, OW); bn: a dict with 'weight', 'bias', 'running_mean', 'running_var' -- the frozen BatchNorm that follows the
     convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients; forward_precision:
-    'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError).  Returns (B, Cout, OH, OW)."""
+    'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError).  reuse_maxima: see the module's
+    docstring.  Returns (B, Cout, OH, OW)."""
     _check_forward_precision(forward_precision)
     _check(x, weight)
     if int(x.shape[1]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[1]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     r = None if residual is None else _ToNHWC.apply(residual)
-    y = _Conv2dNHWC.apply(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision, forward_precision)
+    y = _conv_nhwc(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision, forward_precision,
+                   reuse_maxima)
     return _ToNCHW.apply(y)
 
 
-def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32'):
+def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
     """relu?(x @ weight.T + bias) as a 1x1 convolution over an (n, 1, 1, K) tensor: x (n, K), weight (out, K) as nn.Linear holds
     it.  K must be a multiple of 32."""
     _check_forward_precision(forward_precision)
@@ -138,12 +209,13 @@ def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_p
     if K % 32 != 0:
         raise ValueError("linear: K must be a multiple of 32 (got %d)" % K)
     out = int(weight.shape[0])
-    y = _Conv2dNHWC.apply(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu),
-                          backward_precision, forward_precision)
+    y = _conv_nhwc(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu),
+                   backward_precision, forward_precision, reuse_maxima)
     return y.view(n, out)
 
 
-def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32'):
+def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',
+                reuse_maxima=True):
     """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
     (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back)."""
     _check_forward_precision(forward_precision)
@@ -151,8 +223,8 @@ def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=
     if int(x.shape[3]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
-    return _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
-                             int(stride), int(padding), bool(relu), backward_precision, forward_precision)
+    return _conv_nhwc(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
+                      int(stride), int(padding), bool(relu), backward_precision, forward_precision, reuse_maxima)
 
 
 def _check_nhwc(x, what):
@@ -256,7 +328,7 @@ class _PixelShuffle2(torch.autograd.Function):
         return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
 
 
-def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32'):
+def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
     """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
     nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
     engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
@@ -271,5 +343,9 @@ def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'
         raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
     w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
     b = None if bias is None else bias.repeat(4)
-    y = _Conv2dNHWC.apply(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision, forward_precision)
-    return _PixelShuffle2.apply(y, cout)
+    y = _conv_nhwc(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision, forward_precision, reuse_maxima)
+    out = _PixelShuffle2.apply(y, cout)
+    word = _known_maximum(y)
+    if word is not None:
+        _record_maximum(out, word)          # the shuffle moves every element and changes none: the same maximum
+    return out

@@ -50,6 +50,9 @@
 //
 // pow2_scale, split_f16, f16x3_clear_scales, absmax_kernel and the K tile's MFMA loop live in conv_f16x3_scaled.h, shared with the
 // training forward (conv_forward_f16x3.hip).
+//
+// srcnn_conv2d_backward_f16x3_maxima: the caller already holds max|x| of the saved x as a device word (the forward found it, or
+// its producer's epilogue did); wgrad reads s_x from that word and the max|x| pass is not launched.  Nothing else differs.
 #include "conv_backward_common.h"
 #include "conv_f16x3_scaled.h"
 
@@ -58,6 +61,7 @@ namespace srcnn {
 struct F16x3Args {
     _Float16 *wt_hi, *wt_lo;       // workspace: re-laid weights (Cin, taps, Cp), hi and lo plane
     unsigned *amax;                // workspace: float bits of max|g|, max|w|, max|x|
+    const unsigned *xmax;          // the word wgrad takes s_x from: amax + 2, or the caller's x_amax
 };
 
 // bwd_weight_relayout with the split: grid (Cin / 32, Cp / 32, taps), block (32, 8)
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16x3_kernel(const BwdArgs 
     const int n0 = mt * BM, j0 = nt * BN;               // first output channel / first (tap, c) column of the tile
     const int kt_begin = blockIdx.y * p.w_kt_per_split;
     const int kt_end = min(p.w_nkt, kt_begin + p.w_kt_per_split);
-    const Pow2 sg = pow2_scale(q.amax[0]), sx = pow2_scale(q.amax[2]);
+    const Pow2 sg = pow2_scale(q.amax[0]), sx = pow2_scale(*q.xmax);
 
     // A: g rows.  This thread's channel group is the same in every K tile
     WgradOperand<BM> A(t);
@@ -341,10 +345,18 @@ size_t srcnn_conv2d_backward_f16x3_workspace_bytes(const srcnn_conv_bwd_desc *d)
 
 int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
 {
+    return srcnn_conv2d_backward_f16x3_maxima(d, nullptr, workspace, workspace_bytes, stream);
+}
+
+int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, void *workspace, size_t workspace_bytes,
+                                       srcnn_stream_t stream)
+{
     using namespace srcnn;
     BwdArgs a;
     BwdPlan pl;
     int rc = bwd_prepare(d, a, pl, true);
+    if (rc != SRCNN_OK) return rc;
+    rc = check_amax_words(x_amax, nullptr);
     if (rc != SRCNN_OK) return rc;
     if (!workspace || workspace_bytes < pl.bytes) {
         set_error("srcnn_conv2d_backward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
@@ -361,9 +373,10 @@ int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, s
     q.wt_hi = d->dx ? reinterpret_cast<_Float16 *>(ws + pl.off_wt) : nullptr;
     q.wt_lo = d->dx ? q.wt_hi + (size_t)a.Cin * a.taps * a.Cp : nullptr;
     q.amax = reinterpret_cast<unsigned *>(ws + pl.off_scale);
+    q.xmax = x_amax ? x_amax : q.amax + 2;
 
     hipStream_t st = as_stream(stream);
-    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, q.amax);
+    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, q.amax, static_cast<unsigned *>(nullptr));
     SRCNN_LAUNCH(bwd_mask_bias_kernel<true>, dim3(pl.nq, a.Cp / BK), dim3(256), 0, st, a, q.amax);
     if (d->db) SRCNN_LAUNCH(bwd_bias_reduce_kernel, dim3(a.Cp / BK), dim3(256), 0, st, a, pl.nq);
     if (d->dx) {
@@ -374,7 +387,7 @@ int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, s
         });
     }
     if (d->dw) {
-        launch_absmax(a.x, a.Min, a.Cin, a.xcs, q.amax + 2, st);
+        if (!x_amax) launch_absmax(a.x, a.Min, a.Cin, a.xcs, q.amax + 2, st);
         dispatch_tile_4w(pl.w_mr, pl.w_nr, [&](auto mr, auto nr) {
             SRCNN_LAUNCH((conv_wgrad_f16x3_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.w_mtiles * a.w_ntiles, pl.splits), dim3(256), 0, st, a, q);
         });

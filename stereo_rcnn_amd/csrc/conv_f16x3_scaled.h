@@ -36,9 +36,21 @@ __device__ __forceinline__ void split_f16(float v, float s, _Float16 &hi, _Float
     lo = (_Float16)(t - (float)hi);     // the residual is exact in fp32
 }
 
-static __global__ void f16x3_clear_scales(unsigned *amax)
+// the call's four max words in the workspace <- 0, and `extra`, one word of the caller's that the call will overwrite with a
+// maximum; either may be null
+static __global__ void f16x3_clear_scales(unsigned *amax, unsigned *extra)
 {
-    if (threadIdx.x < 4) amax[threadIdx.x] = 0u;
+    if (threadIdx.x < 4 && amax) amax[threadIdx.x] = 0u;
+    if (threadIdx.x == 4 && extra) *extra = 0u;
+}
+
+// A thread's max |v| (>= 0, NaNs already dropped by fmaxf) -> the word: one integer atomicMax on the float bits per wave, none for
+// a wave of zeros.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_absmax_to_word(float mx, unsigned *word)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(word, __float_as_uint(mx));
 }
 
 // max |v| over `rows` rows of `len` floats at a stride of `stride` floats.  VEC: len, stride multiples of 4 and a 16-byte aligned base
@@ -58,9 +70,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *v, long long r
             mx = fmaxf(mx, fabsf(*ptr));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(word, __float_as_uint(mx));
+    wave_absmax_to_word(mx, word);
 }
 
 static void launch_absmax(const float *v, long long rows, int len, long long stride, unsigned *word, hipStream_t st)
@@ -70,6 +80,16 @@ static void launch_absmax(const float *v, long long rows, int len, long long str
     const unsigned blocks = (unsigned)min(1024LL, (total + 255) / 256);
     if (vec) SRCNN_LAUNCH(absmax_kernel<true>, dim3(blocks), dim3(256), 0, st, v, rows, len, stride, word);
     else SRCNN_LAUNCH(absmax_kernel<false>, dim3(blocks), dim3(256), 0, st, v, rows, len, stride, word);
+}
+
+// The caller-owned max words of the *_maxima entries (either may be null): 4-byte aligned, and never the same word -- the call's
+// clear of y_amax would destroy x_amax before the GEMM reads it
+static int check_amax_words(const unsigned *x_amax, const unsigned *y_amax)
+{
+    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(x_amax) & 3) == 0, "x_amax must be 4-byte aligned");
+    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(y_amax) & 3) == 0, "y_amax must be 4-byte aligned");
+    SRCNN_REQUIRE(x_amax == nullptr || x_amax != y_amax, "x_amax and y_amax alias: they must be two words");
+    return SRCNN_OK;
 }
 
 // One K tile out of an LDS buffer of four panels [A_hi | A_lo | B_hi | B_lo] of swizzled 64-byte rows (conv_f16x3_kernel's layout):

@@ -20,8 +20,14 @@
 //   of 16 channels.  Per step cross += lo hi, main += hi hi, cross += hi lo; at the end (main + cross) * 1/s_x * 1/s_w, + bias,
 //   + residual, ReLU, each rounded once.  Inside one MFMA step the 16 products are summed by the matrix unit in its own fixed order.
 //
-// No atomics other than the two max words (whose result no order can change), no host read, no device-scope fence: every kernel
+// No atomics other than the max words (whose result no order can change), no host read, no device-scope fence: every kernel
 // reads what an earlier kernel of the same stream completed.
+//
+// MAXIMA (srcnn_conv2d_forward_f16x3_maxima).  max|x| is a function of x alone, so a caller that already holds it as a device word
+// (x_amax) spares the pass: the GEMM reads s_x from that word and absmax_kernel is not launched for x.  y_amax is the word the
+// NEXT layer wants: the epilogue of conv_fwd_f16x3_kernel<.., true> keeps fmaxf(mx, |v|) over the values it stores (rows < M,
+// columns < Cout, after bias, residual and ReLU), reduces it over the wave and issues one integer atomicMax per wave; the word is
+// cleared by f16x3_clear_scales with the workspace's.  The <.., false> kernel is the one the plain entry launches.
 #include "conv_f16x3_scaled.h"
 
 namespace srcnn {
@@ -31,6 +37,8 @@ struct FwdArgs {
     float *y;
     _Float16 *w_hi, *w_lo;         // workspace: the weights' hi and lo plane (Cp, Kw)
     unsigned *amax;                // workspace: float bits of max|x|, max|w|
+    const unsigned *xmax;          // the word s_x is taken from: amax, or the caller's x_amax
+    unsigned *ymax;                // the caller's y_amax or null
     int H, W, Cin, xcs;
     int OH, OW, Cout, Cp;
     int KH, KW, stride, pad;
@@ -69,7 +77,7 @@ __global__ __launch_bounds__(256) void fwd_weight_split(const FwdArgs p)
     }
 }
 
-template <int MR, int NR>
+template <int MR, int NR, bool YMAX>
 __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
 {
     constexpr int BM = 64 * MR, BN = 64 * NR;
@@ -82,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
     const int logical = xcd_logical_tile(blockIdx.x, p.mtiles * p.ntiles);
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
-    const Pow2 sx = pow2_scale(p.amax[0]), sw = pow2_scale(p.amax[1]);
+    const Pow2 sx = pow2_scale(*p.xmax), sw = pow2_scale(p.amax[1]);
 
     // A: the forward's gather (rows = output pixels); a row beyond M never passes the image test
     const int lrow = t >> 3, lcol = (t & 7) * 4;
@@ -175,6 +183,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
     ktile_pipeline(0, p.nkt, load_tile, store_tile, [&](int buf) { f16x3_ktile(smem[buf], g, acc, accx); });
 
     // every (row, col) of the tile inside (M, Cout) is stored once; the 32 lanes of a row write 128 contiguous bytes
+    float mx = 0.f;                 // YMAX: max |v| over what this thread stores, nothing else
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
 #pragma unroll
@@ -191,9 +200,11 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
                 if (p.res) v += p.res[(size_t)row * p.Cout + col];
                 if (p.relu) v = fmaxf(v, 0.f);
                 p.y[(size_t)row * p.ycs + p.yco + col] = v;
+                if (YMAX) mx = fmaxf(mx, fabsf(v));
             }
         }
     }
+    if (YMAX) wave_absmax_to_word(mx, p.ymax);
 }
 
 // Validates the descriptor and lays out the call (workspace pointers are bound by the caller)
@@ -221,7 +232,7 @@ static int fwd_prepare(const srcnn_conv_fwd_f16x3_desc *d, FwdArgs &a, FwdPlan &
                   "bad shape: tensor too large");
 
     a.x = d->x; a.w = d->w; a.bias = d->bias; a.res = d->residual; a.y = d->y;
-    a.w_hi = a.w_lo = nullptr; a.amax = nullptr;
+    a.w_hi = a.w_lo = nullptr; a.amax = nullptr; a.xmax = nullptr; a.ymax = nullptr;
     a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
     a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
     a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
@@ -248,6 +259,41 @@ static int fwd_prepare(const srcnn_conv_fwd_f16x3_desc *d, FwdArgs &a, FwdPlan &
     return SRCNN_OK;
 }
 
+// The two entries' body.  x_amax / y_amax: the _maxima entry's words (null, null from the plain entry)
+static int fwd_run(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, void *workspace, size_t workspace_bytes,
+                   srcnn_stream_t stream)
+{
+    FwdArgs a;
+    FwdPlan pl;
+    int rc = fwd_prepare(d, a, pl);
+    if (rc != SRCNN_OK) return rc;
+    rc = check_amax_words(x_amax, y_amax);
+    if (rc != SRCNN_OK) return rc;
+    if (!workspace || workspace_bytes < pl.bytes) {
+        set_error("srcnn_conv2d_forward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
+        return SRCNN_ERR_WORKSPACE;
+    }
+    char *ws = static_cast<char *>(workspace);
+    a.w_hi = reinterpret_cast<_Float16 *>(ws + pl.off_hi);
+    a.w_lo = reinterpret_cast<_Float16 *>(ws + pl.off_lo);
+    a.amax = reinterpret_cast<unsigned *>(ws + pl.off_scale);
+    a.xmax = x_amax ? x_amax : a.amax;
+    a.ymax = y_amax;
+
+    hipStream_t st = as_stream(stream);
+    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, a.amax, a.ymax);
+    launch_absmax(a.w, a.Cout, a.Kw, a.Kw, a.amax + 1, st);
+    if (!x_amax) launch_absmax(a.x, a.Min, a.Cin, a.xcs, a.amax, st);
+    const long long groups = (long long)a.Cp * (a.Kw / 4);
+    SRCNN_LAUNCH(fwd_weight_split, dim3((unsigned)min(2048LL, (groups + 255) / 256)), dim3(256), 0, st, a);
+    dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
+        constexpr int MR = decltype(mr)::value, NR = decltype(nr)::value;
+        if (a.ymax) SRCNN_LAUNCH((conv_fwd_f16x3_kernel<MR, NR, true>), dim3(a.mtiles * a.ntiles), dim3(256), 0, st, a);
+        else SRCNN_LAUNCH((conv_fwd_f16x3_kernel<MR, NR, false>), dim3(a.mtiles * a.ntiles), dim3(256), 0, st, a);
+    });
+    return check_launch("srcnn_conv2d_forward_f16x3");
+}
+
 }  // namespace srcnn
 
 extern "C" {
@@ -263,30 +309,28 @@ size_t srcnn_conv2d_forward_f16x3_workspace_bytes(const srcnn_conv_fwd_f16x3_des
 
 int srcnn_conv2d_forward_f16x3(const srcnn_conv_fwd_f16x3_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
 {
-    using namespace srcnn;
-    FwdArgs a;
-    FwdPlan pl;
-    int rc = fwd_prepare(d, a, pl);
-    if (rc != SRCNN_OK) return rc;
-    if (!workspace || workspace_bytes < pl.bytes) {
-        set_error("srcnn_conv2d_forward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
-        return SRCNN_ERR_WORKSPACE;
-    }
-    char *ws = static_cast<char *>(workspace);
-    a.w_hi = reinterpret_cast<_Float16 *>(ws + pl.off_hi);
-    a.w_lo = reinterpret_cast<_Float16 *>(ws + pl.off_lo);
-    a.amax = reinterpret_cast<unsigned *>(ws + pl.off_scale);
+    return srcnn::fwd_run(d, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
 
+int srcnn_conv2d_forward_f16x3_maxima(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, void *workspace,
+                                      size_t workspace_bytes, srcnn_stream_t stream)
+{
+    return srcnn::fwd_run(d, x_amax, y_amax, workspace, workspace_bytes, stream);
+}
+
+int srcnn_absmax(const float *x, long long rows, int len, long long stride, unsigned *word, srcnn_stream_t stream)
+{
+    using namespace srcnn;
+    SRCNN_REQUIRE(x != nullptr, "null pointer: x");
+    SRCNN_REQUIRE(word != nullptr, "null pointer: word");
+    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(word) & 3) == 0, "x and word must be 4-byte aligned");
+    SRCNN_REQUIRE(rows > 0 && len > 0, "bad shape: rows and len must be positive");
+    SRCNN_REQUIRE(stride >= len, "stride: a stride of at least len floats");
+    SRCNN_REQUIRE(rows < (1LL << 31), "bad shape: tensor too large");
     hipStream_t st = as_stream(stream);
-    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, a.amax);
-    launch_absmax(a.w, a.Cout, a.Kw, a.Kw, a.amax + 1, st);
-    launch_absmax(a.x, a.Min, a.Cin, a.xcs, a.amax, st);
-    const long long groups = (long long)a.Cp * (a.Kw / 4);
-    SRCNN_LAUNCH(fwd_weight_split, dim3((unsigned)min(2048LL, (groups + 255) / 256)), dim3(256), 0, st, a);
-    dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
-        SRCNN_LAUNCH((conv_fwd_f16x3_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.mtiles * a.ntiles), dim3(256), 0, st, a);
-    });
-    return check_launch("srcnn_conv2d_forward_f16x3");
+    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, static_cast<unsigned *>(nullptr), word);
+    launch_absmax(x, rows, len, stride, word, st);
+    return check_launch("srcnn_absmax");
 }
 
 }  // extern "C"

@@ -692,7 +692,7 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
 
 
 def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), splits=0, x_cstride=None, y_cstride=None, y_coffset=0,
-                    relu=None, g_out=None, out=None, tile=None, precision='f32'):
+                    relu=None, g_out=None, out=None, tile=None, precision='f32', x_amax=None):
     """Gradients of conv2d(cw, x, ..., precision='f32') (srcnn_conv2d_backward; include/srcnn_hip.h states the sums' orders).
     precision: 'f32', that exact fp32 backward, or 'f16x3', srcnn_conv2d_backward_f16x3 -- the same gradients by the 3 x f16 split
     with per-tensor power-of-two scales found on the device; the one asked for runs, never the other in its place.
@@ -701,10 +701,15 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     (Cout, KH, KW, Cin) and 'db' (Cout) to compute -- the others are neither computed nor allocated.  g_out: optional dense
     (B, OH, OW, Cout) tensor that receives the masked gradient dy * [y > 0] (the residual branch's gradient).  out: {name: tensor}
     to write into instead of fresh tensors (every element is overwritten).  splits: K slices of the weight gradient (0 = the
-    library's choice); tile: (tile_mr, tile_nr).  Returns {name: tensor} for the names in want."""
+    library's choice); tile: (tile_mr, tile_nr).  x_amax (precision 'f16x3' only): a 1-element int32 device tensor holding the float
+    bits of max |x| over channels [0, Cin) of all B H W pixels (absmax, or a forward's y_amax): the weight gradient's max |x| pass
+    is then not launched (srcnn_conv2d_backward_f16x3_maxima); the gradients keep their bits.  Returns {name: tensor} for the names
+    in want."""
     L = _lib.lib()
     if precision not in ('f32', 'f16x3'):
         raise ValueError("conv2d_backward: precision must be 'f32' or 'f16x3' (got %r)" % (precision,))
+    if x_amax is not None and precision != 'f16x3':
+        raise ValueError("conv2d_backward: x_amax belongs to precision 'f16x3'")
     entry = 'srcnn_conv2d_backward' if precision == 'f32' else 'srcnn_conv2d_backward_f16x3'
     assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a backward"
     unknown = set(want) - {'dx', 'dw', 'db'}
@@ -737,17 +742,55 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
         d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
     nbytes = getattr(L, entry + '_workspace_bytes')(ctypes.byref(d))
     ws = _lib.workspace(nbytes, dy.device, "conv_backward")
-    _lib.check(getattr(L, entry)(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), entry)
+    if x_amax is not None:
+        _lib.check(L.srcnn_conv2d_backward_f16x3_maxima(ctypes.byref(d), _amax_ptr(x_amax), ws.data_ptr(), ws.numel(), _lib.stream()),
+                   entry + '_maxima')
+    else:
+        if precision == 'f16x3' and 'dw' in want:
+            F16X3_MAXIMA['scans'] += 1
+        _lib.check(getattr(L, entry)(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), entry)
     return res
 
 
-def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None, y_cstride=None, y_coffset=0, relu=None, tile=None):
+# The f16x3 training calls' max |x|: host counters of the passes over an activation that were issued ('scans': inside a call that
+# was given no word, or by absmax) and of the calls that needed max |x| and were served by a word older than themselves ('reused',
+# counted by the owner of the words -- autograd's record -- since only it knows where a word came from).
+F16X3_MAXIMA = {'scans': 0, 'reused': 0}
+
+
+def reset_f16x3_maxima():
+    F16X3_MAXIMA['scans'] = F16X3_MAXIMA['reused'] = 0
+
+
+def _amax_ptr(word):
+    assert word.is_cuda and word.dtype == torch.int32 and word.numel() == 1, "a max word is a 1-element int32 device tensor"
+    return word.data_ptr()
+
+
+def absmax(x, cin=None, x_cstride=None):
+    """max |x| over channels [0, cin) of every pixel of x (..., x_cstride) (srcnn_absmax; defaults: x's last dimension for both) as
+    a fresh 1-element int32 device tensor holding the float's bits -- the word conv2d_train_f16x3 and conv2d_backward(precision=
+    'f16x3') take as x_amax.  Floats behind cin are not read; NaNs are dropped; an all-zero x gives 0.  Nothing is read by the host."""
+    xcs = int(x.shape[-1]) if x_cstride is None else int(x_cstride)
+    cin = xcs if cin is None else int(cin)
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() % xcs == 0
+    word = torch.empty(1, dtype=torch.int32, device=x.device)
+    F16X3_MAXIMA['scans'] += 1
+    _lib.check(_lib.lib().srcnn_absmax(x.data_ptr(), x.numel() // xcs, cin, xcs, word.data_ptr(), _lib.stream()), "srcnn_absmax")
+    return word
+
+
+def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None, y_cstride=None, y_coffset=0, relu=None, tile=None,
+                       x_amax=None, y_amax=None):
     """The training forward on the f16 matrix pipe (srcnn_conv2d_forward_f16x3): y = relu?(conv(x, w) + bias + residual) by the 3 x f16
     split with one power-of-two scale for x and one for w, both found on the device inside the call -- the scheme of
     conv2d_backward(precision='f16x3').  cw: an engine.ConvW holding the plain fp32 weights (Cout, KH, KW, Cin) (BN folded) and
     bias, mode 0; no prepared planes, no host-side exponent.  x (B, H, W, *) and y (B, OH, OW, *) are raw NHWC float32 device
     tensors; residual dense (B, OH, OW, Cout).  tile: (tile_mr, tile_nr).  It is not conv2d(precision='f16x3'), the inference
-    engine, and never runs in its place or lets it run in its own."""
+    engine, and never runs in its place or lets it run in its own.
+    x_amax / y_amax: 1-element int32 device tensors (float bits), never slices of the shared workspace.  x_amax, when given, is
+    max |x| over channels [0, Cin) of all B H W pixels and replaces the call's own pass over x; y_amax, when given, is overwritten
+    with max |y| over exactly what the call stores (srcnn_conv2d_forward_f16x3_maxima).  y keeps its bits either way."""
     L = _lib.lib()
     assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a training forward"
     d = _lib.ConvFwdF16x3Desc()
@@ -764,7 +807,14 @@ def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None,
     if tile is not None:
         d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
     ws = _lib.workspace(L.srcnn_conv2d_forward_f16x3_workspace_bytes(ctypes.byref(d)), x.device, "conv_forward_f16x3")
-    _lib.check(L.srcnn_conv2d_forward_f16x3(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_forward_f16x3")
+    if x_amax is None:
+        F16X3_MAXIMA['scans'] += 1
+    if x_amax is None and y_amax is None:
+        _lib.check(L.srcnn_conv2d_forward_f16x3(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_forward_f16x3")
+    else:
+        _lib.check(L.srcnn_conv2d_forward_f16x3_maxima(ctypes.byref(d), None if x_amax is None else _amax_ptr(x_amax),
+                                                       None if y_amax is None else _amax_ptr(y_amax), ws.data_ptr(), ws.numel(),
+                                                       _lib.stream()), "srcnn_conv2d_forward_f16x3_maxima")
     return y
 
 

@@ -82,17 +82,19 @@ def make_optimizer(model, uncert, lr=None):
 LOSS_NAMES = ('rpn_loss_cls', 'rpn_loss_bbox_left_right', 'RCNN_loss_cls', 'RCNN_loss_bbox', 'RCNN_loss_dim_orien', 'RCNN_loss_kpts')
 
 
-def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, backward_precision='f32', forward_precision='f32'):
+def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, backward_precision='f32', forward_precision='f32',
+               reuse_maxima=True):
     """One iteration of trainval_net.py:207-227.  batch: forward_train's nine inputs (im_left, im_right, im_info, gt_boxes_left,
     gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes).  Gradients are set to None, forward_train and
     losses.multi_task_loss build the total, backward() fills the gradients, and optimizer.step clips the MODEL's gradients to
-    `clip_norm` (uncert's stays as it is, as in the reference) inside the fused update.  backward_precision, forward_precision:
-    forward_train's.  Returns device scalars: 'loss', the six
+    `clip_norm` (uncert's stays as it is, as in the reference) inside the fused update.  backward_precision, forward_precision,
+    reuse_maxima: forward_train's.  Returns device scalars: 'loss', the six
     terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0]."""
     optimizer.zero_grad(set_to_none=True)
     for p in model.parameters():
         p.grad = None
-    out = forward_train(model, *batch, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision)
+    out = forward_train(model, *batch, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision,
+                        reuse_maxima=reuse_maxima)
     terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
     total = losses.multi_task_loss(terms, uncert)
     total.backward()
@@ -117,18 +119,18 @@ class _Taps(object):
         return t
 
 
-def _conv(m, x, relu=False, residual=None, bn=None, bp='f32', fp='f32'):
+def _conv(m, x, relu=False, residual=None, bn=None, bp='f32', fp='f32', rm=True):
     return autograd.conv2d_nhwc(x, m.weight, m.bias, int(m.stride[0]), int(m.padding[0]), relu, residual, None if bn is None else _bn(bn),
-                                backward_precision=bp, forward_precision=fp)
+                                backward_precision=bp, forward_precision=fp, reuse_maxima=rm)
 
 
-def _bottleneck(blk, x, name, tap, bp='f32', fp='f32'):
+def _bottleneck(blk, x, name, tap, bp='f32', fp='f32', rm=True):
     """resnet.py:66-100: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut(x)), the ReLUs and the residual fused
     into the convolutions as the engine fuses them."""
-    t = tap(name + '.conv1', _conv(blk.conv1, x, True, bn=blk.bn1, bp=bp, fp=fp))
-    t = tap(name + '.conv2', _conv(blk.conv2, t, True, bn=blk.bn2, bp=bp, fp=fp))
-    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, False, bn=blk.downsample[1], bp=bp, fp=fp)
-    return tap(name + '.out', _conv(blk.conv3, t, True, residual=res, bn=blk.bn3, bp=bp, fp=fp))
+    t = tap(name + '.conv1', _conv(blk.conv1, x, True, bn=blk.bn1, bp=bp, fp=fp, rm=rm))
+    t = tap(name + '.conv2', _conv(blk.conv2, t, True, bn=blk.bn2, bp=bp, fp=fp, rm=rm))
+    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, False, bn=blk.downsample[1], bp=bp, fp=fp, rm=rm)
+    return tap(name + '.out', _conv(blk.conv3, t, True, residual=res, bn=blk.bn3, bp=bp, fp=fp, rm=rm))
 
 
 def _stem(model, im_left, im_right):
@@ -199,7 +201,7 @@ def _dropout(x, generator, tap, name):
 
 
 def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes,
-                  generator=None, taps=None, backward_precision='f32', forward_precision='f32'):
+                  generator=None, taps=None, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
     """The reference's training forward (stereo_rcnn.py:141-324).  model: a _StereoRCNN on the GPU; images (B, 3, H, W) on the
     same device; im_info (B, 3) (CPU or device), ground truth as the reference's data loader gives it.  Returns (rois_left,
     rois_right, cls_prob, bbox_pred, dim_orien_pred, kpts_prob, left_border_prob, right_border_prob, rpn_loss_cls,
@@ -212,7 +214,9 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     (the exact-fp32 engine, the default: outputs and losses keep their bits whatever backward_precision is) or 'f16x3'
     (srcnn_conv2d_forward_f16x3: the 3 x f16 split with scales found on the device, no host read) for the forward of the same
     layers; RCNN_layer0 and the first cfg.RESNET.FIXED_BLOCKS stages, which have no graph, stay on the fp32 engine.  The two are
-    independent."""
+    independent.  reuse_maxima (default True; it matters only where a precision is 'f16x3'): each activation's max |x| is found at
+    most once -- in the epilogue of the f16x3 convolution that produced it, or by one scan -- and handed to every f16x3 call that
+    consumes it (stereo_rcnn_amd.autograd); every output and gradient keeps its bits."""
     dev = model.RCNN_toplayer.weight.device
     if dev.type != 'cuda' or not im_left.is_cuda:
         raise NotImplementedError
@@ -220,7 +224,7 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
     if forward_precision not in ('f32', 'f16x3'):
         raise ValueError("forward_precision must be 'f32' or 'f16x3' (got %r)" % (forward_precision,))
-    bp, fp = backward_precision, forward_precision
+    bp, fp, rm = backward_precision, forward_precision, bool(reuse_maxima)
     tap = _Taps(taps if isinstance(taps, dict) else None)
     for p in trainable_parameters(model).values():
         p.requires_grad_(True)
@@ -241,15 +245,15 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         frozen = li <= cfg.RESNET.FIXED_BLOCKS
         with (torch.no_grad() if frozen else contextlib.nullcontext()):
             for b, blk in enumerate(getattr(model, 'RCNN_layer%d' % li)[0]):
-                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, bp, 'f32' if frozen else fp)
+                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, bp, 'f32' if frozen else fp, rm)
         c.append(x)
     c2, c3, c4, c5 = c
 
     # ---- top-down (:161-168, 178-185)
-    p5 = _conv(model.RCNN_toplayer, c5, bp=bp, fp=fp)
-    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, bp=bp, fp=fp)), bp=bp, fp=fp)
-    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, bp=bp, fp=fp)), bp=bp, fp=fp)
-    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, bp=bp, fp=fp)), bp=bp, fp=fp)
+    p5 = _conv(model.RCNN_toplayer, c5, bp=bp, fp=fp, rm=rm)
+    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
+    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
+    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
     p6 = autograd.subsample2(p5)
     levels = [p2, p3, p4, p5, p6]
     shapes = [(int(p.shape[1]), int(p.shape[2])) for p in levels]
@@ -263,8 +267,8 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     deltas = torch.empty((B, n_anchors, 6), dtype=torch.float32, device=dev)
     scores, bbox_preds, off = [], [], 0
     for l, (p, (h, w)) in enumerate(zip(levels, shapes)):
-        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, True, bp=bp, fp=fp))                  # (2B, h, w, 512): left images, then right
-        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, backward_precision=bp, forward_precision=fp)    # [cls 6 | bbox 18] per pixel
+        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, True, bp=bp, fp=fp, rm=rm))                  # (2B, h, w, 512): left images, then right
+        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, backward_precision=bp, forward_precision=fp, reuse_maxima=rm)    # [cls 6 | bbox 18] per pixel
         # :89,91: NHWC rows viewed as (-1, 2) / (-1, 6) -- the raw scores pair channels (0, 1) (2, 3) (4, 5)
         scores.append(hd[..., :6].reshape(B, h * w * 3, 2))
         bbox_preds.append(hd[..., 6:].reshape(B, h * w * 3, 6))
@@ -303,24 +307,24 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     feat = _roi_feat([left_maps, right_maps], [rois_left, rois_right], im_height, cfg.POOLING_SIZE)
     top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
     w0 = top0.weight.permute(0, 2, 3, 1).reshape(int(top0.weight.shape[0]), -1)          # (2048, (kh, kw, c)): the NHWC window
-    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), w0, top0.bias, relu=True, backward_precision=bp, forward_precision=fp))
+    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), w0, top0.bias, relu=True, backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
     t = _dropout(t, generator, tap, 'dropout1')
     t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True,
-                                           backward_precision=bp, forward_precision=fp))
+                                           backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
     t = _dropout(t, generator, tap, 'dropout2')                                           # .mean(3).mean(2) over a 1x1 map
     n_bbox, n_dim = int(model.RCNN_bbox_pred.weight.shape[0]), int(model.RCNN_dim_orien_pred.weight.shape[0])
     fc = autograd.linear(t, torch.cat((model.RCNN_bbox_pred.weight, model.RCNN_dim_orien_pred.weight, model.RCNN_cls_score.weight), 0),
-                         torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0), backward_precision=bp, forward_precision=fp)
+                         torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0), backward_precision=bp, forward_precision=fp, reuse_maxima=rm)
     bbox_all, dim_all, cls_score = fc[:, :n_bbox], fc[:, n_bbox:n_bbox + n_dim], fc[:, n_bbox + n_dim:]
     cls_prob = F.softmax(cls_score, 1)
 
     # ---- keypoint head (:260-271)
     k = _roi_feat([left_maps], [rois_left], im_height, cfg.POOLING_SIZE * 2)
     for i in (0, 2, 4, 6, 8, 10):
-        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, True, bp=bp, fp=fp))
+        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, True, bp=bp, fp=fp, rm=rm))
     up = model.RCNN_kpts[12]
-    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, backward_precision=bp, forward_precision=fp))
-    kpts_pred_all = _conv(model.kpts_class, k, bp=bp, fp=fp).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
+    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
+    kpts_pred_all = _conv(model.kpts_class, k, bp=bp, fp=fp, rm=rm).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
     G = cfg.KPTS_GRID
     kpts_prob = F.softmax(kpts_pred_all[:, :4, :].reshape(n, 4 * G), 1)
     left_border_prob = F.softmax(kpts_pred_all[:, 4, :], 1)

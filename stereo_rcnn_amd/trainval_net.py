@@ -16,6 +16,8 @@ is bit-identical with and without it.
 (training.train_step's backward_precision).
 --forward-precision f32|f16x3 (default f32; logged in trainlog.txt only when it is not the default): the engine of the forward of
 every convolution / linear layer that has a graph (training.train_step's forward_precision; srcnn_conv2d_forward_f16x3).
+--no-reuse-maxima: with an f16x3 precision, every call finds max |x| of its input itself (training.train_step's
+reuse_maxima=False); by default each activation's maximum is found once and handed on.  The results are bit-identical.
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -62,6 +64,9 @@ def parse_args(argv=None):
     p.add_argument('--forward-precision', dest='forward_precision', choices=['f32', 'f16x3'], default='f32',
                    help='engine of the training forward of the layers that have a graph: the exact fp32 engine, or the 3 x f16 split '
                         'with scales found on the device')
+    p.add_argument('--no-reuse-maxima', dest='reuse_maxima', action='store_false',
+                   help="f16x3 precisions only: let every convolution call scan its input for max |x| itself instead of taking it from "
+                        "the call that produced the tensor (same bits either way)")
     return p.parse_args(argv)
 
 
@@ -142,7 +147,8 @@ def main(argv=None):
                 if step >= iters_per_epoch:              # trainval_net.py:183,194: the leftover samples are not trained on
                     break
                 res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
-                                          backward_precision=args.backward_precision, forward_precision=args.forward_precision)
+                                          backward_precision=args.backward_precision, forward_precision=args.forward_precision,
+                                          reuse_maxima=args.reuse_maxima)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))

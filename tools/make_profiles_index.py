@@ -34,6 +34,7 @@ COMMANDS = [      # (family regex, how the family is produced)
     (r'^conv_backward_bench', 'python tools/conv_backward_bench.py   (srcnn_conv2d_backward against torch\'s convolution backward, per layer)'),
     (r'^conv_forward_f16x3_bench', 'python tools/conv_forward_f16x3_bench.py   (srcnn_conv2d_forward_f16x3 against the exact-fp32 forward, per layer, alternating)'),
     (r'^train_step_f16x3_forward_bench', 'python tools/train_step_bench.py --forward-f16x3 --out profiles/train_step_f16x3_forward_bench.txt'),
+    (r'^f16x3_maxima_bench', 'python tools/f16x3_maxima_bench.py   (the f16x3 forward with max |x| handed in and max |y| handed out, per layer; the R-101 step with reuse_maxima on / off / fp32, alternating)'),
     (r'^loader_bench', 'python tools/loader_bench.py   (one training batch assembly, csrc/loader.hip against eager torch; the loader\'s sustained pairs/s against the train_step rate)'),
     (r'^overlay_bench', 'python tools/overlay_bench.py   (the result picture of one pair: csrc/overlay.hip against numpy + PIL ImageDraw on the host)'),
     (r'^optim_bench', 'python tools/optim_bench.py   (optim.SGD.step(clip_norm=10.) against the reference\'s clip_gradient + torch.optim.SGD.step() on R-101\'s trainable shapes)'),

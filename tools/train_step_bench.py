@@ -168,7 +168,8 @@ def eager_step(model, im_left, im_right, im_height, taps, fixed_blocks):
     return list(rpn_losses) + list(rcnn_losses)
 
 
-def step(dev, reps, lines, f16x3=False, forward_f16x3=False):
+def headline_case(dev):
+    """The step's model and forward_train's nine inputs at the headline size (also tools/f16x3_maxima_bench.py's)."""
     from stereo_rcnn_amd import fixture, training
     from stereo_rcnn_amd.model.stereo_rcnn.resnet import resnet
     from stereo_rcnn_amd.model.utils.config import cfg
@@ -192,6 +193,14 @@ def step(dev, reps, lines, f16x3=False, forward_f16x3=False):
     kp = left[:, :, 0:1] + w * torch.tensor([0.3, 0., 0., 0., 0.1, 0.9])
     kp[:, :, 1:4] = -1
     args = [im_l, im_r, torch.tensor([[float(Hh), float(Ww), 1.0]])] + [t.to(dev) for t in (left, right, merge, dim, kp, torch.tensor([3]))]
+    return model, args
+
+
+def step(dev, reps, lines, f16x3=False, forward_f16x3=False):
+    from stereo_rcnn_amd import training
+    from stereo_rcnn_amd.model.utils.config import cfg
+    model, args = headline_case(dev)
+    im_l, im_r, Hh = args[0], args[1], 600
     gen = torch.Generator(device=dev).manual_seed(1)
     taps = {}
     first = training.forward_train(model, *args, generator=gen, taps=taps)
