@@ -26,11 +26,26 @@ consumer, one pass instead of two for a block input that feeds conv1 and downsam
 gradient will want it (grad mode on and the weight requires grad).  A maximum does not depend on who computed it: every result
 keeps its bits.  engine.F16X3_MAXIMA counts the passes issued and the calls served by an older word.
 """
+import collections
 import weakref
 
 import torch
 
 from . import _lib, engine
+
+
+class Precision(collections.namedtuple('Precision', 'forward backward reuse_maxima')):
+    """The public functions' three precision keywords as one immutable value, validated here and nowhere else (forward first)."""
+    __slots__ = ()
+
+    def __new__(cls, forward='f32', backward='f32', reuse_maxima=True):
+        for name, value in (('forward', forward), ('backward', backward)):
+            if value not in ('f32', 'f16x3'):
+                raise ValueError("%s_precision must be 'f32' or 'f16x3' (got %r)" % (name, value))
+        return super().__new__(cls, forward, backward, bool(reuse_maxima))
+
+    def without_graph(self):
+        return self._replace(forward='f32')         # layers without a graph (the frozen stages) stay on the fp32 forward
 
 
 def _bn_scale_shift(bn, eps=1e-5):
@@ -62,14 +77,14 @@ def _known_maximum(t):
     return hit[2]
 
 
-def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, backward_precision, forward_precision, reuse_maxima):
+def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, prec):
     """_Conv2dNHWC.apply with the record of maxima around it.  x is contiguous (B, H, W, Cin): the convolution reads the tensor's
     full channel range (Cin = its last dimension = its pixel stride), which is what a recorded word covers."""
     x_word = y_word = None
     fresh = False
-    f16_fwd = forward_precision == 'f16x3'
-    f16_dw = backward_precision == 'f16x3' and torch.is_grad_enabled() and weight.requires_grad
-    if reuse_maxima and x.is_cuda and (f16_fwd or f16_dw):
+    f16_fwd = prec.forward == 'f16x3'
+    f16_dw = prec.backward == 'f16x3' and torch.is_grad_enabled() and weight.requires_grad
+    if prec.reuse_maxima and x.is_cuda and (f16_fwd or f16_dw):
         x_word = _known_maximum(x)
         if x_word is None:
             x_word = engine.absmax(x.detach())
@@ -77,7 +92,7 @@ def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, backward_precision,
             fresh = True
         if f16_fwd:
             y_word = torch.empty(1, dtype=torch.int32, device=x.device)
-    y = _Conv2dNHWC.apply(x, weight, bias, residual, stride, pad, relu, backward_precision, forward_precision, x_word, y_word, fresh)
+    y = _Conv2dNHWC.apply(x, weight, bias, residual, stride, pad, relu, prec, x_word, y_word, fresh)
     if y_word is not None:
         _record_maximum(y, y_word)
     return y
@@ -88,21 +103,17 @@ class _Conv2dNHWC(torch.autograd.Function):
     (B, OH, OW, Cout) or None; all contiguous float32 on the device."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, stride, pad, relu, backward_precision='f32', forward_precision='f32',
-                x_word=None, y_word=None, x_word_fresh=False):
-        """x_word: the word of max |x| or None; y_word: a word to receive max |y| (f16x3 forward) or None; x_word_fresh: x_word was
-        scanned for this call, so its first use is not a scan avoided."""
-        if backward_precision not in ('f32', 'f16x3'):
-            raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
-        _check_forward_precision(forward_precision)
-        ctx.backward_precision = backward_precision
+    def forward(ctx, x, weight, bias, residual, stride, pad, relu, prec=Precision(), x_word=None, y_word=None, x_word_fresh=False):
+        """prec: a Precision; x_word: the word of max |x| or None; y_word: a word to receive max |y| (f16x3 forward) or None;
+        x_word_fresh: x_word was scanned for this call, so its first use is not a scan avoided."""
+        ctx.backward_precision = prec.backward
         B, H, W, cin = (int(v) for v in x.shape)
         cout, kh, kw = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         cw = engine.ConvW(weight.detach(), None if bias is None else bias.detach(), kh, kw, stride, pad, relu)
         OH, OW = engine.conv_out_hw(H, W, kh, kw, stride, pad)
         y = torch.empty((B, OH, OW, cout), dtype=torch.float32, device=x.device)
         res = None if residual is None else residual.detach()
-        if forward_precision == 'f16x3':
+        if prec.forward == 'f16x3':
             engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res, x_amax=x_word, y_amax=y_word)
             if x_word is not None:
                 engine.F16X3_MAXIMA['reused'] += 0 if x_word_fresh else 1
@@ -132,12 +143,7 @@ class _Conv2dNHWC(torch.autograd.Function):
                                          x_amax=x_word)
             if x_word is not None and need_w and not ctx.x_word_fresh:
                 engine.F16X3_MAXIMA['reused'] += 1
-        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None) + (None,) * 8
-
-
-def _check_forward_precision(forward_precision):
-    if forward_precision not in ('f32', 'f16x3'):
-        raise ValueError("forward_precision must be 'f32' or 'f16x3' (got %r)" % (forward_precision,))
+        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None) + (None,) * 7
 
 
 def _check(x, weight):
@@ -189,42 +195,41 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None,
     convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients; forward_precision:
     'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError).  reuse_maxima: see the module's
     docstring.  Returns (B, Cout, OH, OW)."""
-    _check_forward_precision(forward_precision)
+    prec = Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     if int(x.shape[1]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[1]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     r = None if residual is None else _ToNHWC.apply(residual)
-    y = _conv_nhwc(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), backward_precision, forward_precision,
-                   reuse_maxima)
+    y = _conv_nhwc(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), prec)
     return _ToNCHW.apply(y)
 
 
-def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
+def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None):
     """relu?(x @ weight.T + bias) as a 1x1 convolution over an (n, 1, 1, K) tensor: x (n, K), weight (out, K) as nn.Linear holds
-    it.  K must be a multiple of 32."""
-    _check_forward_precision(forward_precision)
+    it.  K must be a multiple of 32.  _prec: conv2d_nhwc's."""
+    prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     n, K = int(x.shape[0]), int(x.shape[1])
     if K % 32 != 0:
         raise ValueError("linear: K must be a multiple of 32 (got %d)" % K)
     out = int(weight.shape[0])
-    y = _conv_nhwc(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu),
-                   backward_precision, forward_precision, reuse_maxima)
+    y = _conv_nhwc(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu), prec)
     return y.view(n, out)
 
 
 def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',
-                reuse_maxima=True):
+                reuse_maxima=True, _prec=None):
     """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
-    (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back)."""
-    _check_forward_precision(forward_precision)
+    (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back).  _prec (private,
+    stereo_rcnn_amd.training's): an already validated Precision, used in place of the three keywords."""
+    prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     if int(x.shape[3]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
     w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
     return _conv_nhwc(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
-                      int(stride), int(padding), bool(relu), backward_precision, forward_precision, reuse_maxima)
+                      int(stride), int(padding), bool(relu), prec)
 
 
 def _check_nhwc(x, what):
@@ -328,13 +333,13 @@ class _PixelShuffle2(torch.autograd.Function):
         return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
 
 
-def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
+def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None):
     """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
     nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
     engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
     with the shuffle and stays in the convolution's epilogue.  Backward: the inverse shuffle of dy, then the convolution's
-    backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups."""
-    _check_forward_precision(forward_precision)
+    backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups.  _prec: conv2d_nhwc's."""
+    prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     cin, cout = int(weight.shape[0]), int(weight.shape[1])
     if tuple(weight.shape[2:]) != (2, 2) or int(x.shape[3]) != cin:
@@ -343,7 +348,7 @@ def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'
         raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
     w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
     b = None if bias is None else bias.repeat(4)
-    y = _conv_nhwc(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), backward_precision, forward_precision, reuse_maxima)
+    y = _conv_nhwc(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), prec)
     out = _PixelShuffle2.apply(y, cout)
     word = _known_maximum(y)
     if word is not None:

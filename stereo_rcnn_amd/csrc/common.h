@@ -33,13 +33,16 @@ inline int check_launch(const char *what)
         }                                                                       \
     } while (0)
 
-#define SRCNN_REQUIRE(cond, msg)                         \
+// refusal in the name of `who` (a helper that validates for its caller)
+#define SRCNN_REQUIRE_AS(who, cond, msg)                 \
     do {                                                 \
         if (!(cond)) {                                   \
-            ::srcnn::set_error("%s: %s", __func__, msg); \
+            ::srcnn::set_error("%s: %s", who, msg);      \
             return SRCNN_ERR_ARG;                        \
         }                                                \
     } while (0)
+
+#define SRCNN_REQUIRE(cond, msg) SRCNN_REQUIRE_AS(__func__, cond, msg)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

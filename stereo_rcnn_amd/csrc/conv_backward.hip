@@ -16,7 +16,8 @@
 //                            global rows -- is read back with ds_read_b32 at consecutive addresses over the 32 lanes of a half
 //                            wave: conflict-free (the two halves are served separately) and no padding is needed.
 //   wgrad_reduce_kernel      split-K partials -> dw, ascending slice order
-// (the mask / bias pass, the two reductions and the call's layout are in conv_backward_common.h: the f16x3 backward shares them)
+// (the mask / bias pass, the two reductions, the call's layout and dgrad's gather, InPixelGather, are in
+// conv_backward_common.h: the f16x3 backward shares them)
 #include "conv_backward_common.h"
 
 namespace srcnn {
@@ -54,24 +55,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
 
     const int lrow = t >> 3;          // 0..31
     const int lcol = (t & 7) * 4;     // float offset inside the 32-float run
-    int a_h[A_LD], a_w[A_LD], a_base[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        if (m < p.Min) {
-            const int hw = p.H * p.W;
-            const int b = m / hw;
-            const int rem = m - b * hw;
-            const int h = rem / p.W;
-            a_h[i] = h + p.pad;
-            a_w[i] = rem - h * p.W + p.pad;
-            a_base[i] = b * p.OH * p.OW;
-        } else {
-            a_h[i] = -(1 << 28);
-            a_w[i] = 0;
-            a_base[i] = 0;
-        }
-    }
+    const InPixelGather<A_LD> a(m0, lrow, p);
     const WeightRows<B_LD> b(p.wt, n0, lrow, lcol, p.Cin, (size_t)p.taps * p.Cp);
 
     float4 ra[A_LD], rb[B_LD];
@@ -81,15 +65,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(const BwdArgs p)
         const int kh = tap / p.KW;
         const int kw = tap - kh * p.KW;
 #pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const int th = a_h[i] - kh, tw = a_w[i] - kw;
-            bool ok = th >= 0 && tw >= 0;
-            const int oh = ok ? th / p.stride : 0, ow = ok ? tw / p.stride : 0;
-            ok = ok && oh * p.stride == th && ow * p.stride == tw && oh < p.OH && ow < p.OW;
-            const int pix = ok ? a_base[i] + oh * p.OW + ow : 0;
-            const float4 v = *reinterpret_cast<const float4 *>(p.g + (size_t)pix * p.gcs + p.gco + c0 + lcol);
-            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int i = 0; i < A_LD; ++i) ra[i] = a.load(i, kh, kw, c0 + lcol);
         b.load(kt, rb);
     };
     auto store_tile = [&](int buf) {      // conv_mfma_kernel's store
@@ -156,6 +132,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const BwdArgs p)
     const int kt_begin = blockIdx.y * p.w_kt_per_split;
     const int kt_end = min(p.w_nkt, kt_begin + p.w_kt_per_split);
 
+    // Own copy of the two operand loads that conv_wgrad_f16x3_kernel repeats, kept after measurement: with both kernels on one
+    // shared pair of load functions the 24-channel layers, whose backward is mostly this kernel, were 3.5 % (RPN head) and 2.5 %
+    // (linear heads) slower in two consecutive jobs, and with this copy back they are inside the parent-against-parent spread
+    // (profiles/train_conv_staging_ab.txt).
     // A: g rows.  This thread's channel group is the same in every K tile
     const int a_c = (t % A_Q) * 4, a_r = t / A_Q;
     const bool a_ok = n0 + a_c < p.Cp;

@@ -1,8 +1,10 @@
 // What the two convolution backwards share (conv_backward.hip: exact fp32; conv_backward_f16x3.hip: 3 x f16 split): the kernel
-// arguments, the call's layout, the mask / bias pass with its defined summation order, and the split-K reduction.
+// arguments, the call's layout, dgrad's operand gather (InPixelGather), the mask / bias pass with its defined summation order,
+// and the split-K reduction.
 // include/srcnn_hip.h states the definitions and the orders.
 #pragma once
 #include "conv_tile_4w.h"
+#include "conv_train_geometry.h"
 #include <cstdint>
 
 namespace srcnn {
@@ -32,8 +34,48 @@ struct BwdPlan {
     size_t off_gp, off_db, off_wt, off_part, off_scale, bytes;
 };
 
-// ABSMAX (the f16x3 backward): the largest |g| of the call also goes into *gmax as its float bits, which order like the values
-// for non-negative floats -- one integer atomicMax per wave; the word must be zero before the launch.
+// dgrad's A operand: the thread's A_LD input pixels m0 + lrow + 32 i, and for a tap the output pixel whose gradient reaches them
+// through it: ((h + pad - kh) / stride, (w + pad - kw) / stride) where both divisions are exact and in range.  Holds a reference
+// to the kernel's arguments, like OutPixelGather.
+template <int A_LD>
+struct InPixelGather {
+    const BwdArgs &p;
+    int a_h[A_LD], a_w[A_LD], a_base[A_LD];
+    __device__ __forceinline__ InPixelGather(int m0, int lrow, const BwdArgs &args) : p(args)
+    {
+#pragma unroll
+        for (int i = 0; i < A_LD; ++i) {
+            const int m = m0 + lrow + 32 * i;
+            if (m < p.Min) {
+                const int hw = p.H * p.W;
+                const int b = m / hw;
+                const int rem = m - b * hw;
+                const int h = rem / p.W;
+                a_h[i] = h + p.pad;
+                a_w[i] = rem - h * p.W + p.pad;
+                a_base[i] = b * p.OH * p.OW;
+            } else {
+                a_h[i] = -(1 << 28);
+                a_w[i] = 0;
+                a_base[i] = 0;
+            }
+        }
+    }
+    // the thread's float4 of g at that output pixel, channels c .. c + 3 (zeros where no output pixel reads the input pixel there)
+    __device__ __forceinline__ float4 load(int i, int kh, int kw, int c) const
+    {
+        const int th = a_h[i] - kh, tw = a_w[i] - kw;
+        bool ok = th >= 0 && tw >= 0;
+        const int oh = ok ? th / p.stride : 0, ow = ok ? tw / p.stride : 0;
+        ok = ok && oh * p.stride == th && ow * p.stride == tw && oh < p.OH && ow < p.OW;
+        const int pix = ok ? a_base[i] + oh * p.OW + ow : 0;
+        const float4 v = *reinterpret_cast<const float4 *>(p.g + (size_t)pix * p.gcs + p.gco + c);
+        return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+};
+
+// ABSMAX (the f16x3 backward): the largest |g| of the call also goes into *gmax (wave_absmax_to_word); the word must be zero
+// before the launch.
 template <bool ABSMAX>
 __global__ __launch_bounds__(256) void bwd_mask_bias_kernel(const BwdArgs p, unsigned *gmax)
 {
@@ -57,11 +99,7 @@ __global__ __launch_bounds__(256) void bwd_mask_bias_kernel(const BwdArgs p, uns
         s += v;
         if (ABSMAX) mx = fmaxf(mx, fabsf(v));
     }
-    if (ABSMAX) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        if ((t & 63) == 0 && mx > 0.f) atomicMax(gmax, __float_as_uint(mx));
-    }
+    if (ABSMAX) wave_absmax_to_word(mx, gmax);
     if (!p.db) return;
     red[r][c] = s;
     __syncthreads();
@@ -118,29 +156,11 @@ static int bwd_prepare(const srcnn_conv_bwd_desc *d, BwdArgs &a, BwdPlan &pl, bo
     SRCNN_REQUIRE(!d->head_w && !d->head_wf, "a fused head has no backward");
     SRCNN_REQUIRE(!d->x2, "a second input has no backward");
     SRCNN_REQUIRE(!d->up_top, "the fused upsample-add has no backward");
-    SRCNN_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->Cin > 0, "bad shape: sizes must be positive");
-    SRCNN_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "bad shape: kernel, stride > 0 and pad >= 0");
-    SRCNN_REQUIRE(d->H + 2 * d->pad >= d->KH && d->W + 2 * d->pad >= d->KW &&
-                      d->OH == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
-                  "bad shape: OH / OW are not the forward's output size");
-    SRCNN_REQUIRE(d->Cin % BK == 0, "Cin must be a positive multiple of 32");
-    SRCNN_REQUIRE(d->x_cstride >= d->Cin && d->x_cstride % 4 == 0, "x_cstride: a stride of at least Cin floats, a multiple of 4");
-    SRCNN_REQUIRE(d->y_coffset >= 0 && d->y_cstride >= d->y_coffset + d->Cout, "y_cstride: a stride of at least y_coffset + Cout floats");
-    SRCNN_REQUIRE(!d->dw || (reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "x must be 16-byte aligned (stride-4 vector loads)");
-    SRCNN_REQUIRE((unsigned)d->tile_mr <= 2 && (unsigned)d->tile_nr <= 2, "tile_mr / tile_nr must be 0, 1 or 2");
     SRCNN_REQUIRE(d->splits >= 0, "splits must be >= 0");
-    const long long M = (long long)d->B * d->OH * d->OW, Min = (long long)d->B * d->H * d->W;
-    const long long Kw = (long long)d->KH * d->KW * d->Cin;
-    SRCNN_REQUIRE(M < (1LL << 31) && Min < (1LL << 31) && Kw < (1LL << 31) && d->Cout < (1 << 20) && d->KH < 256 && d->KW < 256,
-                  "bad shape: tensor too large");
-
+    const int rc = check_conv_geometry(__func__, d, d->dw != nullptr, a);
+    if (rc != SRCNN_OK) return rc;
     a.x = d->x; a.w = d->w; a.y = d->y; a.dy = d->dy;
     a.dx = d->dx; a.dw = d->dw; a.db = d->db; a.g_out = d->g_out;
-    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
-    a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.ycs = d->y_cstride; a.yco = d->y_coffset; a.relu = d->relu ? 1 : 0;
-    a.M = (int)M; a.Min = (int)Min; a.taps = d->KH * d->KW; a.Kw = (int)Kw;
     const bool gemm = d->dx || d->dw;
     pl.pass = f16x3 || d->relu || d->db || d->g_out || d->Cout % BK != 0 || d->y_cstride % 4 != 0 || d->y_coffset % 4 != 0 ||
               (reinterpret_cast<uintptr_t>(d->dy) & 15) != 0;

@@ -48,8 +48,9 @@
 //       slices' (already rescaled) sums are added in ascending slice order by wgrad_reduce_kernel.
 //   Inside one MFMA step the 16 products are summed by the matrix unit in its own fixed order.
 //
-// pow2_scale, split_f16, f16x3_clear_scales, absmax_kernel and the K tile's MFMA loop live in conv_f16x3_scaled.h, shared with the
-// training forward (conv_forward_f16x3.hip).
+// pow2_scale, split_f16, f16x3_clear_scales, absmax_kernel, the K tile's MFMA loop and dgrad's staging and K loop
+// (f16x3_scaled_kloop) live in conv_f16x3_scaled.h, shared with the training forward (conv_forward_f16x3.hip); dgrad's gather
+// (InPixelGather) lives in conv_backward_common.h, shared with the fp32 backward.
 //
 // srcnn_conv2d_backward_f16x3_maxima: the caller already holds max|x| of the saved x as a device word (the forward found it, or
 // its producer's epilogue did); wgrad reads s_x from that word and the max|x| pass is not launched.  Nothing else differs.
@@ -92,10 +93,7 @@ template <int MR, int NR>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_f16x3_kernel(const BwdArgs p, const F16x3Args q)
 {
     constexpr int BM = 64 * MR, BN = 64 * NR;
-    constexpr int A_LD = BM / 32;   // float4 loads per thread per tile (A, fp32)
-    constexpr int B_LD = BN / 64;   // uint4 loads per thread per tile and per panel (B, f16)
-    constexpr int PANEL_A = BM * HROW, PANEL_B = BN * HROW;
-    __shared__ __attribute__((aligned(16))) _Float16 smem[2][2 * PANEL_A + 2 * PANEL_B];
+    __shared__ __attribute__((aligned(16))) _Float16 smem[2][f16x3_buf_halves(MR, NR)];
 
     const int t = threadIdx.x;
     const int logical = xcd_logical_tile(blockIdx.x, p.d_mtiles * p.d_ntiles);
@@ -103,97 +101,12 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_f16x3_kernel(const BwdArgs 
     const int m0 = mt * BM, n0 = nt * BN;
     const Pow2 sg = pow2_scale(q.amax[0]), sw = pow2_scale(q.amax[1]);
 
-    // A: conv_dgrad_kernel's gather (rows = input pixels)
+    // A: conv_dgrad_kernel's gather (rows = input pixels).  B: rows = input channels of the re-laid planes, K = taps * Cp contiguous
     const int lrow = t >> 3, lcol = (t & 7) * 4;
-    int a_h[A_LD], a_w[A_LD], a_base[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        if (m < p.Min) {
-            const int hw = p.H * p.W;
-            const int b = m / hw;
-            const int rem = m - b * hw;
-            const int h = rem / p.W;
-            a_h[i] = h + p.pad;
-            a_w[i] = rem - h * p.W + p.pad;
-            a_base[i] = b * p.OH * p.OW;
-        } else {
-            a_h[i] = -(1 << 28);
-            a_w[i] = 0;
-            a_base[i] = 0;
-        }
-    }
-    // B: conv_f16x3_kernel's two f16 panels (rows = input channels, K = taps * Cp contiguous)
-    const int brow = t >> 2, bcol = (t & 3) * 8;
-    const _Float16 *bh_ptr[B_LD], *bl_ptr[B_LD];
-    bool b_ok[B_LD];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-        const int n = n0 + brow + 64 * i;
-        b_ok[i] = n < p.Cin;
-        const size_t off = (size_t)(b_ok[i] ? n : 0) * p.taps * p.Cp + bcol;
-        bh_ptr[i] = q.wt_hi + off;
-        bl_ptr[i] = q.wt_lo + off;
-    }
-    const int a_sw = ((((t & 7) >> 1) ^ ((lrow >> 2) & 3)) << 3) + ((t & 1) << 2);
-    const int b_sw = ((t & 3) ^ ((brow >> 2) & 3)) << 3;
-
-    float4 ra[A_LD];
-    uint4 rbh[B_LD], rbl[B_LD];
-    auto load_tile = [&](int kt) {
-        const int tap = kt / p.d_ctiles;
-        const int c0 = (kt - tap * p.d_ctiles) * BK;
-        const int kh = tap / p.KW;
-        const int kw = tap - kh * p.KW;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const int th = a_h[i] - kh, tw = a_w[i] - kw;
-            bool ok = th >= 0 && tw >= 0;
-            const int oh = ok ? th / p.stride : 0, ow = ok ? tw / p.stride : 0;
-            ok = ok && oh * p.stride == th && ow * p.stride == tw && oh < p.OH && ow < p.OW;
-            const int pix = ok ? a_base[i] + oh * p.OW + ow : 0;
-            const float4 v = *reinterpret_cast<const float4 *>(p.g + (size_t)pix * p.gcs + p.gco + c0 + lcol);
-            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) {
-            const uint4 vh = *reinterpret_cast<const uint4 *>(bh_ptr[i] + (size_t)kt * BK);
-            const uint4 vl = *reinterpret_cast<const uint4 *>(bl_ptr[i] + (size_t)kt * BK);
-            rbh[i] = b_ok[i] ? vh : make_uint4(0, 0, 0, 0);
-            rbl[i] = b_ok[i] ? vl : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto store_tile = [&](int buf) {
-        _Float16 *sah = smem[buf], *sal = smem[buf] + PANEL_A;
-        _Float16 *sbh = smem[buf] + 2 * PANEL_A, *sbl = sbh + PANEL_B;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-            half4 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                _Float16 h, l;
-                split_f16(v[e], sg.s, h, l);
-                hi[e] = h;
-                lo[e] = l;
-            }
-            const int o = (lrow + 32 * i) * HROW + a_sw;
-            *reinterpret_cast<half4 *>(sah + o) = hi;
-            *reinterpret_cast<half4 *>(sal + o) = lo;
-        }
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) {
-            const int o = (brow + 64 * i) * HROW + b_sw;
-            *reinterpret_cast<uint4 *>(sbh + o) = rbh[i];
-            *reinterpret_cast<uint4 *>(sbl + o) = rbl[i];
-        }
-    };
-
+    const InPixelGather<BM / 32> a(m0, lrow, p);
     const WaveGeom g(t);
     floatx16 acc[MR][NR], accx[MR][NR];
-    zero_acc(acc);
-    zero_acc(accx);
-    ktile_pipeline(0, p.d_nkt, load_tile, store_tile, [&](int buf) { f16x3_ktile(smem[buf], g, acc, accx); });
+    f16x3_scaled_kloop(smem[0], a, lrow, lcol, sg.s, q.wt_hi, q.wt_lo, n0, p.Cin, p.d_ctiles, p.KW, p.d_nkt, g, acc, accx);
 
     // every (row, col) of the tile inside the tensor is stored, zeros included: dx needs no fill
 #pragma unroll
@@ -255,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16x3_kernel(const BwdArgs 
 {
     constexpr int BM = 64 * MR, BN = 64 * NR;
     constexpr int PANEL_A = BM * HROW, PANEL_B = BN * HROW;
-    __shared__ __attribute__((aligned(16))) _Float16 smem[2][2 * PANEL_A + 2 * PANEL_B];
+    __shared__ __attribute__((aligned(16))) _Float16 smem[2][f16x3_buf_halves(MR, NR)];
 
     const int t = threadIdx.x;
     const int logical = xcd_logical_tile(blockIdx.x, p.w_mtiles * p.w_ntiles);
@@ -265,6 +178,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16x3_kernel(const BwdArgs 
     const int kt_end = min(p.w_nkt, kt_begin + p.w_kt_per_split);
     const Pow2 sg = pow2_scale(q.amax[0]), sx = pow2_scale(*q.xmax);
 
+    // The two operand loads are conv_wgrad_kernel's, a second copy on purpose: see the comment there.
     // A: g rows.  This thread's channel group is the same in every K tile
     WgradOperand<BM> A(t);
     const bool a_ok = n0 + 4 * A.cg < p.Cp;

@@ -1,6 +1,8 @@
 // What the training-side 3 x f16 calls share (conv_backward_f16x3.hip: dgrad and wgrad; conv_forward_f16x3.hip: the forward): the
-// device-found power-of-two scale of a tensor, the split of a scaled fp32 value into two halves, and one K tile of the
-// three-product MFMA loop.  One copy, so that the forward and the backward round alike.  include/srcnn_hip.h states the scheme.
+// device-found power-of-two scale of a tensor, the split of a scaled fp32 value into two halves, one K tile of the
+// three-product MFMA loop, and the staging + K loop of the tile that the forward and dgrad have in common (fp32 A split on the way
+// into LDS, prepared f16 B planes: F16PlaneRows, f16x3_store_a, f16x3_scaled_kloop).  One copy, so that the forward and the
+// backward round alike.  include/srcnn_hip.h states the scheme.
 #pragma once
 #include "conv_tile_4w.h"
 #include <cstdint>
@@ -42,15 +44,6 @@ static __global__ void f16x3_clear_scales(unsigned *amax, unsigned *extra)
 {
     if (threadIdx.x < 4 && amax) amax[threadIdx.x] = 0u;
     if (threadIdx.x == 4 && extra) *extra = 0u;
-}
-
-// A thread's max |v| (>= 0, NaNs already dropped by fmaxf) -> the word: one integer atomicMax on the float bits per wave, none for
-// a wave of zeros.  Every lane of the wave must call it.
-__device__ __forceinline__ void wave_absmax_to_word(float mx, unsigned *word)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(word, __float_as_uint(mx));
 }
 
 // max |v| over `rows` rows of `len` floats at a stride of `stride` floats.  VEC: len, stride multiples of 4 and a 16-byte aligned base
@@ -126,6 +119,117 @@ __device__ __forceinline__ void f16x3_ktile(const _Float16 *buf, const WaveGeom 
                 accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], accx[i][j], 0, 0, 0);
             }
     }
+}
+
+// halves in one such buffer
+constexpr int f16x3_buf_halves(int mr, int nr) { return 2 * 64 * (mr + nr) * HROW; }
+
+// ---- The tile of conv_fwd_f16x3_kernel and conv_dgrad_f16x3_kernel: A is gathered as fp32 and split with its tensor's scale on the
+// way into LDS, B comes from prepared hi / lo f16 planes of K-contiguous rows.
+
+// B side: the thread's B_LD rows n0 + (t >> 2) + 64 i of the two planes (rows of K halves; rows beyond `rows` read as zeros), one
+// 16-byte chunk of each per K tile
+template <int B_LD>
+struct F16PlaneRows {
+    const _Float16 *hi[B_LD], *lo[B_LD];
+    bool ok[B_LD];
+    int brow, sw;
+    uint4 rh[B_LD], rl[B_LD];
+    __device__ __forceinline__ F16PlaneRows(const _Float16 *hi_plane, const _Float16 *lo_plane, int n0, int rows, size_t K)
+    {
+        const int t = threadIdx.x, bcol = (t & 3) * 8;
+        brow = t >> 2;
+        sw = ((t & 3) ^ ((brow >> 2) & 3)) << 3;
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const int n = n0 + brow + 64 * i;
+            ok[i] = n < rows;
+            const size_t off = (size_t)(ok[i] ? n : 0) * K + bcol;
+            hi[i] = hi_plane + off;
+            lo[i] = lo_plane + off;
+        }
+    }
+    __device__ __forceinline__ void load(int kt)
+    {
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const uint4 vh = *reinterpret_cast<const uint4 *>(hi[i] + (size_t)kt * BK);
+            const uint4 vl = *reinterpret_cast<const uint4 *>(lo[i] + (size_t)kt * BK);
+            rh[i] = ok[i] ? vh : make_uint4(0, 0, 0, 0);
+            rl[i] = ok[i] ? vl : make_uint4(0, 0, 0, 0);
+        }
+    }
+    // registers -> the B_hi / B_lo panels
+    __device__ __forceinline__ void store(_Float16 *b_hi, _Float16 *b_lo) const
+    {
+#pragma unroll
+        for (int i = 0; i < B_LD; ++i) {
+            const int o = (brow + 64 * i) * HROW + sw;
+            *reinterpret_cast<uint4 *>(b_hi + o) = rh[i];
+            *reinterpret_cast<uint4 *>(b_lo + o) = rl[i];
+        }
+    }
+};
+
+__device__ __forceinline__ void split_f16x4(const float4 &f, float s, half4 &hi, half4 &lo)
+{
+    const float v[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        _Float16 h, l;
+        split_f16(v[e], s, h, l);
+        hi[e] = h;
+        lo[e] = l;
+    }
+}
+
+// A store: the thread's float4 ra[i] of row lrow + 32 i, floats lcol .. lcol + 3 (lcol a multiple of 4), split with s into the
+// A_hi / A_lo panels
+template <int A_LD>
+__device__ __forceinline__ void f16x3_store_a(const float4 (&ra)[A_LD], int lrow, int lcol, float s, _Float16 *a_hi, _Float16 *a_lo)
+{
+    const int sw = (((lcol >> 3) ^ ((lrow >> 2) & 3)) << 3) + (lcol & 4);
+#pragma unroll
+    for (int i = 0; i < A_LD; ++i) {
+        half4 hi, lo;
+        split_f16x4(ra[i], s, hi, lo);
+        const int o = (lrow + 32 * i) * HROW + sw;
+        *reinterpret_cast<half4 *>(a_hi + o) = hi;
+        *reinterpret_cast<half4 *>(a_lo + o) = lo;
+    }
+}
+
+// The tile's whole K loop into zeroed accumulators.  K tile kt is channels [32 c, 32 c + 32) of tap (kh, kw), kt = (kh KW + kw) ctiles + c;
+// a.load(i, kh, kw, channel) is the gather (OutPixelGather, InPixelGather), built by the kernel for the same (lrow, lcol) = (t >> 3,
+// (t & 7) * 4) it passes here -- row lrow + 32 i, floats lcol .. lcol + 3 of the tile's A rows -- and s_a its tensor's scale; the
+// planes have nkt * 32 halves per row.  smem: two buffers of f16x3_buf_halves(MR, NR).
+template <int MR, int NR, class Gather>
+__device__ __forceinline__ void f16x3_scaled_kloop(_Float16 *smem, const Gather &a, int lrow, int lcol, float s_a, const _Float16 *b_hi,
+                                                   const _Float16 *b_lo, int n0, int b_rows, int ctiles, int KW, int nkt, const WaveGeom &g,
+                                                   floatx16 (&acc)[MR][NR], floatx16 (&accx)[MR][NR])
+{
+    constexpr int A_LD = 2 * MR, PANEL_A = 64 * MR * HROW, PANEL_B = 64 * NR * HROW, BUF = f16x3_buf_halves(MR, NR);
+    F16PlaneRows<NR> b(b_hi, b_lo, n0, b_rows, (size_t)nkt * BK);
+    float4 ra[A_LD];
+    zero_acc(acc);
+    zero_acc(accx);
+    ktile_pipeline(
+        0, nkt,
+        [&](int kt) {
+            const int tap = kt / ctiles;
+            const int c0 = (kt - tap * ctiles) * BK;
+            const int kh = tap / KW;
+            const int kw = tap - kh * KW;
+#pragma unroll
+            for (int i = 0; i < A_LD; ++i) ra[i] = a.load(i, kh, kw, c0 + lcol);
+            b.load(kt);
+        },
+        [&](int buf) {
+            _Float16 *s = smem + buf * BUF;
+            f16x3_store_a(ra, lrow, lcol, s_a, s, s + PANEL_A);
+            b.store(s + 2 * PANEL_A, s + 2 * PANEL_A + PANEL_B);
+        },
+        [&](int buf) { f16x3_ktile(smem + buf * BUF, g, acc, accx); });
 }
 
 }  // namespace srcnn

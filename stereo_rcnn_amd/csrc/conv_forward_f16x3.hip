@@ -11,9 +11,10 @@
 //   absmax_kernel            max|w|, max|x| (x: channels [0, Cin) of every pixel; floats behind Cin are not read)
 //   fwd_weight_split         w (Cout, taps, Cin) fp32 -> w_hi, w_lo (Cp, taps, Cin) f16, rows [Cout, Cp) zero.  K is already
 //                            contiguous in the engine's layout: no transpose
-//   conv_fwd_f16x3_kernel    conv_dgrad_f16x3_kernel's tile, panels and MFMA loop with the forward's gather: rows = the B OH OW
-//                            output pixels, columns = Cout.  x stays fp32 in memory and is split while it is staged into LDS;
-//                            taps outside the image and rows beyond M are staged as zeros, whose halves are exact zeros.
+//   conv_fwd_f16x3_kernel    conv_dgrad_f16x3_kernel's tile, staging and K loop (f16x3_scaled_kloop, conv_f16x3_scaled.h) with the
+//                            forward's gather (OutPixelGather, conv_tile_4w.h): rows = the B OH OW output pixels, columns = Cout.
+//                            x stays fp32 in memory and is split while it is staged into LDS; taps outside the image and rows
+//                            beyond M are staged as zeros, whose halves are exact zeros.
 //
 // SUMMATION ORDER (fixed by the geometry alone: never split, and an element's K order does not depend on the tile it falls in).
 //   K tiles over taps in (kh, kw) row-major order, inside a tap the 32-channel tiles of Cin ascending; a K tile is two MFMA steps
@@ -29,6 +30,7 @@
 // columns < Cout, after bias, residual and ReLU), reduces it over the wave and issues one integer atomicMax per wave; the word is
 // cleared by f16x3_clear_scales with the workspace's.  The <.., false> kernel is the one the plain entry launches.
 #include "conv_f16x3_scaled.h"
+#include "conv_train_geometry.h"
 
 namespace srcnn {
 
@@ -63,15 +65,8 @@ __global__ __launch_bounds__(256) void fwd_weight_split(const FwdArgs p)
         const int n = (int)(i / per_row);
         float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
         if (n < p.Cout) f = *reinterpret_cast<const float4 *>(p.w + i * 4);
-        const float v[4] = {f.x, f.y, f.z, f.w};
         half4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            _Float16 h, l;
-            split_f16(v[e], s, h, l);
-            hi[e] = h;
-            lo[e] = l;
-        }
+        split_f16x4(f, s, hi, lo);
         *reinterpret_cast<half4 *>(p.w_hi + i * 4) = hi;
         *reinterpret_cast<half4 *>(p.w_lo + i * 4) = lo;
     }
@@ -81,10 +76,7 @@ template <int MR, int NR, bool YMAX>
 __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
 {
     constexpr int BM = 64 * MR, BN = 64 * NR;
-    constexpr int A_LD = BM / 32;   // float4 loads per thread per tile (A, fp32)
-    constexpr int B_LD = BN / 64;   // uint4 loads per thread per tile and per panel (B, f16)
-    constexpr int PANEL_A = BM * HROW, PANEL_B = BN * HROW;
-    __shared__ __attribute__((aligned(16))) _Float16 smem[2][2 * PANEL_A + 2 * PANEL_B];
+    __shared__ __attribute__((aligned(16))) _Float16 smem[2][f16x3_buf_halves(MR, NR)];
 
     const int t = threadIdx.x;
     const int logical = xcd_logical_tile(blockIdx.x, p.mtiles * p.ntiles);
@@ -92,95 +84,13 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_f16x3_kernel(const FwdArgs p)
     const int m0 = mt * BM, n0 = nt * BN;
     const Pow2 sx = pow2_scale(*p.xmax), sw = pow2_scale(p.amax[1]);
 
-    // A: the forward's gather (rows = output pixels); a row beyond M never passes the image test
+    // A: the forward's gather (rows = output pixels); a row beyond M never passes the image test.  B: rows = output channels of the
+    // Cp-row planes, K = taps * Cin contiguous
     const int lrow = t >> 3, lcol = (t & 7) * 4;
-    int ih0[A_LD], iw0[A_LD], pix0[A_LD];
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        if (m < p.M) {
-            const int ohw = p.OH * p.OW;
-            const int b = m / ohw;
-            const int rem = m - b * ohw;
-            const int oh = rem / p.OW;
-            ih0[i] = oh * p.stride - p.pad;
-            iw0[i] = (rem - oh * p.OW) * p.stride - p.pad;
-            pix0[i] = (b * p.H + ih0[i]) * p.W + iw0[i];
-        } else {
-            ih0[i] = -(1 << 28);
-            iw0[i] = 0;
-            pix0[i] = 0;
-        }
-    }
-    // B: two f16 panels (rows = output channels of the Cp-row planes, K = taps * Cin contiguous)
-    const int brow = t >> 2, bcol = (t & 3) * 8;
-    const _Float16 *bh_ptr[B_LD], *bl_ptr[B_LD];
-    bool b_ok[B_LD];
-#pragma unroll
-    for (int i = 0; i < B_LD; ++i) {
-        const int n = n0 + brow + 64 * i;
-        b_ok[i] = n < p.Cp;
-        const size_t off = (size_t)(b_ok[i] ? n : 0) * p.Kw + bcol;
-        bh_ptr[i] = p.w_hi + off;
-        bl_ptr[i] = p.w_lo + off;
-    }
-    const int a_sw = ((((t & 7) >> 1) ^ ((lrow >> 2) & 3)) << 3) + ((t & 1) << 2);
-    const int b_sw = ((t & 3) ^ ((brow >> 2) & 3)) << 3;
-
-    float4 ra[A_LD];
-    uint4 rbh[B_LD], rbl[B_LD];
-    auto load_tile = [&](int kt) {
-        const int tap = kt / p.ctiles;
-        const int c0 = (kt - tap * p.ctiles) * BK;
-        const int kh = tap / p.KW;
-        const int kw = tap - kh * p.KW;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const int ih = ih0[i] + kh, iw = iw0[i] + kw;
-            const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            const int pix = ok ? pix0[i] + kh * p.W + kw : 0;
-            const float4 v = *reinterpret_cast<const float4 *>(p.x + (size_t)pix * p.xcs + c0 + lcol);
-            ra[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) {
-            const uint4 vh = *reinterpret_cast<const uint4 *>(bh_ptr[i] + (size_t)kt * BK);
-            const uint4 vl = *reinterpret_cast<const uint4 *>(bl_ptr[i] + (size_t)kt * BK);
-            rbh[i] = b_ok[i] ? vh : make_uint4(0, 0, 0, 0);
-            rbl[i] = b_ok[i] ? vl : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto store_tile = [&](int buf) {
-        _Float16 *sah = smem[buf], *sal = smem[buf] + PANEL_A;
-        _Float16 *sbh = smem[buf] + 2 * PANEL_A, *sbl = sbh + PANEL_B;
-#pragma unroll
-        for (int i = 0; i < A_LD; ++i) {
-            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-            half4 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                _Float16 h, l;
-                split_f16(v[e], sx.s, h, l);
-                hi[e] = h;
-                lo[e] = l;
-            }
-            const int o = (lrow + 32 * i) * HROW + a_sw;
-            *reinterpret_cast<half4 *>(sah + o) = hi;
-            *reinterpret_cast<half4 *>(sal + o) = lo;
-        }
-#pragma unroll
-        for (int i = 0; i < B_LD; ++i) {
-            const int o = (brow + 64 * i) * HROW + b_sw;
-            *reinterpret_cast<uint4 *>(sbh + o) = rbh[i];
-            *reinterpret_cast<uint4 *>(sbl + o) = rbl[i];
-        }
-    };
-
+    const OutPixelGather<BM / 32, FwdArgs> a(m0, lrow, p);
     const WaveGeom g(t);
     floatx16 acc[MR][NR], accx[MR][NR];
-    zero_acc(acc);
-    zero_acc(accx);
-    ktile_pipeline(0, p.nkt, load_tile, store_tile, [&](int buf) { f16x3_ktile(smem[buf], g, acc, accx); });
+    f16x3_scaled_kloop(smem[0], a, lrow, lcol, sx.s, p.w_hi, p.w_lo, n0, p.Cp, p.ctiles, p.KW, p.nkt, g, acc, accx);
 
     // every (row, col) of the tile inside (M, Cout) is stored once; the 32 lanes of a row write 128 contiguous bytes
     float mx = 0.f;                 // YMAX: max |v| over what this thread stores, nothing else
@@ -215,29 +125,11 @@ static int fwd_prepare(const srcnn_conv_fwd_f16x3_desc *d, FwdArgs &a, FwdPlan &
     SRCNN_REQUIRE(d->w != nullptr, "null pointer: w");
     SRCNN_REQUIRE(d->y != nullptr, "null pointer: y");
     SRCNN_REQUIRE(d->x_format == SRCNN_FMT_F32 && d->y_format == SRCNN_FMT_F32, "format must be SRCNN_FMT_F32");
-    SRCNN_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cout > 0 && d->Cin > 0, "bad shape: sizes must be positive");
-    SRCNN_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "bad shape: kernel, stride > 0 and pad >= 0");
-    SRCNN_REQUIRE(d->H + 2 * d->pad >= d->KH && d->W + 2 * d->pad >= d->KW &&
-                      d->OH == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->OW == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
-                  "bad shape: OH / OW are not the forward's output size");
-    SRCNN_REQUIRE(d->Cin % BK == 0, "Cin must be a positive multiple of 32");
-    SRCNN_REQUIRE(d->x_cstride >= d->Cin && d->x_cstride % 4 == 0, "x_cstride: a stride of at least Cin floats, a multiple of 4");
-    SRCNN_REQUIRE(d->y_coffset >= 0 && d->y_cstride >= d->y_coffset + d->Cout, "y_cstride: a stride of at least y_coffset + Cout floats");
-    SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "x must be 16-byte aligned (stride-4 vector loads)");
     SRCNN_REQUIRE((reinterpret_cast<uintptr_t>(d->w) & 15) == 0, "w must be 16-byte aligned (vector loads)");
-    SRCNN_REQUIRE((unsigned)d->tile_mr <= 2 && (unsigned)d->tile_nr <= 2, "tile_mr / tile_nr must be 0, 1 or 2");
-    const long long M = (long long)d->B * d->OH * d->OW, Min = (long long)d->B * d->H * d->W;
-    const long long Kw = (long long)d->KH * d->KW * d->Cin;
-    SRCNN_REQUIRE(M < (1LL << 31) && Min < (1LL << 31) && Kw < (1LL << 31) && d->Cout < (1 << 20) && d->KH < 256 && d->KW < 256,
-                  "bad shape: tensor too large");
-
+    const int rc = check_conv_geometry(__func__, d, true, a);
+    if (rc != SRCNN_OK) return rc;
     a.x = d->x; a.w = d->w; a.bias = d->bias; a.res = d->residual; a.y = d->y;
     a.w_hi = a.w_lo = nullptr; a.amax = nullptr; a.xmax = nullptr; a.ymax = nullptr;
-    a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.xcs = d->x_cstride;
-    a.OH = d->OH; a.OW = d->OW; a.Cout = d->Cout; a.Cp = cdiv(d->Cout, BK) * BK;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.ycs = d->y_cstride; a.yco = d->y_coffset; a.relu = d->relu ? 1 : 0;
-    a.M = (int)M; a.Min = (int)Min; a.taps = d->KH * d->KW; a.Kw = (int)Kw;
 
     // the engine's rule: the largest tile that still gives two workgroups per CU
     choose_tile_4w(a.M, a.Cout, &pl.mr, &pl.nr);

@@ -1,4 +1,5 @@
-// The 4-wave implicit-GEMM workgroup shared by conv_mfma_kernel, conv_f16x3_kernel, conv_dgrad_kernel and conv_wgrad_kernel:
+// The 4-wave implicit-GEMM workgroup shared by conv_mfma_kernel, conv_f16x3_kernel, conv_dgrad_kernel, conv_wgrad_kernel and the
+// training-side f16x3 kernels (conv_f16x3_scaled.h):
 // 256 threads as a 2x2 wave grid, (32*MR)x(32*NR) wave tiles of 32x32 MFMAs, register prefetch, double-buffered LDS.
 //
 // The forward kernels compute
@@ -78,12 +79,13 @@ __device__ __forceinline__ void ktile_pipeline(int kt_begin, int kt_end, Load lo
 }
 
 // Forward A operand: the thread's A_LD output pixels m0 + lrow + 32 i, and for a tap whether it lies inside the image and where.
-// Holds a reference to the kernel's argument struct: a local of the kernel, never stored or returned.
-template <int A_LD>
+// Holds a reference to the kernel's argument struct (ConvArgs, or any struct with its x, xcs, H, W, OH, OW, stride, pad, M): a
+// local of the kernel, never stored or returned.
+template <int A_LD, class Args = ConvArgs>
 struct OutPixelGather {
-    const ConvArgs &p;
+    const Args &p;
     int ih0[A_LD], iw0[A_LD], pix0[A_LD];
-    __device__ __forceinline__ OutPixelGather(int m0, int lrow, const ConvArgs &args) : p(args)
+    __device__ __forceinline__ OutPixelGather(int m0, int lrow, const Args &args) : p(args)
     {
 #pragma unroll
         for (int i = 0; i < A_LD; ++i) {
@@ -120,6 +122,15 @@ struct OutPixelGather {
         return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 };
+
+// A thread's max |v| (>= 0, NaNs already dropped by fmaxf) -> the word: one integer atomicMax on the float bits (which order like
+// the values for non-negative floats) per wave, none for a wave of zeros.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_absmax_to_word(float mx, unsigned *word)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(word, __float_as_uint(mx));
+}
 
 // fp32 B operand: the thread's B_LD rows n0 + lrow + 32 i of a K-contiguous (rows, K) matrix, rows beyond `rows` read as zeros
 template <int B_LD>

@@ -691,6 +691,19 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
     return used
 
 
+def _fill_train_geometry(d, cw, B, H, W, OH, OW, x_cstride, y_cstride, y_coffset, relu, tile):
+    """The fields srcnn_conv_bwd_desc and srcnn_conv_fwd_f16x3_desc share, from a ConvW and the call's strides."""
+    d.B, d.H, d.W, d.Cin = B, H, W, cw.cin
+    d.x_cstride = cw.cin if x_cstride is None else x_cstride
+    d.OH, d.OW, d.Cout = OH, OW, cw.cout
+    d.KH, d.KW, d.stride, d.pad = cw.kh, cw.kw, cw.stride, cw.pad
+    d.y_cstride = cw.cout if y_cstride is None else y_cstride
+    d.y_coffset = y_coffset
+    d.relu = cw.relu if relu is None else int(relu)
+    if tile is not None:
+        d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
+
+
 def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), splits=0, x_cstride=None, y_cstride=None, y_coffset=0,
                     relu=None, g_out=None, out=None, tile=None, precision='f32', x_amax=None):
     """Gradients of conv2d(cw, x, ..., precision='f32') (srcnn_conv2d_backward; include/srcnn_hip.h states the sums' orders).
@@ -730,16 +743,9 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     d.dy = dy.data_ptr()
     d.dx, d.dw, d.db = (res[k].data_ptr() if k in res else None for k in ('dx', 'dw', 'db'))
     d.g_out = g_out.data_ptr() if g_out is not None else None
-    d.B, d.H, d.W, d.Cin, d.x_cstride = B, H, W, cw.cin, xcs
-    d.OH, d.OW, d.Cout = OH, OW, cw.cout
-    d.KH, d.KW, d.stride, d.pad = cw.kh, cw.kw, cw.stride, cw.pad
-    d.y_cstride = cw.cout if y_cstride is None else y_cstride
-    d.y_coffset = y_coffset
-    d.relu = cw.relu if relu is None else int(relu)
+    _fill_train_geometry(d, cw, B, H, W, OH, OW, xcs, y_cstride, y_coffset, relu, tile)
     d.splits = int(splits)
     d.precision = 0 if precision == 'f32' else 1
-    if tile is not None:
-        d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
     nbytes = getattr(L, entry + '_workspace_bytes')(ctypes.byref(d))
     ws = _lib.workspace(nbytes, dy.device, "conv_backward")
     if x_amax is not None:
@@ -797,15 +803,7 @@ def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None,
     d.x, d.w, d.y = x.data_ptr(), cw.weight.data_ptr(), y.data_ptr()
     d.bias = cw.bias.data_ptr() if cw.bias is not None else None
     d.residual = residual.data_ptr() if residual is not None else None
-    d.B, d.H, d.W, d.Cin = B, H, W, cw.cin
-    d.x_cstride = cw.cin if x_cstride is None else x_cstride
-    d.OH, d.OW, d.Cout = OH, OW, cw.cout
-    d.KH, d.KW, d.stride, d.pad = cw.kh, cw.kw, cw.stride, cw.pad
-    d.y_cstride = cw.cout if y_cstride is None else y_cstride
-    d.y_coffset = y_coffset
-    d.relu = cw.relu if relu is None else int(relu)
-    if tile is not None:
-        d.tile_mr, d.tile_nr = int(tile[0]), int(tile[1])
+    _fill_train_geometry(d, cw, B, H, W, OH, OW, x_cstride, y_cstride, y_coffset, relu, tile)
     ws = _lib.workspace(L.srcnn_conv2d_forward_f16x3_workspace_bytes(ctypes.byref(d)), x.device, "conv_forward_f16x3")
     if x_amax is None:
         F16X3_MAXIMA['scans'] += 1

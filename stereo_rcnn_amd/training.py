@@ -119,18 +119,18 @@ class _Taps(object):
         return t
 
 
-def _conv(m, x, relu=False, residual=None, bn=None, bp='f32', fp='f32', rm=True):
+def _conv(m, x, prec, relu=False, residual=None, bn=None):
     return autograd.conv2d_nhwc(x, m.weight, m.bias, int(m.stride[0]), int(m.padding[0]), relu, residual, None if bn is None else _bn(bn),
-                                backward_precision=bp, forward_precision=fp, reuse_maxima=rm)
+                                _prec=prec)
 
 
-def _bottleneck(blk, x, name, tap, bp='f32', fp='f32', rm=True):
+def _bottleneck(blk, x, name, tap, prec):
     """resnet.py:66-100: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut(x)), the ReLUs and the residual fused
     into the convolutions as the engine fuses them."""
-    t = tap(name + '.conv1', _conv(blk.conv1, x, True, bn=blk.bn1, bp=bp, fp=fp, rm=rm))
-    t = tap(name + '.conv2', _conv(blk.conv2, t, True, bn=blk.bn2, bp=bp, fp=fp, rm=rm))
-    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, False, bn=blk.downsample[1], bp=bp, fp=fp, rm=rm)
-    return tap(name + '.out', _conv(blk.conv3, t, True, residual=res, bn=blk.bn3, bp=bp, fp=fp, rm=rm))
+    t = tap(name + '.conv1', _conv(blk.conv1, x, prec, True, bn=blk.bn1))
+    t = tap(name + '.conv2', _conv(blk.conv2, t, prec, True, bn=blk.bn2))
+    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, prec, False, bn=blk.downsample[1])
+    return tap(name + '.out', _conv(blk.conv3, t, prec, True, residual=res, bn=blk.bn3))
 
 
 def _stem(model, im_left, im_right):
@@ -217,14 +217,10 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     independent.  reuse_maxima (default True; it matters only where a precision is 'f16x3'): each activation's max |x| is found at
     most once -- in the epilogue of the f16x3 convolution that produced it, or by one scan -- and handed to every f16x3 call that
     consumes it (stereo_rcnn_amd.autograd); every output and gradient keeps its bits."""
+    prec = autograd.Precision(forward_precision, backward_precision, reuse_maxima)
     dev = model.RCNN_toplayer.weight.device
     if dev.type != 'cuda' or not im_left.is_cuda:
         raise NotImplementedError
-    if backward_precision not in ('f32', 'f16x3'):
-        raise ValueError("backward_precision must be 'f32' or 'f16x3' (got %r)" % (backward_precision,))
-    if forward_precision not in ('f32', 'f16x3'):
-        raise ValueError("forward_precision must be 'f32' or 'f16x3' (got %r)" % (forward_precision,))
-    bp, fp, rm = backward_precision, forward_precision, bool(reuse_maxima)
     tap = _Taps(taps if isinstance(taps, dict) else None)
     for p in trainable_parameters(model).values():
         p.requires_grad_(True)
@@ -245,15 +241,15 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         frozen = li <= cfg.RESNET.FIXED_BLOCKS
         with (torch.no_grad() if frozen else contextlib.nullcontext()):
             for b, blk in enumerate(getattr(model, 'RCNN_layer%d' % li)[0]):
-                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, bp, 'f32' if frozen else fp, rm)
+                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, prec.without_graph() if frozen else prec)
         c.append(x)
     c2, c3, c4, c5 = c
 
     # ---- top-down (:161-168, 178-185)
-    p5 = _conv(model.RCNN_toplayer, c5, bp=bp, fp=fp, rm=rm)
-    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
-    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
-    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, bp=bp, fp=fp, rm=rm)), bp=bp, fp=fp, rm=rm)
+    p5 = _conv(model.RCNN_toplayer, c5, prec)
+    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, prec)), prec)
+    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, prec)), prec)
+    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, prec)), prec)
     p6 = autograd.subsample2(p5)
     levels = [p2, p3, p4, p5, p6]
     shapes = [(int(p.shape[1]), int(p.shape[2])) for p in levels]
@@ -267,8 +263,8 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     deltas = torch.empty((B, n_anchors, 6), dtype=torch.float32, device=dev)
     scores, bbox_preds, off = [], [], 0
     for l, (p, (h, w)) in enumerate(zip(levels, shapes)):
-        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, True, bp=bp, fp=fp, rm=rm))                  # (2B, h, w, 512): left images, then right
-        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, backward_precision=bp, forward_precision=fp, reuse_maxima=rm)    # [cls 6 | bbox 18] per pixel
+        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, prec, True))                  # (2B, h, w, 512): left images, then right
+        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, _prec=prec)    # [cls 6 | bbox 18] per pixel
         # :89,91: NHWC rows viewed as (-1, 2) / (-1, 6) -- the raw scores pair channels (0, 1) (2, 3) (4, 5)
         scores.append(hd[..., :6].reshape(B, h * w * 3, 2))
         bbox_preds.append(hd[..., 6:].reshape(B, h * w * 3, 6))
@@ -307,24 +303,23 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     feat = _roi_feat([left_maps, right_maps], [rois_left, rois_right], im_height, cfg.POOLING_SIZE)
     top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
     w0 = top0.weight.permute(0, 2, 3, 1).reshape(int(top0.weight.shape[0]), -1)          # (2048, (kh, kw, c)): the NHWC window
-    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), w0, top0.bias, relu=True, backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
+    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), w0, top0.bias, relu=True, _prec=prec))
     t = _dropout(t, generator, tap, 'dropout1')
-    t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True,
-                                           backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
+    t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True, _prec=prec))
     t = _dropout(t, generator, tap, 'dropout2')                                           # .mean(3).mean(2) over a 1x1 map
     n_bbox, n_dim = int(model.RCNN_bbox_pred.weight.shape[0]), int(model.RCNN_dim_orien_pred.weight.shape[0])
     fc = autograd.linear(t, torch.cat((model.RCNN_bbox_pred.weight, model.RCNN_dim_orien_pred.weight, model.RCNN_cls_score.weight), 0),
-                         torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0), backward_precision=bp, forward_precision=fp, reuse_maxima=rm)
+                         torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0), _prec=prec)
     bbox_all, dim_all, cls_score = fc[:, :n_bbox], fc[:, n_bbox:n_bbox + n_dim], fc[:, n_bbox + n_dim:]
     cls_prob = F.softmax(cls_score, 1)
 
     # ---- keypoint head (:260-271)
     k = _roi_feat([left_maps], [rois_left], im_height, cfg.POOLING_SIZE * 2)
     for i in (0, 2, 4, 6, 8, 10):
-        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, True, bp=bp, fp=fp, rm=rm))
+        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, prec, True))
     up = model.RCNN_kpts[12]
-    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, backward_precision=bp, forward_precision=fp, reuse_maxima=rm))
-    kpts_pred_all = _conv(model.kpts_class, k, bp=bp, fp=fp, rm=rm).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
+    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, _prec=prec))
+    kpts_pred_all = _conv(model.kpts_class, k, prec).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
     G = cfg.KPTS_GRID
     kpts_prob = F.softmax(kpts_pred_all[:, :4, :].reshape(n, 4 * G), 1)
     left_border_prob = F.softmax(kpts_pred_all[:, 4, :], 1)

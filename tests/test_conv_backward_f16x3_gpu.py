@@ -154,7 +154,7 @@ def test_forced_split(m, dev, splits):
     assert _bits_equal(a['dw'], b['dw'])
 
 
-@pytest.mark.parametrize('tile', [(1, 1), (1, 2), (2, 2)])
+@pytest.mark.parametrize('tile', [(1, 1), (1, 2), (2, 1), (2, 2)])
 def test_tiles(m, dev, tile):
     c = _case('ragged_3x3', m, dev)
     c.check(c.run(m, want=('dx', 'dw'), tile=tile), 0, 'ragged_3x3 tile=%s' % (tile,))
