@@ -1,7 +1,9 @@
 // Shared helpers for libsrcnn_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <tuple>
 #include <type_traits>
@@ -46,6 +48,24 @@ inline int check_launch(const char *what)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// blocks of a grid-stride launch over `total` work items: enough to cover them once, at most `cap`
+inline int grid_for(size_t total, int threads, size_t cap) { return (int)std::min<size_t>((total + threads - 1) / threads, cap); }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// flat index of a (B, H, W, G) tensor -> its coordinates (G: channel groups of whatever width the caller works on)
+struct NhwcIndex { int b, h, w, g; };
+
+__device__ __forceinline__ NhwcIndex nhwc_split(size_t idx, int H, int W, int G)
+{
+    NhwcIndex p;
+    p.g = (int)(idx % G);
+    size_t r = idx / G;
+    p.w = (int)(r % W);
+    r /= W;
+    p.h = (int)(r % H);
+    p.b = (int)(r / H);
+    return p;
+}
 
 // carve 256-byte aligned chunks out of a caller-provided workspace
 struct Carver {

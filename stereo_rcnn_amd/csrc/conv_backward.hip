@@ -259,7 +259,7 @@ int srcnn_conv2d_backward(const srcnn_conv_bwd_desc *d, void *workspace, size_t 
         });
         if (pl.splits > 1) {
             const size_t total = (size_t)a.Cout * a.Kw;
-            SRCNN_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)min((size_t)2048, (total + 255) / 256)), dim3(256), 0, st, a, pl.splits);
+            SRCNN_LAUNCH(wgrad_reduce_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, st, a, pl.splits);
         }
     }
     return check_launch("srcnn_conv2d_backward");

@@ -307,7 +307,7 @@ int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsig
         });
         if (pl.splits > 1) {
             const size_t total = (size_t)a.Cout * a.Kw;
-            SRCNN_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)min((size_t)2048, (total + 255) / 256)), dim3(256), 0, st, a, pl.splits);
+            SRCNN_LAUNCH(wgrad_reduce_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, st, a, pl.splits);
         }
     }
     return check_launch("srcnn_conv2d_backward_f16x3");

@@ -88,6 +88,8 @@ struct float8 {
     float v[8];
 };
 
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+
 __device__ __forceinline__ float8 act_load8(const void *base, int fmt, size_t pixel, int cstride, int group)
 {
     const char *p = reinterpret_cast<const char *>(base) + (pixel * (size_t)cstride + (size_t)group * 8) * 4;
@@ -97,7 +99,6 @@ __device__ __forceinline__ float8 act_load8(const void *base, int fmt, size_t pi
         r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
         r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
     } else {
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
         const h8 hi = *reinterpret_cast<const h8 *>(p), lo = *reinterpret_cast<const h8 *>(p + 16);
 #pragma unroll
         for (int e = 0; e < 8; ++e) r.v[e] = (float)hi[e] + (float)lo[e];
@@ -107,42 +108,37 @@ __device__ __forceinline__ float8 act_load8(const void *base, int fmt, size_t pi
 
 // (NT: non-temporal stores -- results no wave of this launch reads again; behind a kernel boundary the next launch finds nothing in
 //  the XCDs' L2s anyway, so the lines only displace the operands this launch is still re-reading)
+// The library's one SPLIT16 group conversion (the stem pack kernels store through here too).  It stays written out in this body:
+// as a __forceinline__ helper of its own (halves by reference, or returned by value) it changed the instruction streams of
+// splitk_reduce_kernel and of the 256x256-tile conv_f16s instantiations, which must not move.
 template <bool NT = false>
 __device__ __forceinline__ void act_store8(void *base, int fmt, size_t pixel, int cstride, int group, const float8 &r)
 {
     char *p = reinterpret_cast<char *>(base) + (pixel * (size_t)cstride + (size_t)group * 8) * 4;
-    if constexpr (NT) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-        if (fmt == 0) {
+    if (fmt == 0) {
+        if constexpr (NT) {
+            typedef float f4 __attribute__((ext_vector_type(4)));
             const f4 a = {r.v[0], r.v[1], r.v[2], r.v[3]}, b = {r.v[4], r.v[5], r.v[6], r.v[7]};
             __builtin_nontemporal_store(a, reinterpret_cast<f4 *>(p));
             __builtin_nontemporal_store(b, reinterpret_cast<f4 *>(p + 16));
         } else {
-            h8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                hi[e] = (_Float16)r.v[e];
-                lo[e] = (_Float16)(r.v[e] - (float)hi[e]);
-            }
-            __builtin_nontemporal_store(hi, reinterpret_cast<h8 *>(p));
-            __builtin_nontemporal_store(lo, reinterpret_cast<h8 *>(p + 16));
+            *reinterpret_cast<float4 *>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+            *reinterpret_cast<float4 *>(p + 16) = make_float4(r.v[4], r.v[5], r.v[6], r.v[7]);
         }
-        return;
-    }
-    if (fmt == 0) {
-        *reinterpret_cast<float4 *>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-        *reinterpret_cast<float4 *>(p + 16) = make_float4(r.v[4], r.v[5], r.v[6], r.v[7]);
     } else {
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
         h8 hi, lo;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             hi[e] = (_Float16)r.v[e];
             lo[e] = (_Float16)(r.v[e] - (float)hi[e]);
         }
-        *reinterpret_cast<h8 *>(p) = hi;
-        *reinterpret_cast<h8 *>(p + 16) = lo;
+        if constexpr (NT) {
+            __builtin_nontemporal_store(hi, reinterpret_cast<h8 *>(p));
+            __builtin_nontemporal_store(lo, reinterpret_cast<h8 *>(p + 16));
+        } else {
+            *reinterpret_cast<h8 *>(p) = hi;
+            *reinterpret_cast<h8 *>(p + 16) = lo;
+        }
     }
 }
 

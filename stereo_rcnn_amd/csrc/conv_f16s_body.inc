@@ -775,6 +775,9 @@
                                 // to this lateral.  upsample_add_kernel's arithmetic (pool_resize.hip) operation by operation -- this
                                 // file is built without contraction too --, on the value the two-launch form would have stored as
                                 // float32: the sum is bit-identical to srcnn_conv2d + srcnn_upsample_add.
+                                // RESTATES bilinear_tap.h (align_ratio, align_tap, align_blend) and must follow it by hand: calling the
+                                // header here -- all three, the taps alone, or the blend alone -- moved the instruction stream of every
+                                // instantiation that holds this site (test_fused_upsample_add_in_the_lateral_conv_equals_two_launches).
                                 const int TH = p.up_TH, TW = p.up_TW;
                                 const float rh = p.OH > 1 ? (float)(TH - 1) / (float)(p.OH - 1) : 0.f;
                                 const float rw = p.OW > 1 ? (float)(TW - 1) / (float)(p.OW - 1) : 0.f;

@@ -423,8 +423,7 @@ int srcnn_conv2d(const srcnn_conv_desc *d, void *workspace, size_t workspace_byt
         });
     if (pl.splits > 1) {
         const size_t total = (size_t)a.M * a.Cout;
-        const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        SRCNN_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a, pl.splits);
+        SRCNN_LAUNCH(splitk_reduce_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, st, a, pl.splits);
     }
     if (prof) prof_end(st, 2.0 * (double)a.M * (double)a.Cout * (double)a.K);
     return check_launch("srcnn_conv2d");

@@ -16,7 +16,7 @@
 // float32 arithmetic follows the reference's operation order (the library is built with
 // -ffp-contract=off); Python-double scalars of the reference (f, bl, cx, cy, slice arithmetic
 // on torch-0.3 scalar-indexed values) are doubles here.
-#include "common.h"
+#include "bilinear_tap.h"
 #include <cstdlib>
 
 namespace srcnn {
@@ -27,7 +27,7 @@ struct DaCalib {
 };
 
 // ------------------------------------------------------------------ 2x bilinear upsample (align_corners)
-// The element's arithmetic is F.upsample's, operation by operation; the taps come from the 29 MB source through the caches.
+// The element's arithmetic is F.upsample's, operation by operation (bilinear_tap.h); the taps come from the 29 MB source through the caches.
 // Round 5's form (one float per thread, flat index decomposed with 64-bit % and /) moved its 143 MB at 1.6 TB/s.
 // A flat-index form with four floats per thread and 32-bit unsigned divisions on the vector unit was bit-exact alone and
 // NOT repeatable beside other forwards' MFMA kernels: 13-41 of 306 frames of tests/test_pipeline_gpu.py's three-in-flight soak
@@ -36,16 +36,9 @@ struct DaCalib {
 // there), whose v_rcp-based sequences misbehave under that co-residency.  Cause not established; the soak test is the gate.
 __device__ __forceinline__ float upsample2x_at(const float *__restrict__ src, int H, int W, int x, int y, int c, float rh, float rw)
 {
-    const float h1r = rh * (float)y;
-    const int h1 = (int)h1r;
-    const int h1p = h1 < H - 1 ? 1 : 0;
-    const float h1l = h1r - (float)h1, h0l = 1.f - h1l;
-    const float w1r = rw * (float)x;
-    const int w1 = (int)w1r;
-    const int w1p = w1 < W - 1 ? 1 : 0;
-    const float w1l = w1r - (float)w1, w0l = 1.f - w1l;
-    const float *p = src + ((size_t)c * H + h1) * W + w1;
-    return h0l * (w0l * p[0] + w1l * p[w1p]) + h1l * (w0l * p[(size_t)h1p * W] + w1l * p[(size_t)h1p * W + w1p]);
+    const UpTap ht = align_tap(rh, y, H), wt = align_tap(rw, x, W);
+    const float *p = src + ((size_t)c * H + ht.i1) * W + wt.i1;
+    return align_blend(ht, wt, p[0], p[wt.i1p], p[(size_t)ht.i1p * W], p[(size_t)ht.i1p * W + wt.i1p]);
 }
 
 // grid (ceil(W / 256), ceil(2H / UP_ROWS), 6): a thread owns one output column pair (one 8-byte store per row: 2W is even, every
@@ -57,6 +50,8 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float *__restrict
                                                          float *__restrict__ oa, float *__restrict__ ob)
 {
     const int H2 = 2 * H, W2 = 2 * W;
+    // bilinear_tap.h's align_ratio, restated without its n_out > 1 guard (2H > 1 always): calling it added the two selects to this
+    // kernel's instruction stream, which must not move (see above); the tap and the blend are the shared ones
     const float rh = (float)(H - 1) / (float)(H2 - 1), rw = (float)(W - 1) / (float)(W2 - 1);
     const int img = blockIdx.z / 3, c = blockIdx.z - 3 * img;
     const float *src = img ? b : a;

@@ -176,7 +176,7 @@ int srcnn_preprocess_train(const srcnn_train_image *slots_host, int B, int Hmax,
     SRCNN_REQUIRE(B > 0 && B <= SRCNN_LOADER_MAX_BATCH, "B must be 1..SRCNN_LOADER_MAX_BATCH");
     SRCNN_REQUIRE(Hmax > 0 && Wmax > 0 && max_size > 0, "Hmax, Wmax and max_size must be positive");
     SRCNN_REQUIRE(out_left && out_right, "null output pointer");
-    SRCNN_REQUIRE(((uintptr_t)out_left | (uintptr_t)out_right) % 16 == 0, "outputs must be 16-byte aligned");
+    SRCNN_REQUIRE(aligned16(out_left) && aligned16(out_right), "outputs must be 16-byte aligned");
     SRCNN_REQUIRE((unsigned long long)B * 3ull * (unsigned long long)Hmax * (unsigned long long)Wmax < (1ull << 31),
                   "a blob of 2^31 elements or more");
     TrainImageArgs a;
@@ -194,8 +194,8 @@ int srcnn_preprocess_train(const srcnn_train_image *slots_host, int B, int Hmax,
         a.slot[b] = TrainImage{s.left, s.right, 1.0 / s.scale, s.H, s.W, OH, OWc, s.flipped ? 1 : 0, 0};
     }
     const size_t groups = ((size_t)B * 3 * Hmax * Wmax + 3) / 4;
-    const int grid = (int)std::min<size_t>((groups + 255) / 256, 4096);
-    SRCNN_LAUNCH(preprocess_train_kernel, dim3(grid, 2), dim3(256), 0, as_stream(stream), a, B, Hmax, Wmax, out_left, out_right);
+    SRCNN_LAUNCH(preprocess_train_kernel, dim3(grid_for(groups, 256, 4096), 2), dim3(256), 0, as_stream(stream), a, B, Hmax, Wmax,
+                 out_left, out_right);
     return check_launch("srcnn_preprocess_train");
 }
 

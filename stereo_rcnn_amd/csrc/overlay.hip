@@ -394,10 +394,9 @@ int srcnn_bev_lidar(const float *points, int n_points, const double *velo_to_cam
     a.y_off = y_off;
     hipStream_t st = as_stream(stream);
     SRCNN_HIP_TRY(memset_async(plane, 255, (size_t)x_max * y_max, st));
-    if (n_points > 0) {
-        const int grid = std::min(cdiv(n_points, 256), 2048);
-        SRCNN_LAUNCH(bev_lidar_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float4 *>(points), n_points, a, plane);
-    }
+    if (n_points > 0)
+        SRCNN_LAUNCH(bev_lidar_kernel, dim3(grid_for(n_points, 256, 2048)), dim3(256), 0, st, reinterpret_cast<const float4 *>(points),
+                     n_points, a, plane);
     return check_launch("srcnn_bev_lidar");
 }
 

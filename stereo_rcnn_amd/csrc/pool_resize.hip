@@ -5,13 +5,29 @@
 // Reference semantics: resnet.py:113 (MaxPool2d(3,2,0,ceil_mode=True)),
 // stereo_rcnn.py:91-108 (_upsample_add; torch-0.3 bilinear == align_corners=True),
 // stereo_rcnn.py:39,168 (MaxPool2d(1, stride=2)).
-#include "conv_common.h"
+#include "bilinear_tap.h"
 #include "resize_tap.h"
 
 namespace srcnn {
 
-// NCHW (B,3,H,W) -> NHWC4 with a zero border: out (B, H+6, W+8, 4); pixel (y,x) -> (y+3, x+3).
+// plane 0 of pixel (y, x) of image b of a stem batch; planes 1 and 2 lie H * W and 2 H * W floats behind it
 // (im2: images b >= B1 come from there -- the right eyes of a stereo batch packed behind the left ones in ONE launch; B1 = B: none)
+__device__ __forceinline__ const float *stem_src(const float *im, const float *im2, int B1, int b, int H, int W, int y, int x)
+{
+    return (b < B1 ? im + (size_t)b * 3 * H * W : im2 + (size_t)(b - B1) * 3 * H * W) + (size_t)y * W + x;
+}
+
+// Group gp of a padded stem row (row: its first byte; WP pixels of 16 B): the pixel pair (2 gp, 2 gp + 1) from 8 floats, as two
+// float4 (fmt 0) or as one SPLIT16 group (fmt 1).  Odd row length: the last group holds one pixel only -- F32 stores that pixel,
+// SPLIT16 groups are whole or absent (the stride-2 stem never reads an odd last pixel).
+__device__ __forceinline__ void stem_store_group(char *row, int WP, int gp, const float8 &v, int fmt)
+{
+    char *dst = row + (size_t)gp * 32;
+    if (2 * gp + 1 < WP) act_store8(dst, fmt, 0, 0, 0, v);
+    else if (fmt == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v.v[0], v.v[1], v.v[2], v.v[3]);
+}
+
+// NCHW (B,3,H,W) -> NHWC4 with a zero border: out (B, H+6, W+8, 4); pixel (y,x) -> (y+3, x+3).
 __global__ void stem_pack_kernel(const float *__restrict__ im, const float *__restrict__ im2, int B1, int B, int H, int W,
                                  float4 *__restrict__ out)
 {
@@ -25,7 +41,7 @@ __global__ void stem_pack_kernel(const float *__restrict__ im, const float *__re
         const int y = yp - 3, x = xp - 3;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
-            const float *p = (b < B1 ? im + (size_t)b * 3 * H * W : im2 + (size_t)(b - B1) * 3 * H * W) + (size_t)y * W + x;
+            const float *p = stem_src(im, im2, B1, b, H, W, y, x);
             v.x = p[0];
             v.y = p[(size_t)H * W];
             v.z = p[(size_t)2 * H * W];
@@ -42,7 +58,6 @@ __global__ void stem_pack_kernel(const float *__restrict__ im, const float *__re
 __global__ void stem_pack_split16_kernel(const float *__restrict__ im, const float *__restrict__ im2, int B1, int B, int H, int W,
                                         char *__restrict__ out, unsigned *__restrict__ range_flag)
 {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     const int HP = H + 6, WP = W + 8, GP = WP / 2;
     const size_t total = (size_t)B * HP * GP;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -51,33 +66,23 @@ __global__ void stem_pack_split16_kernel(const float *__restrict__ im, const flo
         const int yp = (int)((idx / GP) % HP);
         const int b = (int)(idx / ((size_t)GP * HP));
         const int y = yp - 3;
-        float v[8];
+        float8 v;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        for (int e = 0; e < 8; ++e) v.v[e] = 0.f;
         if ((unsigned)y < (unsigned)H) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int x = 2 * gp + q - 3;
                 if ((unsigned)x < (unsigned)W) {
-                    const float *p = (b < B1 ? im + (size_t)b * 3 * H * W : im2 + (size_t)(b - B1) * 3 * H * W) + (size_t)y * W + x;
-                    v[4 * q + 0] = p[0];
-                    v[4 * q + 1] = p[(size_t)H * W];
-                    v[4 * q + 2] = p[(size_t)2 * H * W];
+                    const float *p = stem_src(im, im2, B1, b, H, W, y, x);
+                    v.v[4 * q + 0] = p[0];
+                    v.v[4 * q + 1] = p[(size_t)H * W];
+                    v.v[4 * q + 2] = p[(size_t)2 * H * W];
                 }
             }
         }
-        h8 hi, lo;
-        float8 chk;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            chk.v[e] = v[e];
-            hi[e] = (_Float16)v[e];
-            lo[e] = (_Float16)(v[e] - (float)hi[e]);
-        }
-        split16_guard(chk, range_flag, 9001);            // an input image beyond the f16 range: flag 9002 = input conversion
-        char *dst = out + ((size_t)b * HP + yp) * WP * 16 + (size_t)gp * 32;
-        *reinterpret_cast<h8 *>(dst) = hi;
-        *reinterpret_cast<h8 *>(dst + 16) = lo;
+        split16_guard(v, range_flag, 9001);              // an input image beyond the f16 range: flag 9002 = input conversion
+        stem_store_group(out + ((size_t)b * HP + yp) * WP * 16, WP, gp, v, 1);
     }
 }
 
@@ -89,12 +94,7 @@ __global__ void maxpool3x3s2_kernel(const float *__restrict__ x, int B, int H, i
     const size_t total = (size_t)B * OH * OW * G;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(idx % G);
-        size_t r = idx / G;
-        const int ow = (int)(r % OW);
-        r /= OW;
-        const int oh = (int)(r % OH);
-        const int b = (int)(r / OH);
+        const auto [b, oh, ow, g] = nhwc_split(idx, OH, OW, G);
         const int h0 = oh * 2, w0 = ow * 2;
         const int h1 = min(h0 + 3, H), w1 = min(w0 + 3, W);   // ceil_mode windows are clipped at the edge
         float8 m;
@@ -111,9 +111,8 @@ __global__ void maxpool3x3s2_kernel(const float *__restrict__ x, int B, int H, i
     }
 }
 
-// y = bilinear(top, align_corners=True -> (H,W)) + lateral.  Index/weight arithmetic follows
-// ATen's upsample_bilinear2d (area_pixel_compute_scale: (in-1)/(out-1); h1 = (int)h1r;
-// lambda = h1r - h1), accumulation order w0*(... ) as written there.
+// y = bilinear(top, align_corners=True -> (H,W)) + lateral.  Index/weight arithmetic and accumulation order follow ATen's
+// upsample_bilinear2d: bilinear_tap.h.
 // grid (ceil(W * C/8 / 256), B * H): one output row per blockIdx.y, so the row geometry (source rows, vertical weights) is
 // wave-uniform and the per-thread index arithmetic is one division by the group count.
 __global__ void upsample_add_kernel(const float *__restrict__ top, int TH, int TW, const float *__restrict__ lat,
@@ -121,31 +120,22 @@ __global__ void upsample_add_kernel(const float *__restrict__ top, int TH, int T
                                     unsigned *__restrict__ range_flag)
 {
     (void)B;
-    const float rh = H > 1 ? (float)(TH - 1) / (float)(H - 1) : 0.f;
-    const float rw = W > 1 ? (float)(TW - 1) / (float)(W - 1) : 0.f;
     const int G = C / 8;
     const int row = blockIdx.y;                      // b * H + h
     const int b = row / H, h = row - b * H;
-    const float h1r = rh * (float)h;
-    const int h1 = (int)h1r;
-    const int h1p = (h1 < TH - 1) ? 1 : 0;
-    const float h1l = h1r - (float)h1, h0l = 1.f - h1l;
-    const size_t trow0 = ((size_t)b * TH + h1) * TW, trow1 = trow0 + (size_t)h1p * TW;
+    const UpTap ht = align_tap(align_ratio(TH, H), h, TH);
+    const size_t trow0 = ((size_t)b * TH + ht.i1) * TW, trow1 = trow0 + (size_t)ht.i1p * TW;
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (unsigned)(W * G)) return;
     const int w = (int)(idx / (unsigned)G), g = (int)(idx - (unsigned)w * (unsigned)G);
-    const float w1r = rw * (float)w;
-    const int w1 = (int)w1r;
-    const int w1p = (w1 < TW - 1) ? 1 : 0;
-    const float w1l = w1r - (float)w1, w0l = 1.f - w1l;
-    const float8 a = act_load8(top, top_fmt, trow0 + w1, C, g), bb = act_load8(top, top_fmt, trow0 + w1 + w1p, C, g);
-    const float8 cc = act_load8(top, top_fmt, trow1 + w1, C, g), d = act_load8(top, top_fmt, trow1 + w1 + w1p, C, g);
+    const UpTap wt = align_tap(align_ratio(TW, W), w, TW);
+    const float8 a = act_load8(top, top_fmt, trow0 + wt.i1, C, g), bb = act_load8(top, top_fmt, trow0 + wt.i1 + wt.i1p, C, g);
+    const float8 cc = act_load8(top, top_fmt, trow1 + wt.i1, C, g), d = act_load8(top, top_fmt, trow1 + wt.i1 + wt.i1p, C, g);
     const size_t pix = (size_t)row * W + w;
     const float8 l = act_load8(lat, 0, pix, C, g);
-    float8 o;
+    float8 o = align_blend(ht, wt, a, bb, cc, d);
 #pragma unroll
-    for (int e = 0; e < 8; ++e)
-        o.v[e] = (h0l * (w0l * a.v[e] + w1l * bb.v[e]) + h1l * (w0l * cc.v[e] + w1l * d.v[e])) + l.v[e];
+    for (int e = 0; e < 8; ++e) o.v[e] = o.v[e] + l.v[e];
     if (yfmt == 1) split16_guard(o, range_flag, 9000);        // a sum of two in-range maps can leave the f16 range
     act_store8(y, yfmt, pix, C, g, o);
 }
@@ -175,47 +165,31 @@ __global__ void act_convert_kernel(const void *__restrict__ x, int xfmt, void *_
 __global__ void preprocess_pack_kernel(const unsigned char *__restrict__ img, int H, int W, double step, int OH, int OW,
                                        float *__restrict__ planar, char *__restrict__ packed, int packed_fmt)
 {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     const int HP = OH + 6, WP = OW + 8, GP = (WP + 1) / 2;
     const size_t total = (size_t)HP * GP, plane = (size_t)OH * OW;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (size_t)gridDim.x * blockDim.x) {
         const int gp = (int)(idx % GP), yp = (int)(idx / GP);
         const int y = yp - 3;
-        float v[8];
+        float8 v;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        for (int e = 0; e < 8; ++e) v.v[e] = 0.f;
         if ((unsigned)y < (unsigned)OH) {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int x = 2 * gp + q - 3;
                 if ((unsigned)x < (unsigned)OW) {
-                    preprocess_pixel(img, H, W, y, x, step, v + 4 * q);
+                    preprocess_pixel(img, H, W, y, x, step, v.v + 4 * q);
                     if (planar) {
                         float *o = planar + (size_t)y * OW + x;
-                        o[0] = v[4 * q + 0];
-                        o[plane] = v[4 * q + 1];
-                        o[2 * plane] = v[4 * q + 2];
+                        o[0] = v.v[4 * q + 0];
+                        o[plane] = v.v[4 * q + 1];
+                        o[2 * plane] = v.v[4 * q + 2];
                     }
                 }
             }
         }
-        if (!packed) continue;
-        char *dst = packed + (size_t)yp * WP * 16 + (size_t)gp * 32;
-        const bool second = 2 * gp + 1 < WP;            // odd row length: the last group holds one pixel only
-        if (packed_fmt == 0) {
-            *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-            if (second) *reinterpret_cast<float4 *>(dst + 16) = make_float4(v[4], v[5], v[6], v[7]);
-        } else if (second) {                            // SPLIT16 groups are whole or absent (stem_pack_split16_kernel)
-            h8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                hi[e] = (_Float16)v[e];
-                lo[e] = (_Float16)(v[e] - (float)hi[e]);
-            }
-            *reinterpret_cast<h8 *>(dst) = hi;
-            *reinterpret_cast<h8 *>(dst + 16) = lo;
-        }
+        if (packed) stem_store_group(packed + (size_t)yp * WP * 16, WP, gp, v, packed_fmt);
     }
 }
 
@@ -225,12 +199,7 @@ __global__ void subsample2_kernel(const float4 *__restrict__ x, int B, int H, in
     const size_t total = (size_t)B * OH * OW * C4;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4);
-        size_t r = idx / C4;
-        const int ow = (int)(r % OW);
-        r /= OW;
-        const int oh = (int)(r % OH);
-        const int b = (int)(r / OH);
+        const auto [b, oh, ow, c] = nhwc_split(idx, OH, OW, C4);
         y[idx] = x[(((size_t)b * H + 2 * oh) * W + 2 * ow) * C4 + c];
     }
 }
@@ -254,8 +223,6 @@ __global__ void transpose_kernel(const float *__restrict__ in, int R, int S, flo
     }
 }
 
-static inline int grid_for(size_t total, int threads) { return (int)std::min<size_t>((total + threads - 1) / threads, 16384); }
-
 }  // namespace srcnn
 
 extern "C" {
@@ -266,12 +233,12 @@ static int stem_pack_launch(const float *im, const float *im2, int B1, int B, in
     using namespace srcnn;
     if (out_format == 1) {
         const size_t groups = (size_t)B * (H + 6) * ((W + 8) / 2);
-        SRCNN_LAUNCH(stem_pack_split16_kernel, dim3(grid_for(groups, 256)), dim3(256), 0, as_stream(stream), im, im2, B1, B,
+        SRCNN_LAUNCH(stem_pack_split16_kernel, dim3(grid_for(groups, 256, 16384)), dim3(256), 0, as_stream(stream), im, im2, B1, B,
                            H, W, reinterpret_cast<char *>(out), range_flag_word());
         return check_launch(what);
     }
     const size_t total = (size_t)B * (H + 6) * (W + 8);
-    SRCNN_LAUNCH(stem_pack_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), im, im2, B1, B, H, W,
+    SRCNN_LAUNCH(stem_pack_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream), im, im2, B1, B, H, W,
                        reinterpret_cast<float4 *>(out));
     return check_launch(what);
 }
@@ -301,7 +268,7 @@ int srcnn_maxpool3x3s2_ceil(const float *x, int B, int H, int W, int C, float *y
     SRCNN_REQUIRE((OH - 1) * 2 < H && (OW - 1) * 2 < W, "output too large for input");
     SRCNN_REQUIRE((unsigned)y_format <= 1, "bad format");
     const size_t total = (size_t)B * OH * OW * (C / 8);
-    SRCNN_LAUNCH(maxpool3x3s2_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, B, H, W, C,
+    SRCNN_LAUNCH(maxpool3x3s2_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream), x, B, H, W, C,
                        y, OH, OW, y_format, range_flag_word());
     return check_launch("srcnn_maxpool3x3s2_ceil");
 }
@@ -326,7 +293,7 @@ int srcnn_act_convert(const void *x, int x_format, void *y, int y_format, long l
     SRCNN_REQUIRE((unsigned)x_format <= 1 && (unsigned)y_format <= 1, "bad format");
     if (pixels == 0) return SRCNN_OK;
     const size_t total = (size_t)pixels * (C / 8);
-    SRCNN_LAUNCH(act_convert_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), x, x_format, y,
+    SRCNN_LAUNCH(act_convert_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream), x, x_format, y,
                        y_format, (size_t)pixels, C, range_flag_word());
     return check_launch("srcnn_act_convert");
 }
@@ -341,7 +308,7 @@ int srcnn_preprocess(const unsigned char *img_rgb, int H, int W, double scale, f
     SRCNN_REQUIRE(OH == (int)nearbyint((double)H * scale) && OW == (int)nearbyint((double)W * scale),
                   "OH/OW must be cvRound(H*scale), cvRound(W*scale)");
     const size_t total = (size_t)(OH + 6) * ((OW + 8 + 1) / 2);
-    SRCNN_LAUNCH(preprocess_pack_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream), img_rgb, H, W,
+    SRCNN_LAUNCH(preprocess_pack_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream), img_rgb, H, W,
                        1.0 / scale, OH, OW, out_nchw, reinterpret_cast<char *>(packed), packed_format);
     return check_launch("srcnn_preprocess");
 }
@@ -352,7 +319,7 @@ int srcnn_subsample2(const float *x, int B, int H, int W, int C, float *y, int O
     SRCNN_REQUIRE(C % 4 == 0, "C must be a multiple of 4");
     SRCNN_REQUIRE((OH - 1) * 2 < H && (OW - 1) * 2 < W, "output too large for input");
     const size_t total = (size_t)B * OH * OW * (C / 4);
-    SRCNN_LAUNCH(subsample2_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream),
+    SRCNN_LAUNCH(subsample2_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const float4 *>(x), B, H, W, C / 4, reinterpret_cast<float4 *>(y), OH, OW);
     return check_launch("srcnn_subsample2");
 }

@@ -8,6 +8,7 @@
 // fraction at the borders, vertical taps clip the two rows but keep the fraction; HResizeLinear S[sx]*a0 + S[sx+1]*a1,
 // VResizeLinear S0*b0 + S1*b1, each product and sum rounded to float32 on its own.  Mean subtraction happens BEFORE the
 // resize and in double, as numpy does for float32 -= float64.
+// (bilinear_tap.h is another rule -- torch's align_corners=True: corner-aligned ratio, no half-pixel offset -- and stays apart.)
 #pragma once
 #include <hip/hip_runtime.h>
 

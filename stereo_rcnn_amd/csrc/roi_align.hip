@@ -230,8 +230,8 @@ int srcnn_pool2x2_s1(const float *x, long long planes, int h, int w, float *y, i
     SRCNN_REQUIRE(x && y && planes >= 0 && h >= 2 && w >= 2, "bad args (the lattice must be at least 2 x 2)");
     const size_t total = (size_t)planes * (h - 1) * (w - 1);
     if (total == 0) return SRCNN_OK;
-    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
-    SRCNN_LAUNCH(pool2x2_s1_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), x, (size_t)planes, h, w, y, take_max);
+    SRCNN_LAUNCH(pool2x2_s1_kernel, dim3(grid_for(total, 256, 65535)), dim3(256), 0, as_stream(stream), x, (size_t)planes, h, w, y,
+                 take_max);
     return check_launch("srcnn_pool2x2_s1");
 }
 

@@ -3,27 +3,9 @@
 // All are one-pass HBM-bound NHWC float32 kernels on 8-channel groups (float4 loads and stores, coalesced over C), without
 // atomics: every output element is owned by one thread and stored once, so no output needs a zero fill and every result is
 // run-to-run bit-equal.  include/srcnn_hip.h ("training: remaining adjoints") states the sums and their order.
-#include "conv_common.h"
+#include "bilinear_tap.h"
 
 namespace srcnn {
-
-// The forward's source index and weights of output index o (upsample_add_kernel, operation by operation):
-// i1 = (int)(r * o), i1p = [i1 < n_top - 1], l1 = r * o - i1, l0 = 1 - l1.
-struct UpTap {
-    int i1, i1p;
-    float l0, l1;
-};
-
-__device__ __forceinline__ UpTap up_tap(float r, int o, int n_top)
-{
-    UpTap t;
-    const float f = r * (float)o;
-    t.i1 = (int)f;
-    t.i1p = (t.i1 < n_top - 1) ? 1 : 0;
-    t.l1 = f - (float)t.i1;
-    t.l0 = 1.f - t.l1;
-    return t;
-}
 
 // Output indices that can read top index t: those with i1 in {t - 1, t}, i.e. r * o in [t - 1, t + 1); one index of slack on
 // each side, the caller recomputes every candidate's taps the forward's way.  r == 0: every output index reads top index 0.
@@ -44,8 +26,7 @@ __device__ __forceinline__ void up_candidates(float r, int t, int n_out, int &lo
 __global__ void upsample_add_backward_kernel(const float *__restrict__ dy, int H, int W, int C, float *__restrict__ d_top,
                                              int TH, int TW)
 {
-    const float rh = H > 1 ? (float)(TH - 1) / (float)(H - 1) : 0.f;
-    const float rw = W > 1 ? (float)(TW - 1) / (float)(W - 1) : 0.f;
+    const float rh = align_ratio(TH, H), rw = align_ratio(TW, W);
     const int G = C / 8;
     const int row = blockIdx.y;                      // b * TH + th
     const int b = row / TH, th = row - b * TH;
@@ -59,16 +40,16 @@ __global__ void upsample_add_backward_kernel(const float *__restrict__ dy, int H
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc.v[e] = 0.f;
     for (int h = hlo; h <= hhi; ++h) {
-        const UpTap ht = up_tap(rh, h, TH);
-        // the forward's two row taps (h1 with h0l, h1 + h1p with h1l); at the last top row both are the same row
+        const UpTap ht = align_tap(rh, h, TH);
+        // the forward's two row taps (ht.i1 with ht.l0, ht.i1 + ht.i1p with ht.l1); at the last top row both are the same row
         const bool r0 = ht.i1 == th, r1 = ht.i1 + ht.i1p == th;
         if (!r0 && !r1) continue;
         for (int w = wlo; w <= whi; ++w) {
-            const UpTap wt = up_tap(rw, w, TW);
+            const UpTap wt = align_tap(rw, w, TW);
             const bool c0 = wt.i1 == tw, c1 = wt.i1 + wt.i1p == tw;
             if (!c0 && !c1) continue;
             const float8 v = act_load8(dy, 0, ((size_t)b * H + h) * W + w, C, g);
-            // the forward's tap order: (h0l, w0l) (h0l, w1l) (h1l, w0l) (h1l, w1l); each coefficient rounded once
+            // align_blend's tap order, (row, column) weights: (l0, l0) (l0, l1) (l1, l0) (l1, l1); each coefficient rounded once
             const float hl[2] = {ht.l0, ht.l1}, wl[2] = {wt.l0, wt.l1};
             const bool rr[2] = {r0, r1}, cc[2] = {c0, c1};
 #pragma unroll
@@ -92,12 +73,7 @@ __global__ void subsample2_backward_kernel(const float4 *__restrict__ dy, int B,
     const size_t total = (size_t)B * H * W * C4;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4);
-        size_t r = idx / C4;
-        const int w = (int)(r % W);
-        r /= W;
-        const int h = (int)(r % H);
-        const int b = (int)(r / H);
+        const auto [b, h, w, c] = nhwc_split(idx, H, W, C4);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (((h | w) & 1) == 0) v = dy[(((size_t)b * OH + (h >> 1)) * OW + (w >> 1)) * C4 + c];
         dx[idx] = v;
@@ -112,20 +88,12 @@ __global__ void pixel_shuffle2_kernel(const float4 *__restrict__ x, int M, int h
     const size_t total = (size_t)M * H2 * W2 * C4;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % C4);
-        size_t r = idx / C4;
-        const int X = (int)(r % W2);
-        r /= W2;
-        const int Y = (int)(r % H2);
-        const int m = (int)(r / H2);
+        const auto [m, Y, X, c] = nhwc_split(idx, H2, W2, C4);
         const size_t packed = ((((size_t)m * h + (Y >> 1)) * w + (X >> 1)) * 4 + (size_t)((Y & 1) * 2 + (X & 1))) * C4 + c;
         if (inverse) y[packed] = x[idx];
         else y[idx] = x[packed];
     }
 }
-
-static inline int train_grid_for(size_t total, int threads) { return (int)std::min<size_t>((total + threads - 1) / threads, 16384); }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace srcnn
 
@@ -157,7 +125,7 @@ int srcnn_subsample2_backward(const float *dy, int B, int OH, int OW, int C, flo
     SRCNN_REQUIRE(C % 8 == 0, "bad channel stride: C must be a multiple of 8");
     SRCNN_REQUIRE(aligned16(dy) && aligned16(dx), "dy and dx must be 16-byte aligned");
     const size_t total = (size_t)B * H * W * (C / 4);
-    SRCNN_LAUNCH(subsample2_backward_kernel, dim3(train_grid_for(total, 256)), dim3(256), 0, as_stream(stream),
+    SRCNN_LAUNCH(subsample2_backward_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream),
                  reinterpret_cast<const float4 *>(dy), B, OH, OW, C / 4, reinterpret_cast<float4 *>(dx), H, W);
     return check_launch("srcnn_subsample2_backward");
 }
@@ -173,7 +141,7 @@ int srcnn_pixel_shuffle2(const float *x, int M, int h, int w, int Cq, float *y, 
     SRCNN_REQUIRE(aligned16(x) && aligned16(y), "x and y must be 16-byte aligned");
     SRCNN_REQUIRE((long long)h < (1 << 20) && (long long)w < (1 << 20), "bad shape: map too large");
     const size_t total = (size_t)M * h * w * Cq;      // float4s of either tensor: M * 2h * 2w * Cq / 4
-    SRCNN_LAUNCH(pixel_shuffle2_kernel, dim3(train_grid_for(total, 256)), dim3(256), 0, as_stream(stream),
+    SRCNN_LAUNCH(pixel_shuffle2_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, as_stream(stream),
                  reinterpret_cast<const float4 *>(x), M, h, w, Cq / 4, reinterpret_cast<float4 *>(y), inverse);
     return check_launch("srcnn_pixel_shuffle2");
 }

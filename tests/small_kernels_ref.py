@@ -146,6 +146,25 @@ def upsample_add(top, lateral):
     return y, mag
 
 
+def upsample_add_f32(top, lateral):
+    """float32 restatement of the shared tap and blend (csrc/bilinear_tap.h: align_ratio, align_tap, align_blend) followed by
+    the lateral, operation by operation: (l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d)) + lateral with every product
+    and sum rounded to float32 on its own (numpy's float32 arithmetic; the library is built with -ffp-contract=off).
+    top (B, TH, TW, C), lateral (B, H, W, C) float32 -> float32 (B, H, W, C)."""
+    top, lat = np.asarray(top, np.float32), np.asarray(lateral, np.float32)
+    H, W = lat.shape[1:3]
+    f = lambda a: a.astype(np.float32)               # exact: _taps computed them in float32
+    h0, h1, a0, a1 = _taps(top.shape[1], H)
+    w0, w1, b0, b1 = _taps(top.shape[2], W)
+    a0, a1 = f(a0)[None, :, None, None], f(a1)[None, :, None, None]
+    b0, b1 = f(b0)[None, None, :, None], f(b1)[None, None, :, None]
+    t00, t01 = top[:, h0][:, :, w0], top[:, h0][:, :, w1]
+    t10, t11 = top[:, h1][:, :, w0], top[:, h1][:, :, w1]
+    y = (a0 * (b0 * t00 + b1 * t01) + a1 * (b0 * t10 + b1 * t11)) + lat
+    assert y.dtype == np.float32
+    return y
+
+
 def upsample_add_bound(mag):
     """|float32 kernel - upsample_add| <= 6 * 2^-24 * (sum |w v| + |lateral|): the weights are the same float32 numbers on
     both sides; a tap's value passes through at most five float32 roundings on its way to the result (w product, inner sum,

@@ -486,6 +486,35 @@ def test_upsample_add_vs_float64(dev, TH, TW, H, W):
                     assert np.array_equal(_bits(y[:-1]), _bits(R.split16_pack(exact) if yf else exact))
 
 
+@pytest.mark.parametrize("TH,TW,H,W", [(1, 1, 3, 5), (1, 4, 2, 7), (3, 1, 5, 1), (3, 4, 3, 4), (3, 4, 5, 7), (7, 5, 19, 11), (2, 2, 1, 1)])
+def test_upsample_add_equals_the_float32_restatement(dev, TH, TW, H, W):
+    """Bit for bit (the library is built with -ffp-contract=off) against small_kernels_ref.upsample_add_f32, the restatement of
+    csrc/bilinear_tap.h, in all four format pairs: a SPLIT16 top enters as float32(hi) + float32(lo), a SPLIT16 result is the
+    split of the restated float32.  The shapes reach every branch of the tap: a one-pixel source (r = 0), a one-pixel output, the
+    clamped last row and column (i1p = 0), the identity size."""
+    _lib, L = _L()
+    for B in (1, 3):
+        for C in (8, 24):
+            rng = np.random.default_rng(TH * 1000 + H * 10 + B + C)
+            top = (rng.normal(0, 30, (B, TH, TW, C))).astype(np.float32)
+            lat = (rng.normal(0, 30, (B, H, W, C))).astype(np.float32)
+            top_raw = R.split16_pack(top)
+            top_q = R.split16_unpack(top_raw)
+            ld = _d(lat, dev)
+            for tf, yf in ((0, 0), (1, 1), (0, 1), (1, 0)):
+                want = R.upsample_add_f32(top_q if tf else top, lat).reshape(-1, C)
+                y = _canary((B * H * W + 1, C), dev)
+                _lib.check(L.srcnn_upsample_add(_d(top_raw if tf else top, dev).data_ptr(), TH, TW, ld.data_ptr(), B, H, W, C, y.data_ptr(),
+                                                tf, yf, _lib.stream()))
+                y = y.cpu().numpy()
+                assert (y[-1] == CANARY).all()
+                expect = R.split16_pack(want) if yf else want
+                differ = int((_bits(y[:-1]) != _bits(expect)).sum())
+                print("upsample_add %s B=%d C=%d fmt %d->%d: %d of %d words differ from the float32 restatement"
+                      % ((TH, TW, H, W), B, C, tf, yf, differ, expect.size))
+                assert differ == 0, (B, C, tf, yf)
+
+
 # ================================================================================================ 7. subsample, transposes
 @pytest.mark.parametrize("H,W", [(1, 1), (2, 2), (3, 5), (4, 6)])
 def test_subsample2_bit_exact(dev, H, W):

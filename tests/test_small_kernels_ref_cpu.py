@@ -129,6 +129,23 @@ def test_upsample_add_is_interpolate_align_corners_in_float64(TH, TW, H, W):
     assert (np.abs(y32.numpy().astype(np.float64) - got) <= R.upsample_add_bound(mag)).all()
 
 
+@pytest.mark.parametrize("TH,TW,H,W", [(1, 1, 3, 5), (1, 4, 2, 7), (3, 1, 5, 1), (3, 4, 3, 4), (3, 4, 5, 7), (7, 5, 19, 11), (2, 2, 1, 1)])
+def test_upsample_add_f32_restatement_lies_within_the_bound_of_float64(TH, TW, H, W):
+    """The float32 restatement the GPU test compares bits with is itself tied to the float64 reference: inside upsample_add_bound
+    on the GPU test's shapes; the identity size is top + lateral exactly."""
+    for B in (1, 3):
+        for C in (8, 24):
+            rng = np.random.default_rng(TH * 1000 + H * 10 + B + C)
+            top = rng.normal(0, 30, (B, TH, TW, C)).astype(np.float32)
+            lat = rng.normal(0, 30, (B, H, W, C)).astype(np.float32)
+            y32 = R.upsample_add_f32(top, lat)
+            ref, mag = R.upsample_add(top, lat)
+            assert y32.dtype == np.float32 and y32.shape == ref.shape
+            assert (np.abs(y32.astype(np.float64) - ref) <= R.upsample_add_bound(mag)).all()
+            if (TH, TW) == (H, W):
+                assert np.array_equal(y32, top + lat)
+
+
 def test_subsample_and_transposes_are_slicing_and_permute():
     x = torch.arange(2 * 5 * 7 * 4, dtype=torch.float32).view(2, 5, 7, 4)
     want = F.max_pool2d(x.permute(0, 3, 1, 2), 1, 2).permute(0, 2, 3, 1)

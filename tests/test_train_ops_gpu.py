@@ -73,6 +73,24 @@ def test_upsample_add_backward(ag, dev, top_hw, out_hw, C):
     assert torch.equal(t.grad, got) and torch.equal(l.grad.cpu(), dy)
 
 
+@pytest.mark.parametrize('top_hw,out_hw', [((1, 1), (3, 5)), ((3, 4), (5, 7)), ((2, 2), (2, 2))])
+def test_upsample_add_backward_equals_the_float32_restatement(dev, top_hw, out_hw):
+    """Bit for bit against train_ops_ref.upsample_add_backward_f32: the forward restatement's taps and weights, accumulated in
+    the kernel's defined summation order with an exact fmaf.  A one-pixel top (r = 0: every output pixel lands on it), clamped
+    last rows and columns where both taps are the same top pixel, and the identity size."""
+    import numpy as np
+    (TH, TW), (H, W), B, C = top_hw, out_hw, 2, 8
+    gen = torch.Generator().manual_seed(400 + TH * TW + H)
+    dy = torch.randn(B, H, W, C, generator=gen)
+    got = _up_backward(dy.to(dev), TH, TW).cpu().numpy()
+    want = T.upsample_add_backward_f32(dy.numpy(), TH, TW)
+    differ = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+    print("upsample_add_backward %s -> %s: %d of %d words differ from the float32 restatement" % (top_hw, out_hw, differ, want.size))
+    assert differ == 0
+    if top_hw == out_hw:
+        assert np.array_equal(got, dy.numpy())
+
+
 @pytest.mark.parametrize('B,H,W,C', [(2, 7, 21, 256), (1, 4, 11, 8), (3, 1, 1, 8), (2, 6, 5, 40)])
 def test_subsample2_backward(ag, dev, B, H, W, C):
     gen = torch.Generator().manual_seed(200 + H)

@@ -34,6 +34,58 @@ def test_upsample_backward_against_interpolate(top_hw, out_hw):
     assert abs(lhs - rhs) <= 1e-12 * float((fwd.abs() * dy.double().abs()).sum())
 
 
+def _round_f32(fr):
+    """Correctly rounded (nearest, ties to even) float32 of an exact Fraction of normal magnitude."""
+    from fractions import Fraction
+    if fr == 0:
+        return 0.0
+    sign, fr = (-1 if fr < 0 else 1), abs(fr)
+    e = fr.numerator.bit_length() - fr.denominator.bit_length()
+    if Fraction(2) ** e > fr:
+        e -= 1
+    q = fr / Fraction(2) ** (e - 23)
+    n = q.numerator // q.denominator
+    rem = q - n
+    if rem > Fraction(1, 2) or (rem == Fraction(1, 2) and n & 1):
+        n += 1
+    return sign * float(n) * 2.0 ** (e - 23)
+
+
+def test_fmaf32_rounds_once():
+    """train_ops_ref.fmaf32 against exact rational arithmetic: random operands, and sums that land exactly between two float32
+    values once the product's low bits are dropped (where rounding the float64 sum a second time goes wrong)."""
+    import numpy as np
+    from fractions import Fraction
+    rng = np.random.default_rng(5)
+    k = rng.random(2000).astype(np.float32)
+    v = rng.normal(0, 1, 2000).astype(np.float32)
+    acc = (rng.normal(0, 1, 2000) * 10.0 ** rng.integers(-3, 4, 2000)).astype(np.float32)
+    # k v = 2^-14 (1 - 2^-46): 2^-60 short of half a float32 ulp of acc = 2^10 (1 + 2^-23), whose last bit is odd.  The float64
+    # sum drops the 2^-60 and lands on the tie, which a second rounding would resolve upwards (to even); once rounded, acc stays.
+    # Mirrored in sign, and the true tie (k v = 2^-14) for contrast.
+    e = np.float32(1.0 + 2.0 ** -23)
+    k = np.concatenate([k, np.float32([2.0 ** -14, 2.0 ** -14, 2.0 ** -14]) * np.float32([e, -e, 1.0])])
+    v = np.concatenate([v, np.float32([1.0 - 2.0 ** -23, 1.0 - 2.0 ** -23, 1.0])])
+    acc = np.concatenate([acc, np.float32([2.0 ** 10, -2.0 ** 10, 2.0 ** 10]) * e])
+    got = T.fmaf32(k, v, acc)
+    assert float(got[-3]) == float(acc[-3]) and float(got[-2]) == float(acc[-2]) and float(got[-1]) > float(acc[-1])
+    assert got.dtype == np.float32
+    for i in range(len(k)):
+        want = _round_f32(Fraction(float(k[i])) * Fraction(float(v[i])) + Fraction(float(acc[i])))
+        assert float(got[i]) == want, (i, float(k[i]), float(v[i]), float(acc[i]), float(got[i]), want)
+
+
+@pytest.mark.parametrize('top_hw,out_hw', [((1, 1), (3, 5)), ((3, 4), (5, 7)), ((2, 2), (2, 2))])
+def test_upsample_backward_f32_restatement_lies_within_the_bound_of_float64(top_hw, out_hw):
+    """The float32 restatement the GPU test compares bits with, against the float64 one: (n + 2) u S as in the GPU test."""
+    (TH, TW), (H, W) = top_hw, out_hw
+    dy = torch.randn(2, H, W, 8, generator=torch.Generator().manual_seed(11))
+    g32 = torch.from_numpy(T.upsample_add_backward_f32(dy.numpy(), TH, TW))
+    g, S = T.upsample_add_backward(dy, TH, TW)
+    n = 4 * H * W
+    assert bool(((g32.double() - g).abs() <= (n + 2) * T.U * S + 1e-300).all())
+
+
 def test_upsample_taps_are_in_range():
     for n_top, n_out in ((4, 7), (7, 13), (13, 26), (1, 3), (5, 5), (38, 75), (2, 1000)):
         i1, i2, l0, l1 = T.up_taps(n_out, n_top)

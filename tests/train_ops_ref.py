@@ -75,6 +75,46 @@ def upsample_add_backward(dy, TH, TW):
     return g, S
 
 
+def fmaf32(k, v, acc):
+    """round_float32(k * v + acc) with ONE rounding, for float32 arrays: the product of two float32 is exact in float64; the sum
+    is taken in float64 with its rounding error (TwoSum) and, where inexact, moved to the neighbour with an odd last bit
+    (round to odd), after which the rounding to float32 is the correct single one (53 >= 2 * 24 + 2 bits)."""
+    p = np.asarray(k, np.float32).astype(np.float64) * np.asarray(v, np.float32).astype(np.float64)
+    a = np.asarray(acc, np.float32).astype(np.float64)
+    s = p + a
+    t = s - p
+    err = (p - (s - t)) + (a - t)
+    even = (np.ascontiguousarray(s).view(np.int64) & 1) == 0
+    s = np.where((err != 0) & even, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def upsample_add_backward_f32(dy, TH, TW):
+    """float32 restatement of srcnn_upsample_add_backward in its DEFINED SUMMATION ORDER (include/srcnn_hip.h): per top pixel,
+    ascending h, inside a row ascending w, inside an output pixel the taps (l0h, l0w) (l0h, l1w) (l1h, l0w) (l1h, l1w); one
+    chain acc = fmaf(k, dy, acc) from 0 with k = lh * lw rounded to float32 once.  The taps and weights are those of
+    small_kernels_ref.upsample_add_f32 (the forward's restatement).  dy (B, H, W, C) float32 numpy -> (B, TH, TW, C) float32."""
+    from small_kernels_ref import _taps
+    dy = np.asarray(dy, np.float32)
+    B, H, W, C = dy.shape
+    f = lambda a: a.astype(np.float32)
+    h0, h1, a0, a1 = _taps(TH, H)
+    w0, w1, b0, b1 = _taps(TW, W)
+    rows, cols = ((h0, f(a0)), (h1, f(a1))), ((w0, f(b0)), (w1, f(b1)))
+    out = np.zeros((B, TH, TW, C), np.float32)
+    for th in range(TH):
+        for tw in range(TW):
+            acc = np.zeros((B, C), np.float32)
+            for h in range(H):
+                for w in range(W):
+                    for ih, lh in rows:
+                        for iw, lw in cols:
+                            if ih[h] == th and iw[w] == tw:
+                                acc = fmaf32(lh[h] * lw[w], dy[:, h, w, :], acc)
+            out[:, th, tw, :] = acc
+    return out
+
+
 def subsample2(x):
     return x[:, ::2, ::2, :]
 
