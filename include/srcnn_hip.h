@@ -551,6 +551,7 @@ SRCNN_API int srcnn_rpn_score_parts(const float *const *parts, const int *nparts
  * decode+clip (bbox_transform.py:79-104,177-185), stable descending sort / top pre_nms,
  * NMS(left) & NMS(right), sorted intersection, first post_nms, zero pad, batch index in col 0.
  * probs (B, A, 2), deltas (B, A, 6); level_hw_host: nlevels x {H, W}; rois_* (B, post_nms, 5).
+ * The scores probs[..., 1] must be finite and non-negative (softmax outputs; no -0.0f, no NaN): the selection orders them by bits.
  * LIMITS: specialised to the reference's anchor configuration (config.py: FPN_ANCHOR_SCALES {32,64,128,256,512} one per
  * level, FPN_FEAT_STRIDES {4,8,16,32,64}, ANCHOR_RATIOS {0.5,1,2}, i.e. nlevels == 5 and 3 anchors per location:
  * num_anchors must equal 3 * sum(H_l * W_l) and stay below 4M); pre_nms <= 8192 (radix top-K buffer), post_nms <= pre_nms.  Anything else

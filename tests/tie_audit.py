@@ -120,20 +120,10 @@ def hip_run_from_workspace(plan, rois_left, rois_right, b=0):
     (include/srcnn_hip.h: srcnn_proposal_workspace_layout) -- the kernels' own candidate order, decoded boxes and keep lists, not a
     re-computation.  Call on the stream the forward ran on, after synchronising.  rois_left / rois_right: the forward's own outputs
     (an eager forward hands its result buffers over and the plan allocates fresh ones)."""
-    import ctypes
-    from stereo_rcnn_amd import _lib
+    import proposal_ref
     from stereo_rcnn_amd.model.utils.config import cfg
-    L = _lib.lib()
-    B, A, pre, post = plan.B, plan.A, cfg.TEST.RPN_PRE_NMS_TOP_N, plan.post
-    n = pre if 0 < pre < A else A
-    off = (ctypes.c_size_t * 5)()
-    _lib.check(L.srcnn_proposal_workspace_layout(B, A, pre, off, 5), 'srcnn_proposal_workspace_layout')
-    ws = _lib.workspace(L.srcnn_proposal_workspace_bytes(B, A, pre, post), plan.dev, 'proposal')
-    raw = ws.cpu().numpy()
-    order = raw[off[0]:off[0] + B * n * 4].view(np.int32).reshape(B, n)[b].astype(np.int64)
-    dets = raw[off[1]:off[1] + B * 2 * n * 5 * 4].view(np.float32).reshape(B, 2, n, 5)[b]
-    keep = raw[off[2]:off[2] + B * 2 * n * 4].view(np.int32).reshape(B, 2, n)[b]
-    num = raw[off[3]:off[3] + B * 2 * 4].view(np.int32).reshape(B, 2)[b]
+    post = plan.post
+    order, dets, keep, num = [a[b] for a in proposal_ref.read_workspace(plan.B, plan.A, cfg.TEST.RPN_PRE_NMS_TOP_N, post, plan.dev)]
     kl, kr = keep[0, :num[0]].astype(np.int64), keep[1, :num[1]].astype(np.int64)
     return {'order': order, 'dets_left': dets[0].copy(), 'dets_right': dets[1].copy(), 'keep_left': kl, 'keep_right': kr,
             'keep': np.intersect1d(kl, kr)[:post], 'fg': plan.probs[b, :, 1].cpu().numpy().astype(np.float32),
