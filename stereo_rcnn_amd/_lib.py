@@ -4,279 +4,165 @@ The reference binds its native ops with cffi (`torch.utils.ffi`,
 lib/model/nms/_ext/nms/__init__.py:2-15); cffi is not in this image, ctypes gives the
 same contract.  There is NO fallback: if the HIP library is missing or fails to load,
 importing any operator raises (the product path never routes through the CPU oracle).
+
+Nothing of the header is written a second time here: at import `parse_header` reads include/srcnn_hip.h and gives this module
+  * every `#define SRCNN_<NAME> <integer>` as the attribute <NAME> (FMT_F32, REC_COLS, ERR_ARG, KITTI_MAX_DET, ...),
+  * one ctypes.Structure per `typedef struct` (srcnn_conv_fwd_f16x3_desc -> ConvFwdF16x3Desc), pointer fields c_void_p,
+  * `_SIGNATURES` = {name: (restype, [argtypes])} over every SRCNN_API declaration.
+Type rule: scalars by C type; a pointer to a declared struct is POINTER(Struct); srcnn_stream_t and every other pointer is
+c_void_p (device memory: callers pass data_ptr()); a non-struct pointer that the HOST reads or writes is POINTER(pointee) --
+the arguments the header names *_host, and those `_HOST_ARRAYS` lists.  What the parser does not understand raises with its text.
 """
+import collections
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRCNN_LIB_PATH") or os.path.join(_HERE, "libsrcnn_hip.so")   # override: A/B builds of the library (dev)
-
-FMT_F32, FMT_SPLIT16 = 0, 1     # SRCNN_FMT_* (include/srcnn_hip.h)
-REC_COLS = 32                   # SRCNN_REC_COLS: detection record row (include/srcnn_hip.h lists the columns)
-LOSS_ROWS_PER_WG = 1024         # SRCNN_LOSS_ROWS_PER_WG: rows of one stage-1 workgroup of the loss kernels (one workspace partial each)
-CE_MAX_COLS = 256               # SRCNN_CE_MAX_COLS
-CE_MEAN_KEPT, CE_WEIGHTED = 0, 1    # SRCNN_CE_*
-TARGETS_MAX_GT = 64             # SRCNN_TARGETS_MAX_GT
-TARGETS_MAX_ROIS = 4096         # SRCNN_TARGETS_MAX_ROIS: proposals + ground-truth boxes of one image
-TARGETS_MAX_BATCH_ROIS = 1024   # SRCNN_TARGETS_MAX_BATCH_ROIS: rois_per_image
-OPT_CHUNK = 4096                # SRCNN_OPT_CHUNK: elements of one chunk of the optimiser kernels (one norm partial each)
-OPT_TENSORS_PER_LAUNCH = 64     # SRCNN_OPT_TENSORS_PER_LAUNCH: tensors one launch of the optimiser kernels carries in its arguments
-LOADER_MAX_BATCH = 16           # SRCNN_LOADER_MAX_BATCH: batch slots one launch of the batch assembly kernels carries in its arguments
-GT_COLS = 24                    # SRCNN_GT_COLS: floats of one object row of the ground-truth table (include/srcnn_hip.h lists the columns)
-GT_MAX_ROWS = 512               # SRCNN_GT_MAX_ROWS: objects of one roidb entry srcnn_gt_batch ranks
-PREP_LAYERS_PER_LAUNCH = 16     # SRCNN_PREP_LAYERS_PER_LAUNCH: layers one launch of the weight preparation kernels carries in its arguments
-PREP_CONV, PREP_SHORTCUT, PREP_STEM, PREP_DECONV2X2 = 0, 1, 2, 3     # SRCNN_PREP_*: the forms of srcnn_prep_weights
-OVERLAY_SLOTS_PER_ROW = 26      # SRCNN_OVERLAY_SLOTS_PER_ROW: segments srcnn_render_overlay keeps per record row (8 + 12 + 6)
-OVERLAY_BOXES, OVERLAY_WIREFRAMES, OVERLAY_BEV_BOXES = 1, 2, 4      # SRCNN_OVERLAY_*: the layers of srcnn_render_overlay
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "srcnn_hip.h")            # where csrc/build.py takes it from
 
 c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_void_p, ctypes.c_size_t)
 
-
-class ConvDesc(ctypes.Structure):
-    """struct srcnn_conv_desc (include/srcnn_hip.h)."""
-    _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("residual", c_void_p), ("y", c_void_p),
-                ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_cstride", c_int),
-                ("OH", c_int), ("OW", c_int), ("Cout", c_int),
-                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
-                ("y_cstride", c_int), ("y_coffset", c_int), ("res_cstride", c_int),
-                ("relu", c_int), ("mode", c_int),
-                ("precision", c_int), ("w_lo", c_void_p), ("w_inv_scale", c_float),
-                ("tile_mr", c_int), ("tile_nr", c_int), ("splits", c_int),
-                ("x_format", c_int), ("y_format", c_int), ("res_format", c_int),
-                ("tile_waves", c_int), ("tile_stages", c_int), ("layer_tag", c_int),
-                ("m_limit", c_void_p), ("m_limit_mul", c_int),
-                ("x2", c_void_p), ("Cin2", c_int), ("H2", c_int), ("W2", c_int), ("x2_cstride", c_int), ("stride2", c_int),
-                ("head_w", c_void_p), ("head_bias", c_void_p), ("head_y", c_void_p), ("head_cout", c_int), ("head_scale", c_float),
-                ("head_wf", c_void_p), ("head_rows", c_int), ("head_parts", c_int), ("head_plane", ctypes.c_longlong),
-                ("up_top", c_void_p), ("up_format", c_int), ("up_H", c_int), ("up_W", c_int)]
-
-
-class ConvBwdDesc(ctypes.Structure):
-    """struct srcnn_conv_bwd_desc (include/srcnn_hip.h)."""
-    _fields_ = [("x", c_void_p), ("w", c_void_p), ("y", c_void_p), ("dy", c_void_p),
-                ("dx", c_void_p), ("dw", c_void_p), ("db", c_void_p), ("g_out", c_void_p),
-                ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_cstride", c_int),
-                ("OH", c_int), ("OW", c_int), ("Cout", c_int),
-                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
-                ("y_cstride", c_int), ("y_coffset", c_int), ("relu", c_int),
-                ("mode", c_int), ("precision", c_int), ("x_format", c_int), ("y_format", c_int),
-                ("tile_mr", c_int), ("tile_nr", c_int), ("splits", c_int),
-                ("head_w", c_void_p), ("head_wf", c_void_p), ("x2", c_void_p), ("up_top", c_void_p)]
-
-
-class ConvFwdF16x3Desc(ctypes.Structure):
-    """struct srcnn_conv_fwd_f16x3_desc (include/srcnn_hip.h)."""
-    _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("residual", c_void_p), ("y", c_void_p),
-                ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_cstride", c_int),
-                ("OH", c_int), ("OW", c_int), ("Cout", c_int),
-                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad", c_int),
-                ("y_cstride", c_int), ("y_coffset", c_int), ("relu", c_int),
-                ("x_format", c_int), ("y_format", c_int),
-                ("tile_mr", c_int), ("tile_nr", c_int)]
-
-
-class KittiSplit(ctypes.Structure):
-    """struct srcnn_kitti_split (include/srcnn_hip.h): a ragged batch of frames, device pointers."""
-    _fields_ = [("n_frames", c_int), ("max_det_per_frame", c_int),
-                ("det_off", c_void_p), ("gt_off", c_void_p), ("dc_off", c_void_p),
-                ("pair_off", c_void_p), ("dcpair_off", c_void_p),
-                ("det", c_void_p), ("gt", c_void_p), ("dc", c_void_p),
-                ("ov_img", c_void_p), ("ov_bev", c_void_p), ("ov_3d", c_void_p), ("ov_dc", c_void_p)]
-
-
-class KittiMatchDesc(ctypes.Structure):
-    """struct srcnn_kitti_match_desc (include/srcnn_hip.h): one match pass, device pointers."""
-    _fields_ = [("n_cfg", c_int), ("n_slots", c_int), ("compute_fp", c_int), ("n_gt_total", c_int), ("n_det_total", c_int),
-                ("cfg_flags", c_void_p), ("cfg_metric", c_void_p), ("cfg_min_overlap", c_void_p), ("cfg_n_thresh", c_void_p),
-                ("thresholds", c_void_p), ("ign_gt", c_void_p), ("ign_det", c_void_p),
-                ("gt_score", c_void_p), ("tp", c_void_p), ("fp", c_void_p), ("fn", c_void_p), ("similarity", c_void_p)]
-
-
-class AnchorTargetParams(ctypes.Structure):
-    """struct srcnn_anchor_target_params (include/srcnn_hip.h)."""
-    _fields_ = [("negative_overlap", c_float), ("positive_overlap", c_float), ("clobber_positives", c_int),
-                ("batch_size", c_int), ("num_fg", c_int), ("inside_weight", c_float)]
-
-
-class ProposalTargetParams(ctypes.Structure):
-    """struct srcnn_proposal_target_params (include/srcnn_hip.h)."""
-    _fields_ = [("fg_thresh", c_float), ("bg_thresh_hi", c_float), ("bg_thresh_lo", c_float),
-                ("rois_per_image", c_int), ("fg_rois_per_image", c_int), ("kpts_grid", c_int),
-                ("bbox_means", c_float * 4), ("bbox_stds", c_float * 4), ("dim_means", c_float * 5), ("dim_stds", c_float * 5),
-                ("inside_weights", c_float * 4)]
-
-
-class GtSlot(ctypes.Structure):
-    """struct srcnn_gt_slot (include/srcnn_hip.h)."""
-    _fields_ = [("row_begin", c_int), ("n", c_int), ("im_scale", c_float), ("im_width", c_float)]
-
-
-class TrainImage(ctypes.Structure):
-    """struct srcnn_train_image (include/srcnn_hip.h)."""
-    _fields_ = [("left", c_void_p), ("right", c_void_p), ("H", c_int), ("W", c_int), ("flipped", c_int), ("scale", c_double)]
-
-
-class PrepLayer(ctypes.Structure):
-    """struct srcnn_prep_layer (include/srcnn_hip.h)."""
-    _fields_ = [("form", c_int), ("n_src", c_int), ("kh", c_int), ("kw", c_int), ("cin", c_int), ("cin2", c_int),
-                ("cout", c_int * 3), ("frag_rows", c_int), ("alias_of", c_int), ("pad_", c_int),
-                ("w", c_void_p * 3), ("b", c_void_p * 3),
-                ("bn_g", c_void_p * 2), ("bn_b", c_void_p * 2), ("bn_m", c_void_p * 2), ("bn_v", c_void_p * 2),
-                ("dst_w", c_void_p), ("dst_b", c_void_p), ("dst_hi", c_void_p), ("dst_lo", c_void_p), ("dst_frag", c_void_p)]
-
-
-_SIGNATURES = {
-    # name: (restype, argtypes)
-    "srcnn_version": (c_int, []),
-    "srcnn_last_error": (ctypes.c_char_p, []),
-    "srcnn_nms_workspace_bytes": (c_size_t, [c_int]),
-    "srcnn_nms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "srcnn_nms_batched_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "srcnn_nms_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
-                                  c_void_p, c_size_t, c_void_p]),
-    "nms_cuda": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "roi_align_forward_cuda": (c_int, [c_int, c_int, c_float, c_void_p, c_int, c_int, c_int, c_int,
-                                       c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_pyramid_roi_align": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
-                                        c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                        c_void_p, c_void_p]),
-    "srcnn_pool2x2_s1": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "roi_align_backward_cuda": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
-                                        c_int, c_void_p]),
-    "srcnn_pool2x2_s1_backward": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "srcnn_pyramid_roi_align_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
-                                                 ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
-                                                 c_int, c_void_p, c_void_p]),
-    "srcnn_act_convert": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
-    "srcnn_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_decode_kept_kpts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                       c_void_p]),
-    "srcnn_conv2d_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
-    "srcnn_conv2d": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_size_t, c_void_p]),
-    "srcnn_conv2d_chain_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "srcnn_conv2d_chain": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
-    "srcnn_conv2d_group": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
-    "srcnn_conv2d_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
-    "srcnn_conv2d_backward": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
-    "srcnn_conv2d_backward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvBwdDesc)]),
-    "srcnn_conv2d_backward_f16x3": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_size_t, c_void_p]),
-    "srcnn_conv2d_forward_f16x3_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvFwdF16x3Desc)]),
-    "srcnn_conv2d_forward_f16x3": (c_int, [ctypes.POINTER(ConvFwdF16x3Desc), c_void_p, c_size_t, c_void_p]),
-    "srcnn_conv2d_forward_f16x3_maxima": (c_int, [ctypes.POINTER(ConvFwdF16x3Desc), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "srcnn_conv2d_backward_f16x3_maxima": (c_int, [ctypes.POINTER(ConvBwdDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
-    "srcnn_absmax": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
-    "srcnn_upsample_add_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "srcnn_subsample2_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "srcnn_pixel_shuffle2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "srcnn_range_flag_read": (c_int, [c_int]),
-    "srcnn_range_flag_device_word": (c_void_p, []),
-    "srcnn_range_flag_bind": (c_int, [c_void_p]),
-    "srcnn_preprocess": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "srcnn_stem_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "srcnn_stem_pack_pair": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "srcnn_maxpool3x3s2_ceil": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "srcnn_upsample_add": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
-                                   c_int, c_void_p]),
-    "srcnn_subsample2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "srcnn_nhwc_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_nchw_to_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_rpn_score": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "srcnn_rpn_score_levels": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "srcnn_rpn_score_parts": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int),
-                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "srcnn_proposal_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "srcnn_proposal_workspace_layout": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t), c_int]),
-    "srcnn_proposal_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_int, c_void_p,
-                                     c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                     c_void_p]),
-    "srcnn_softmax_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_box_head_tail": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_kpts_tail": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_decode_detections": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p]),
-    "srcnn_class_nms_workspace_bytes": (c_size_t, [c_int]),
-    "srcnn_class_nms": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p,
-                                c_void_p, c_size_t, c_void_p]),
-    "srcnn_pack_detections": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "srcnn_dense_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "srcnn_dense_align_workspace_layout": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t), c_int]),
-    "srcnn_dense_align": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_size_t, c_void_p]),
-    "srcnn_box3d_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "srcnn_infer_boundary": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "srcnn_solve_4dof": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_float,
-                                 c_void_p, c_void_p]),
-    "srcnn_solve_4dof_scalar": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_float,
-                                        c_void_p, c_void_p]),
-    "srcnn_solve_3dof_scalar": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_void_p,
-                                        c_void_p, c_void_p, c_void_p]),
-    "srcnn_align_inputs": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_solve_3dof": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_void_p,
-                                 c_void_p, c_void_p, c_void_p]),
-    "srcnn_solve_4dof_records_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double,
-                                              c_float, c_void_p, c_int]),
-    "srcnn_solve_3dof_records_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_double,
-                                              c_void_p, c_void_p, c_void_p, c_int]),
-    "srcnn_solve_4dof_host": (c_int, [c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
-    "srcnn_solve_3dof_host": (c_int, [c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
-                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_solver_evaluate_host": (c_int, [c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_program_create": (c_void_p, []),
-    "srcnn_program_destroy": (None, [c_void_p]),
-    "srcnn_program_begin": (c_int, [c_void_p, c_void_p]),
-    "srcnn_program_end": (c_int, [c_void_p]),
-    "srcnn_program_recording": (c_int, []),
-    "srcnn_program_record_event": (c_int, [c_void_p, c_void_p]),
-    "srcnn_program_wait_event": (c_int, [c_void_p, c_void_p, c_int]),
-    "srcnn_program_size": (c_int, [c_void_p]),
-    "srcnn_program_run": (c_int, [c_void_p, c_void_p]),
-    "srcnn_stream_create": (c_int, [c_int, ctypes.POINTER(c_void_p)]),
-    "srcnn_stream_create_cu_mask": (c_int, [c_int, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(c_void_p)]),
-    "srcnn_stream_destroy": (c_int, [c_void_p]),
-    "srcnn_probe_placement": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
-    "srcnn_prof_enable": (c_int, [c_int]),
-    "srcnn_prof_read_launches": (c_int, [ctypes.POINTER(ctypes.c_float), c_int]),
-    "srcnn_prof_read": (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_double),
-                                ctypes.POINTER(ctypes.c_longlong)]),
-    "srcnn_kitti_overlaps": (c_int, [ctypes.POINTER(KittiSplit), c_void_p]),
-    "srcnn_kitti_match": (c_int, [ctypes.POINTER(KittiSplit), ctypes.POINTER(KittiMatchDesc), c_void_p]),
-    "srcnn_loss_workspace_bytes": (c_size_t, [ctypes.c_longlong]),
-    "srcnn_cross_entropy": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_size_t, c_void_p]),
-    "srcnn_cross_entropy_backward": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_void_p,
-                                             c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
-    "srcnn_smooth_l1": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int, c_float,
-                                c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "srcnn_smooth_l1_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_longlong, c_int,
-                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "srcnn_anchor_targets_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "srcnn_anchor_targets": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                     ctypes.POINTER(AnchorTargetParams)] + [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
-    "srcnn_proposal_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "srcnn_proposal_targets": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                       c_void_p, ctypes.POINTER(ProposalTargetParams)] + [c_void_p] * 12
-                               + [c_void_p, c_size_t, c_void_p]),
-    "srcnn_grad_norm_workspace_bytes": (c_size_t, [c_int, ctypes.POINTER(ctypes.c_longlong)]),
-    "srcnn_grad_norm": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong), c_int, c_float, c_void_p, c_void_p, c_size_t,
-                                c_void_p]),
-    "srcnn_grad_scale": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong), c_int, c_void_p, c_void_p]),
-    "srcnn_sgd_step": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong),
-                               ctypes.POINTER(c_float), ctypes.POINTER(c_float), ctypes.POINTER(c_int), c_int, c_float, c_int, c_void_p,
-                               c_void_p]),
-    "srcnn_prep_weights_workspace_bytes": (c_size_t, [c_int]),
-    "srcnn_prep_weights": (c_int, [ctypes.POINTER(PrepLayer), c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "srcnn_gt_batch": (c_int, [c_void_p, c_int, ctypes.POINTER(GtSlot), c_int, c_void_p, c_int, c_int] + [c_void_p] * 6 + [c_void_p]),
-    "srcnn_preprocess_train": (c_int, [ctypes.POINTER(TrainImage), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "srcnn_overlay_workspace_bytes": (c_size_t, [c_int]),
-    "srcnn_render_overlay": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.POINTER(c_double), c_float, c_void_p,
-                                     c_double, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "srcnn_bev_lidar": (c_int, [c_void_p, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+# Host arrays and out-parameters whose header names do not end in _host (renaming them would touch the header).
+_HOST_ARRAYS = {
+    "srcnn_rpn_score_levels": ("heads", "level_hw"),
+    "srcnn_rpn_score_parts": ("parts", "nparts", "plane_floats", "level_hw"),
+    "srcnn_proposal_workspace_layout": ("offsets",),
+    "srcnn_dense_align_workspace_layout": ("offsets",),
+    "srcnn_stream_create": ("stream",),
+    "srcnn_stream_create_cu_mask": ("mask", "stream"),
+    "srcnn_prof_read": ("conv_ms", "conv_flops", "conv_launches"),
+    "srcnn_prof_read_launches": ("ms",),
 }
+
+# base type -> (ctype, or None for void; pointer levels the name itself carries); parse_header adds the header's typedefs
+_BASE_TYPES = {"void": (None, 0), "int": (c_int, 0), "unsigned": (ctypes.c_uint, 0), "unsigned int": (ctypes.c_uint, 0),
+               "long long": (ctypes.c_longlong, 0), "float": (c_float, 0), "double": (c_double, 0), "size_t": (c_size_t, 0),
+               "char": (ctypes.c_char, 0), "signed char": (ctypes.c_byte, 0), "unsigned char": (ctypes.c_ubyte, 0)}
+_DECLARATOR = r"\s*((?:\*\s*)*)([A-Za-z_]\w*)\s*(?:\[\s*(\d+)\s*\])?\s*"
+_STATEMENT = r"\s*(?:typedef\s+struct\s+\w*\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>\w+)|(?P<decl>[^;{}]+?))\s*;"
+
+Header = collections.namedtuple("Header", "constants structs signatures")
+
+
+def _match(pattern, text, where, match=re.fullmatch):
+    m = match(pattern, text, flags=re.S)
+    if not m:
+        raise ValueError("declaration does not split: %s" % where)
+    return m
+
+
+def _declarators(decl, types, where):
+    """'const float *const *x, *y[2]' -> [(name, ctype of the base or None for void, pointer depth, array length or 0), ...]."""
+    first, *rest = re.sub(r"\bconst\b", " ", decl).split(",")
+    m = _match(r"\s*(\w+(?:\s+\w+)*?)\b" + _DECLARATOR, first, where)
+    base = " ".join(m.group(1).split())
+    if base not in types:
+        raise ValueError("unknown base type %r: %s" % (base, where))
+    ctype, depth = types[base]
+    return [(name, ctype, depth + stars.count("*"), int(n or 0))
+            for stars, name, n in [m.groups()[1:]] + [_match(_DECLARATOR, r, where).groups() for r in rest]]
+
+
+def _ctype(ctype, depth, host, where):
+    """The module docstring's type rule for one argument or return value."""
+    if depth == 1 and isinstance(ctype, type) and issubclass(ctype, ctypes.Structure):
+        return ctypes.POINTER(ctype)
+    if host:
+        if depth == 0 or (depth == 1 and ctype is None):
+            raise ValueError("a host array must be a pointer to a sized type: %s" % where)
+        return ctypes.POINTER(ctype if depth == 1 else c_void_p)
+    if depth:
+        return c_void_p
+    if ctype is None:
+        raise ValueError("a value cannot be void: %s" % where)
+    return ctype
+
+
+def parse_header(text, host_arrays=None):
+    """What a header text declares -> Header(constants {NAME: int}, SRCNN_ stripped; structs {C name: ctypes.Structure};
+    signatures {name: (restype, [argtypes])}).  host_arrays: {function: arguments typed as host arrays without a _host suffix}."""
+    host_arrays = {k: list(v) for k, v in (host_arrays or {}).items()}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, structs, signatures = {}, collections.OrderedDict(), collections.OrderedDict()
+    types = dict(_BASE_TYPES)
+
+    def fresh(name, where):
+        if name in constants or name in types or name in signatures:
+            raise ValueError("duplicate name %r: %s" % (name, where))
+        return name
+
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+SRCNN_(\w+)[ \t]+(\(?[ \t]*-?\d.*?)[ \t]*$", text, flags=re.M):
+        where = "#define SRCNN_%s %s" % (name, value)
+        m = re.fullmatch(r"\(\s*(-?\w+)\s*\)|(-?\w+)", value)
+        if not m or not re.fullmatch(r"-?(0[xX][0-9a-fA-F]+|\d+)", m.group(1) or m.group(2)):
+            raise ValueError("not an integer: %s" % where)
+        constants[fresh(name, where)] = int(m.group(1) or m.group(2), 0)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*$", " ", text, flags=re.S | re.M)   # extern "C" { / }
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+
+    pos = 0
+    while text[pos:].strip():
+        m = _match(_STATEMENT, text[pos:], " ".join(text[pos:pos + 200].split()), re.match)
+        pos += m.end()
+        where = " ".join(m.group(0).split())
+        if m.group("struct"):
+            cname = fresh(m.group("struct"), where)
+            *members, tail = m.group("body").split(";")
+            fields = [(name, c_void_p if depth else _ctype(ctype, 0, False, where), n)
+                      for s in members for name, ctype, depth, n in _declarators(s, types, "%s; in struct %s" % (" ".join(s.split()), cname))]
+            if tail.strip() or len({f[0] for f in fields}) != len(fields):
+                raise ValueError("declaration does not split: %s" % where)
+            pyname = "".join(p.capitalize() for p in re.sub(r"^srcnn_", "", cname).split("_"))
+            structs[cname] = type(pyname, (ctypes.Structure,), {"_fields_": [(name, t * n if n else t) for name, t, n in fields],
+                                                                "__doc__": "struct %s (include/srcnn_hip.h)." % cname})
+            types[cname] = (structs[cname], 0)
+            continue
+        handle = re.fullmatch(r"typedef\s+void\s*\*\s*(\w+)", m.group("decl"))
+        if handle:                                  # srcnn_stream_t: void with one pointer level of its own
+            types[fresh(handle.group(1), where)] = (None, 1)
+            continue
+        fn = _match(r"SRCNN_API\s+([^(),]+)\((.*)\)", m.group("decl"), where)
+        (name, ctype, depth, n), = _declarators(fn.group(1), types, where)
+        fresh(name, where)
+        if (ctype, depth) == (ctypes.c_char, 1):
+            restype = ctypes.c_char_p
+        else:
+            restype = None if (ctype, depth) == (None, 0) else _ctype(ctype, depth, False, where)
+        listed = host_arrays.pop(name, [])
+        argtypes = []
+        for a in ([] if fn.group(2).strip() == "void" else fn.group(2).split(",")):
+            (aname, ctype, depth, an), = _declarators(a, types, where)
+            n += an
+            host = aname in listed or aname.endswith("_host")
+            if aname in listed:
+                listed.remove(aname)
+            argtypes.append(_ctype(ctype, depth, host, "%s in %s" % (" ".join(a.split()), where)))
+        if n:
+            raise ValueError("declaration does not split (an array in a signature): %s" % where)
+        if listed:
+            raise ValueError("the host-array table names %s, which is no argument of: %s" % (", ".join(listed), where))
+        signatures[name] = (restype, argtypes)
+    if host_arrays:
+        raise ValueError("the host-array table names functions the header lacks: %s" % ", ".join(sorted(host_arrays)))
+    return Header(constants, structs, signatures)
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError("include/srcnn_hip.h not found at %s: the ctypes binding is derived from it" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read(), _HOST_ARRAYS)
+
+
+HEADER = _read_header()
+globals().update(HEADER.constants)                                      # FMT_F32, REC_COLS, LOSS_ROWS_PER_WG, PREP_CONV, ...
+globals().update((s.__name__, s) for s in HEADER.structs.values())      # ConvDesc, ConvBwdDesc, KittiSplit, PrepLayer, ...
+_SIGNATURES = HEADER.signatures
 
 _lib = None
 

@@ -9,10 +9,11 @@ records per step (~29 KB/image: latency-bound on xGMI, issued asynchronously).
 import torch
 import torch.distributed as dist
 
+from ._lib import REC_COLS
+
 # one row per detection: [score, left box 4, right box 4, dim_orien 5, kpts 5, roi index | 4-DoF status, x y z theta (4-DoF) |
-# alignment status, disparity, final x y z theta, alpha] -- include/srcnn_hip.h SRCNN_REC_COLS; columns 20.. are filled by
+# alignment status, disparity, final x y z theta, alpha] -- REC_COLS floats, listed in include/srcnn_hip.h; columns 20.. are filled by
 # the device 3-D stage (pipeline.launch_3d) and are zero in a detector-only record
-REC_COLS = 32
 
 
 def shard_indices(num_items, rank, world_size):

@@ -26,6 +26,8 @@ import time
 
 import numpy as np
 
+from ._lib import KITTI_COLS, KITTI_MAX_DET as MAX_DET_PER_FRAME     # the library's row width and per-frame limit
+
 CLASSES = ('Car', 'Pedestrian', 'Cyclist')
 NEIGHBOUR = {'car': 'van', 'pedestrian': 'person_sitting'}         # counted as ignored, not as false
 DIFFICULTIES = ('easy', 'moderate', 'hard')
@@ -37,12 +39,11 @@ DEFAULT_OVERLAPS = {'Car': ((0.7, 0.7, 0.7), (0.7, 0.5, 0.5)),
                     'Pedestrian': ((0.5, 0.5, 0.5), (0.5, 0.25, 0.25)),
                     'Cyclist': ((0.5, 0.5, 0.5), (0.5, 0.25, 0.25))}
 N_SAMPLE_PTS = 41
-MAX_DET_PER_FRAME = 4096                                            # SRCNN_KITTI_MAX_DET (include/srcnn_hip.h)
 
 LABEL_DTYPE = np.dtype([('type', 'U32'), ('truncated', 'f8'), ('occluded', 'i4')] +
                        [(f, 'f8') for f in ('alpha', 'x1', 'y1', 'x2', 'y2', 'h', 'w', 'l', 'x', 'y', 'z', 'ry')])
 RESULT_DTYPE = np.dtype(LABEL_DTYPE.descr + [('score', 'f8')])
-# device row: [x1 y1 x2 y2 h w l x y z ry alpha score] (SRCNN_KITTI_COLS)
+# device row: [x1 y1 x2 y2 h w l x y z ry alpha score] (KITTI_COLS of them)
 _ROW = ('x1', 'y1', 'x2', 'y2', 'h', 'w', 'l', 'x', 'y', 'z', 'ry', 'alpha')
 
 
@@ -170,7 +171,7 @@ class _Flat(object):
 
     @staticmethod
     def rows(a, with_score):
-        out = np.zeros((len(a), 13), np.float64)
+        out = np.zeros((len(a), KITTI_COLS), np.float64)
         for k, name in enumerate(_ROW):
             out[:, k] = a[name]
         if with_score:
@@ -188,7 +189,7 @@ def _device_overlaps(fl, dev):
     def dt(a, dtype):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
 
-    rows = [dt(_Flat.rows(a, a is fl.det), np.float64) if len(a) else torch.zeros(13, dtype=torch.float64, device=dev)
+    rows = [dt(_Flat.rows(a, a is fl.det), np.float64) if len(a) else torch.zeros(KITTI_COLS, dtype=torch.float64, device=dev)
             for a in (fl.det, fl.gt, fl.dc)]
     offs = [dt(a, np.int32) for a in (fl.det_off, fl.gt_off, fl.dc_off)] + [dt(a, np.int64) for a in (fl.pair_off, fl.dcpair_off)]
     npair, ndc = int(fl.pair_off[-1]), int(fl.dcpair_off[-1])
