@@ -25,6 +25,17 @@ backward.  When only the backward is f16x3 the scan therefore moves to the forwa
 consumer, one pass instead of two for a block input that feeds conv1 and downsample -- and it is issued only where a weight
 gradient will want it (grad mode on and the weight requires grad).  A maximum does not depend on who computed it: every result
 keeps its bits.  engine.F16X3_MAXIMA counts the passes issued and the calls served by an older word.
+
+'auto' (either precision).  choose_engine(direction, M, N, K) names the engine per call from the call's GEMM size -- a closed-form
+rule fitted to the measured table in stereo_rcnn_amd/train_engine_table.py -- and the call then runs exactly as if that engine had
+been asked for: a layer resolved to fp32 neither scans nor records a maximum, and the next f16x3 consumer of its output scans once.
+An explicit 'f32' or 'f16x3' is never replaced.
+
+prepared=.  max |w| and the hi / lo planes of a weight are functions of the weight alone.  engine.prepare_train_weights computes
+them for a list of folded weights in one call (csrc/train_weights.hip); a PreparedLayer carries one layer's folded weight (still in
+the graph), bias and planes, and a function given it launches no pass over the weight in either direction.  The bits do not change.
+Nothing here caches across optimiser steps: optim.SGD writes parameters through raw pointers, which no version counter sees, so
+whoever steps prepares again (stereo_rcnn_amd.training.TrainWeights).
 """
 import collections
 import weakref
@@ -40,12 +51,91 @@ class Precision(collections.namedtuple('Precision', 'forward backward reuse_maxi
 
     def __new__(cls, forward='f32', backward='f32', reuse_maxima=True):
         for name, value in (('forward', forward), ('backward', backward)):
-            if value not in ('f32', 'f16x3'):
-                raise ValueError("%s_precision must be 'f32' or 'f16x3' (got %r)" % (name, value))
+            if value not in ('f32', 'f16x3', 'auto'):
+                raise ValueError("%s_precision must be 'f32' or 'f16x3' (got %r), or 'auto' for choose_engine's pick per layer" % (name, value))
         return super().__new__(cls, forward, backward, bool(reuse_maxima))
 
     def without_graph(self):
         return self._replace(forward='f32')         # layers without a graph (the frozen stages) stay on the fp32 forward
+
+    def resolved(self, M, N, K):
+        """'auto' replaced by choose_engine's answer for one call's GEMM, each direction on its own; an explicit engine stays."""
+        if 'auto' not in (self.forward, self.backward):
+            return self
+        return self._replace(forward=choose_engine('forward', M, N, K) if self.forward == 'auto' else self.forward,
+                             backward=choose_engine('backward', M, N, K) if self.backward == 'auto' else self.backward)
+
+
+# choose_engine's thresholds, fitted to profiles/train_engine_table.txt (train_engine_table.ROWS holds its rows; the table times
+# the f16x3 calls with maxima handed over and weights prepared, so a layer's f16x3 time carries no preparation).
+# tests/test_auto_precision_cpu.py holds the rule to every row outside the +-3 % band.
+# Forward: every measured layer of 4750 rows and more wins (0.41 .. 0.94, one at 1.02) and every layer of 1197 rows and fewer
+# loses (1.05 .. 2.03): below a few thousand rows the call streams its weights once whatever the engine, and the split adds work.
+AUTO_FORWARD_MIN_M = 2400
+# Backward: it wins wherever M is small or moderate (0.43 .. 0.97 up to 4750 rows: the weight gradient's long K = M is where the
+# f16 pipe pays), and at large M only where a pixel carries enough products: the mask pass, the staged gradient and the split of
+# both wgrad operands cost per pixel, the gain grows with N K per pixel.  Measured at M >= 18675: N K <= 65536 loses (1.06 .. 1.24),
+# N K >= 131072 wins (0.61 .. 0.81).  M N K >= AUTO_BACKWARD_MIN_NK * M states N K >= 98304 in the rule's own terms.
+AUTO_BACKWARD_MIN_M = 64
+AUTO_BACKWARD_LARGE_M = 8192
+AUTO_BACKWARD_MIN_NK = 98304
+
+
+def choose_engine(direction, M, N, K):
+    """The engine 'auto' stands for in one convolution call: 'f16x3' or 'f32'.  direction: 'forward' (y) or 'backward' (dx, dw,
+    db); M = B OH OW output pixels, N = Cout, K = KH KW Cin.  A pure closed-form rule over M and M N K (the thresholds above):
+      forward   f16x3 iff M >= AUTO_FORWARD_MIN_M;
+      backward  f16x3 iff M >= AUTO_BACKWARD_MIN_M and (M < AUTO_BACKWARD_LARGE_M or M N K >= AUTO_BACKWARD_MIN_NK * M).
+    A degenerate M = 1 is fp32 in both directions."""
+    if direction not in ('forward', 'backward'):
+        raise ValueError("direction must be 'forward' or 'backward' (got %r)" % (direction,))
+    M, N, K = int(M), int(N), int(K)
+    if direction == 'forward':
+        return 'f16x3' if M >= AUTO_FORWARD_MIN_M else 'f32'
+    return 'f16x3' if M >= AUTO_BACKWARD_MIN_M and (M < AUTO_BACKWARD_LARGE_M or M * N * K >= AUTO_BACKWARD_MIN_NK * M) else 'f32'
+
+
+class PreparedLayer(collections.namedtuple('PreparedLayer', 'w b planes')):
+    """One layer as stereo_rcnn_amd.training.TrainWeights prepares it: w, the folded weight in the engine's layout (Cout, KH, KW,
+    Cin), contiguous and still inside the graph (its gradient flows on to the parameter as it does from the weight a call folds
+    itself); b, the folded bias or None; planes, the engine.PreparedW made from w.  A function given `prepared=` uses w and b in
+    place of its weight / bias / bn arguments."""
+    __slots__ = ()
+
+
+# The engines of the calls of one forward, in call order: [(M, N, K, forward, backward)], appended to while it is a list
+# (record_engines); _REPLAY: an iterator of (forward, backward) that replaces the precisions of the calls one by one (replay_engines).
+_DECISIONS = None
+_REPLAY = None
+
+
+class record_engines(object):
+    """with record_engines() as log: ... -- log receives (M, N, K, forward engine, backward engine) of every convolution call."""
+
+    def __enter__(self):
+        global _DECISIONS
+        self.outer, _DECISIONS = _DECISIONS, []
+        return _DECISIONS
+
+    def __exit__(self, *exc):
+        global _DECISIONS
+        _DECISIONS = self.outer
+
+
+class replay_engines(object):
+    """with replay_engines(engines): ... -- the i-th convolution call runs on engines[i] = (forward, backward), both explicit,
+    whatever its own precision keywords say: a recorded 'auto' run, forced layer by layer."""
+
+    def __init__(self, engines):
+        self.engines = [(f, b) for f, b in engines]
+
+    def __enter__(self):
+        global _REPLAY
+        self.outer, _REPLAY = _REPLAY, iter(self.engines)
+
+    def __exit__(self, *exc):
+        global _REPLAY
+        _REPLAY = self.outer
 
 
 def _bn_scale_shift(bn, eps=1e-5):
@@ -77,9 +167,19 @@ def _known_maximum(t):
     return hit[2]
 
 
-def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, prec):
+def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, prec, prepared=None):
     """_Conv2dNHWC.apply with the record of maxima around it.  x is contiguous (B, H, W, Cin): the convolution reads the tensor's
-    full channel range (Cin = its last dimension = its pixel stride), which is what a recorded word covers."""
+    full channel range (Cin = its last dimension = its pixel stride), which is what a recorded word covers.  'auto' is resolved
+    here, per call; what follows sees two explicit engines, so a layer resolved to fp32 neither scans nor records a maximum.
+    prepared: an engine.PreparedW made from `weight`, or None."""
+    cout, kh, kw, cin = (int(v) for v in weight.shape)
+    OH, OW = engine.conv_out_hw(int(x.shape[1]), int(x.shape[2]), kh, kw, stride, pad)
+    M, K = int(x.shape[0]) * OH * OW, kh * kw * cin
+    prec = prec.resolved(M, cout, K)
+    if _REPLAY is not None:
+        prec = Precision(*next(_REPLAY), reuse_maxima=prec.reuse_maxima).resolved(M, cout, K)
+    if _DECISIONS is not None:
+        _DECISIONS.append((M, cout, K, prec.forward, prec.backward))
     x_word = y_word = None
     fresh = False
     f16_fwd = prec.forward == 'f16x3'
@@ -92,7 +192,7 @@ def _conv_nhwc(x, weight, bias, residual, stride, pad, relu, prec):
             fresh = True
         if f16_fwd:
             y_word = torch.empty(1, dtype=torch.int32, device=x.device)
-    y = _Conv2dNHWC.apply(x, weight, bias, residual, stride, pad, relu, prec, x_word, y_word, fresh)
+    y = _Conv2dNHWC.apply(x, weight, bias, residual, stride, pad, relu, prec, x_word, y_word, fresh, prepared)
     if y_word is not None:
         _record_maximum(y, y_word)
     return y
@@ -103,10 +203,14 @@ class _Conv2dNHWC(torch.autograd.Function):
     (B, OH, OW, Cout) or None; all contiguous float32 on the device."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, stride, pad, relu, prec=Precision(), x_word=None, y_word=None, x_word_fresh=False):
-        """prec: a Precision; x_word: the word of max |x| or None; y_word: a word to receive max |y| (f16x3 forward) or None;
-        x_word_fresh: x_word was scanned for this call, so its first use is not a scan avoided."""
+    def forward(ctx, x, weight, bias, residual, stride, pad, relu, prec=Precision(), x_word=None, y_word=None, x_word_fresh=False,
+                prepared=None):
+        """prec: a Precision without 'auto'; x_word: the word of max |x| or None; y_word: a word to receive max |y| (f16x3 forward)
+        or None; x_word_fresh: x_word was scanned for this call, so its first use is not a scan avoided; prepared: the
+        engine.PreparedW of `weight` or None -- the f16x3 calls of either direction then skip their own pass over the weights, a
+        layer on the fp32 engine ignores it."""
         ctx.backward_precision = prec.backward
+        ctx.prepared = prepared
         B, H, W, cin = (int(v) for v in x.shape)
         cout, kh, kw = int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         cw = engine.ConvW(weight.detach(), None if bias is None else bias.detach(), kh, kw, stride, pad, relu)
@@ -114,7 +218,7 @@ class _Conv2dNHWC(torch.autograd.Function):
         y = torch.empty((B, OH, OW, cout), dtype=torch.float32, device=x.device)
         res = None if residual is None else residual.detach()
         if prec.forward == 'f16x3':
-            engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res, x_amax=x_word, y_amax=y_word)
+            engine.conv2d_train_f16x3(cw, x.detach(), B, H, W, y, OH, OW, residual=res, x_amax=x_word, y_amax=y_word, prepared=prepared)
             if x_word is not None:
                 engine.F16X3_MAXIMA['reused'] += 0 if x_word_fresh else 1
                 x_word_fresh = False
@@ -138,12 +242,13 @@ class _Conv2dNHWC(torch.autograd.Function):
         res = {}
         if want or g_out is not None:
             cw = engine.ConvW(weight, None, kh, kw, stride, pad, relu)
-            x_word = ctx.x_word if ctx.backward_precision == 'f16x3' else None
+            f16 = ctx.backward_precision == 'f16x3'
+            x_word = ctx.x_word if f16 else None
             res = engine.conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=want, g_out=g_out, precision=ctx.backward_precision,
-                                         x_amax=x_word)
+                                         x_amax=x_word, prepared=ctx.prepared if f16 else None)
             if x_word is not None and need_w and not ctx.x_word_fresh:
                 engine.F16X3_MAXIMA['reused'] += 1
-        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None) + (None,) * 7
+        return (res.get('dx'), res.get('dw'), res.get('db'), (g_out if relu else dy) if need_r else None) + (None,) * 8
 
 
 def _check(x, weight):
@@ -187,49 +292,77 @@ def _fold(weight_eng, bias, bn):
     return w, b
 
 
+def _folded(prepared, fold):
+    """(w, b, planes) of a public function's layer: the PreparedLayer's, or fold()'s own w (made contiguous) and b without planes."""
+    if prepared is not None:
+        return prepared.w, prepared.b, prepared.planes
+    w, b = fold()
+    return w.contiguous(), b, None
+
+
+def fold_conv(weight, bias=None, bn=None):
+    """conv2d's / conv2d_nhwc's folded weight and bias: weight (Cout, Cin, KH, KW) -> (Cout, KH, KW, Cin) with the frozen BN in."""
+    return _fold(weight.permute(0, 2, 3, 1), bias, bn)
+
+
+def fold_linear(weight, bias=None):
+    """linear's: weight (out, K) -> (out, 1, 1, K)."""
+    return weight.contiguous().view(int(weight.shape[0]), 1, 1, int(weight.shape[1])), bias
+
+
+def fold_deconv2x2(weight, bias=None):
+    """conv_transpose2x2's: weight (Cin, Cout, 2, 2) -> (4 Cout, 1, 1, Cin) in row order (i, j, co), the bias four times."""
+    cin, cout = int(weight.shape[0]), int(weight.shape[1])
+    return weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin), None if bias is None else bias.repeat(4)
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',
-           reuse_maxima=True):
+           reuse_maxima=True, prepared=None):
     """relu?(bn?(conv2d(x, weight) + bias) + residual) on the exact-fp32 engine, differentiable with respect to x, weight, bias
     and residual.  x (B, Cin, H, W) with Cin a multiple of 32, weight (Cout, Cin, KH, KW) as nn.Conv2d holds it, residual
     (B, Cout, OH, OW); bn: a dict with 'weight', 'bias', 'running_mean', 'running_var' -- the frozen BatchNorm that follows the
     convolution (no gradient reaches it).  backward_precision: 'f32' or 'f16x3', the engine of the gradients; forward_precision:
-    'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError).  reuse_maxima: see the module's
-    docstring.  Returns (B, Cout, OH, OW)."""
+    'f32' or 'f16x3', the engine of y (independent of it; anything else raises ValueError); either may be 'auto': choose_engine
+    decides per call.  reuse_maxima: see the module's docstring.  prepared: a PreparedLayer of this layer (fold_conv of the same
+    weight, bias and bn, then engine.prepare_train_weights): its w and b are used, and the f16x3 calls skip their passes over the
+    weight.  Returns (B, Cout, OH, OW)."""
     prec = Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     if int(x.shape[1]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[1]))
-    w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
+    w, b, planes = _folded(prepared, lambda: fold_conv(weight, bias, bn))
     r = None if residual is None else _ToNHWC.apply(residual)
-    y = _conv_nhwc(_ToNHWC.apply(x), w.contiguous(), b, r, int(stride), int(padding), bool(relu), prec)
+    y = _conv_nhwc(_ToNHWC.apply(x), w, b, r, int(stride), int(padding), bool(relu), prec, planes)
     return _ToNCHW.apply(y)
 
 
-def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None):
+def linear(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None,
+           prepared=None):
     """relu?(x @ weight.T + bias) as a 1x1 convolution over an (n, 1, 1, K) tensor: x (n, K), weight (out, K) as nn.Linear holds
-    it.  K must be a multiple of 32.  _prec: conv2d_nhwc's."""
+    it.  K must be a multiple of 32.  _prec: conv2d_nhwc's.  prepared: conv2d's, from fold_linear."""
     prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     n, K = int(x.shape[0]), int(x.shape[1])
     if K % 32 != 0:
         raise ValueError("linear: K must be a multiple of 32 (got %d)" % K)
     out = int(weight.shape[0])
-    y = _conv_nhwc(x.contiguous().view(n, 1, 1, K), weight.contiguous().view(out, 1, 1, K), bias, None, 1, 0, bool(relu), prec)
+    w, b, planes = _folded(prepared, lambda: fold_linear(weight, bias))
+    y = _conv_nhwc(x.contiguous().view(n, 1, 1, K), w, b, None, 1, 0, bool(relu), prec, planes)
     return y.view(n, out)
 
 
 def conv2d_nhwc(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',
-                reuse_maxima=True, _prec=None):
+                reuse_maxima=True, _prec=None, prepared=None):
     """conv2d without the layout edges: x (B, H, W, Cin), residual and the result (B, OH, OW, Cout) NHWC; weight still
     (Cout, Cin, KH, KW) as nn.Conv2d holds it (its re-layout is one small kernel and carries the gradient back).  _prec (private,
-    stereo_rcnn_amd.training's): an already validated Precision, used in place of the three keywords."""
+    stereo_rcnn_amd.training's): an already validated Precision, used in place of the three keywords.  prepared: conv2d's."""
     prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     if int(x.shape[3]) % 32 != 0:
         raise ValueError("Cin must be a multiple of 32 (got %d)" % int(x.shape[3]))
-    w, b = _fold(weight.permute(0, 2, 3, 1), bias, bn)
-    return _conv_nhwc(x.contiguous(), w.contiguous(), b, None if residual is None else residual.contiguous(),
-                      int(stride), int(padding), bool(relu), prec)
+    w, b, planes = _folded(prepared, lambda: fold_conv(weight, bias, bn))
+    return _conv_nhwc(x.contiguous(), w, b, None if residual is None else residual.contiguous(),
+                      int(stride), int(padding), bool(relu), prec, planes)
 
 
 def _check_nhwc(x, what):
@@ -333,12 +466,13 @@ class _PixelShuffle2(torch.autograd.Function):
         return pixel_shuffle2(dy.contiguous(), ctx.cq, inverse=True), None
 
 
-def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None):
+def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32', forward_precision='f32', reuse_maxima=True, _prec=None,
+                      prepared=None):
     """relu?(ConvTranspose2d(k=2, s=2)(x)): x (M, h, w, Cin) NHWC with Cin a multiple of 32, weight (Cin, Cout, 2, 2) as
     nn.ConvTranspose2d holds it, Cout a multiple of 8; returns (M, 2h, 2w, Cout).  A 1x1 convolution to 4 Cout channels in
     engine.prep_deconv2x2's row order (i, j, co) with the bias replicated four times, then the pixel shuffle; the ReLU commutes
     with the shuffle and stays in the convolution's epilogue.  Backward: the inverse shuffle of dy, then the convolution's
-    backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups.  _prec: conv2d_nhwc's."""
+    backward; torch's autograd takes dw back to (Cin, Cout, 2, 2) and sums db over the four (i, j) groups.  _prec: conv2d_nhwc's.  prepared: conv2d's, from fold_deconv2x2."""
     prec = _prec or Precision(forward_precision, backward_precision, reuse_maxima)
     _check(x, weight)
     cin, cout = int(weight.shape[0]), int(weight.shape[1])
@@ -346,9 +480,8 @@ def conv_transpose2x2(x, weight, bias=None, relu=False, backward_precision='f32'
         raise ValueError("conv_transpose2x2: weight (Cin, Cout, 2, 2) with x's Cin (got %s)" % (tuple(weight.shape),))
     if cin % 32 != 0 or cout % 8 != 0:
         raise ValueError("conv_transpose2x2: Cin a multiple of 32 and Cout a multiple of 8 (got %d, %d)" % (cin, cout))
-    w = weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin)
-    b = None if bias is None else bias.repeat(4)
-    y = _conv_nhwc(x.contiguous(), w.contiguous(), b, None, 1, 0, bool(relu), prec)
+    w, b, planes = _folded(prepared, lambda: fold_deconv2x2(weight, bias))
+    y = _conv_nhwc(x.contiguous(), w, b, None, 1, 0, bool(relu), prec, planes)
     out = _PixelShuffle2.apply(y, cout)
     word = _known_maximum(y)
     if word is not None:

@@ -29,7 +29,7 @@ def _newer(dst, srcs):
 def build(force=False, verbose=True):
     srcs = sorted(glob.glob(os.path.join(HERE, "*.hip")))
     hdrs = sorted(glob.glob(os.path.join(HERE, "*.h")) + glob.glob(os.path.join(HERE, "*.inc")))
-    hdrs.append(os.path.join(ROOT, "include", "srcnn_hip.h"))
+    hdrs += sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
     if not force and _newer(OUT, srcs + hdrs):
         return OUT
     os.makedirs(OBJ_DIR, exist_ok=True)

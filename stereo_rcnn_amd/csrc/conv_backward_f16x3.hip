@@ -54,6 +54,10 @@
 //
 // srcnn_conv2d_backward_f16x3_maxima: the caller already holds max|x| of the saved x as a device word (the forward found it, or
 // its producer's epilogue did); wgrad reads s_x from that word and the max|x| pass is not launched.  Nothing else differs.
+//
+// srcnn_conv2d_backward_f16x3_prepared: max|w| and the re-laid planes come from train_weights.hip (once per step for all layers);
+// dgrad reads the caller's planes, absmax_kernel over w and bwd_weight_relayout_split are not launched, and the clear
+// (f16x3_clear_scales_prepared) copies the layer's word into amax[1].  The GEMM kernels are unchanged.
 #include "conv_backward_common.h"
 #include "conv_f16x3_scaled.h"
 
@@ -244,6 +248,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f16x3_kernel(const BwdArgs 
     }
 }
 
+// What srcnn_train_weights_prepare left for the layer (the _prepared entry)
+struct BwdPrepared {
+    const unsigned *w_amax;
+    const void *wt_hi, *wt_lo;
+    size_t plane_bytes;
+};
+
+// The _maxima and _prepared entries' body (below).  prep: the layer's word and re-laid planes, or null -- then the call scans,
+// re-lays and splits w itself
+static int bwd_f16x3_run(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, const BwdPrepared *prep, void *workspace,
+                         size_t workspace_bytes, srcnn_stream_t stream);
+
 }  // namespace srcnn
 
 extern "C" {
@@ -265,13 +281,34 @@ int srcnn_conv2d_backward_f16x3(const srcnn_conv_bwd_desc *d, void *workspace, s
 int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, void *workspace, size_t workspace_bytes,
                                        srcnn_stream_t stream)
 {
-    using namespace srcnn;
+    return srcnn::bwd_f16x3_run(d, x_amax, nullptr, workspace, workspace_bytes, stream);
+}
+
+int srcnn_conv2d_backward_f16x3_prepared(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, const unsigned *w_amax, const void *wt_hi,
+                                         const void *wt_lo, size_t plane_bytes, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
+{
+    const srcnn::BwdPrepared prep = {w_amax, wt_hi, wt_lo, plane_bytes};
+    return srcnn::bwd_f16x3_run(d, x_amax, &prep, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+namespace srcnn {
+
+static int bwd_f16x3_run(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, const BwdPrepared *prep, void *workspace,
+                         size_t workspace_bytes, srcnn_stream_t stream)
+{
     BwdArgs a;
     BwdPlan pl;
     int rc = bwd_prepare(d, a, pl, true);
     if (rc != SRCNN_OK) return rc;
     rc = check_amax_words(x_amax, nullptr);
     if (rc != SRCNN_OK) return rc;
+    if (prep && d->dx) {                // the weight gradient reads no weights: without dx the three may be null
+        rc = check_prepared_planes("srcnn_conv2d_backward_f16x3_prepared", prep->w_amax, prep->wt_hi, prep->wt_lo, prep->plane_bytes,
+                                   (size_t)a.Cin * a.taps * a.Cp * sizeof(_Float16));
+        if (rc != SRCNN_OK) return rc;
+    }
     if (!workspace || workspace_bytes < pl.bytes) {
         set_error("srcnn_conv2d_backward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
         return SRCNN_ERR_WORKSPACE;
@@ -290,12 +327,23 @@ int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsig
     q.xmax = x_amax ? x_amax : q.amax + 2;
 
     hipStream_t st = as_stream(stream);
-    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, q.amax, static_cast<unsigned *>(nullptr));
+    if (prep) {
+        if (d->dx) {                    // dgrad reads the caller's planes; nothing writes them
+            q.wt_hi = static_cast<_Float16 *>(const_cast<void *>(prep->wt_hi));
+            q.wt_lo = static_cast<_Float16 *>(const_cast<void *>(prep->wt_lo));
+        }
+        SRCNN_LAUNCH(f16x3_clear_scales_prepared, dim3(1), dim3(64), 0, st, q.amax, static_cast<unsigned *>(nullptr),
+                     d->dx ? prep->w_amax : static_cast<const unsigned *>(nullptr));
+    } else {
+        SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, q.amax, static_cast<unsigned *>(nullptr));
+    }
     SRCNN_LAUNCH(bwd_mask_bias_kernel<true>, dim3(pl.nq, a.Cp / BK), dim3(256), 0, st, a, q.amax);
     if (d->db) SRCNN_LAUNCH(bwd_bias_reduce_kernel, dim3(a.Cp / BK), dim3(256), 0, st, a, pl.nq);
     if (d->dx) {
-        launch_absmax(a.w, a.Cout, a.Kw, a.Kw, q.amax + 1, st);
-        SRCNN_LAUNCH(bwd_weight_relayout_split, dim3(a.Cin / BK, a.Cp / BK, a.taps), dim3(32, 8), 0, st, a, q);
+        if (!prep) {
+            launch_absmax(a.w, a.Cout, a.Kw, a.Kw, q.amax + 1, st);
+            SRCNN_LAUNCH(bwd_weight_relayout_split, dim3(a.Cin / BK, a.Cp / BK, a.taps), dim3(32, 8), 0, st, a, q);
+        }
         dispatch_tile_4w(pl.d_mr, pl.d_nr, [&](auto mr, auto nr) {
             SRCNN_LAUNCH((conv_dgrad_f16x3_kernel<decltype(mr)::value, decltype(nr)::value>), dim3(a.d_mtiles * a.d_ntiles), dim3(256), 0, st, a, q);
         });
@@ -313,4 +361,4 @@ int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, const unsig
     return check_launch("srcnn_conv2d_backward_f16x3");
 }
 
-}  // extern "C"
+}  // namespace srcnn

@@ -5,6 +5,7 @@
 // backward round alike.  include/srcnn_hip.h states the scheme.
 #pragma once
 #include "conv_tile_4w.h"
+#include "../../include/srcnn_train_weights.h"
 #include <cstdint>
 
 namespace srcnn {
@@ -44,6 +45,27 @@ static __global__ void f16x3_clear_scales(unsigned *amax, unsigned *extra)
 {
     if (threadIdx.x < 4 && amax) amax[threadIdx.x] = 0u;
     if (threadIdx.x == 4 && extra) *extra = 0u;
+}
+
+// The *_prepared entries' clear: the same words, except that the max|w| word (amax[1] in the forward's and the backward's
+// layout alike) takes the bits srcnn_train_weights_prepare left in *wmax -- the GEMM kernels go on reading s_w from the workspace
+// and stay as they are.  wmax may be null (a backward without dx reads no weights): the word is cleared.
+static __global__ void f16x3_clear_scales_prepared(unsigned *amax, unsigned *extra, const unsigned *wmax)
+{
+    if (threadIdx.x < 4) amax[threadIdx.x] = (threadIdx.x == 1 && wmax) ? *wmax : 0u;
+    if (threadIdx.x == 4 && extra) *extra = 0u;
+}
+
+// The *_prepared entries' three arguments: the layer's max word and its plane pair, each plane `need` bytes at least
+static int check_prepared_planes(const char *who, const unsigned *w_amax, const void *hi, const void *lo, size_t plane_bytes, size_t need)
+{
+    SRCNN_REQUIRE_AS(who, w_amax != nullptr, "null pointer: w_amax");
+    SRCNN_REQUIRE_AS(who, hi != nullptr && lo != nullptr, "null pointer: a prepared plane");
+    SRCNN_REQUIRE_AS(who, (reinterpret_cast<uintptr_t>(w_amax) & 3) == 0, "w_amax must be 4-byte aligned");
+    SRCNN_REQUIRE_AS(who, ((reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(lo)) & 15) == 0,
+                     "the prepared planes must be 16-byte aligned (vector loads)");
+    SRCNN_REQUIRE_AS(who, plane_bytes >= need, "plane_bytes: a prepared plane holds Cp KH KW Cin halves");
+    return SRCNN_OK;
 }
 
 // max |v| over `rows` rows of `len` floats at a stride of `stride` floats.  VEC: len, stride multiples of 4 and a 16-byte aligned base

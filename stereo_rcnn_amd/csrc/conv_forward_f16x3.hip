@@ -24,6 +24,10 @@
 // No atomics other than the max words (whose result no order can change), no host read, no device-scope fence: every kernel
 // reads what an earlier kernel of the same stream completed.
 //
+// PREPARED (srcnn_conv2d_forward_f16x3_prepared).  max|w| and the planes are functions of w alone; train_weights.hip computes them
+// for all layers once per step.  The entry binds the caller's planes instead of the workspace's, launches neither absmax_kernel over
+// w nor fwd_weight_split, and its clear (f16x3_clear_scales_prepared) copies the layer's word into amax[1]: the GEMM is unchanged.
+//
 // MAXIMA (srcnn_conv2d_forward_f16x3_maxima).  max|x| is a function of x alone, so a caller that already holds it as a device word
 // (x_amax) spares the pass: the GEMM reads s_x from that word and absmax_kernel is not launched for x.  y_amax is the word the
 // NEXT layer wants: the epilogue of conv_fwd_f16x3_kernel<.., true> keeps fmaxf(mx, |v|) over the values it stores (rows < M,
@@ -151,9 +155,17 @@ static int fwd_prepare(const srcnn_conv_fwd_f16x3_desc *d, FwdArgs &a, FwdPlan &
     return SRCNN_OK;
 }
 
-// The two entries' body.  x_amax / y_amax: the _maxima entry's words (null, null from the plain entry)
-static int fwd_run(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, void *workspace, size_t workspace_bytes,
-                   srcnn_stream_t stream)
+// What srcnn_train_weights_prepare left for the layer (the _prepared entry), or nothing
+struct FwdPrepared {
+    const unsigned *w_amax;
+    const void *w_hi, *w_lo;
+    size_t plane_bytes;
+};
+
+// The three entries' body.  x_amax / y_amax: the _maxima entry's words (null, null from the plain entry); prep: the _prepared
+// entry's word and planes, or null -- then the call scans and splits w itself
+static int fwd_run(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, const FwdPrepared *prep, void *workspace,
+                   size_t workspace_bytes, srcnn_stream_t stream)
 {
     FwdArgs a;
     FwdPlan pl;
@@ -161,6 +173,12 @@ static int fwd_run(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, u
     if (rc != SRCNN_OK) return rc;
     rc = check_amax_words(x_amax, y_amax);
     if (rc != SRCNN_OK) return rc;
+    if (prep) {
+        rc = check_prepared_planes("srcnn_conv2d_forward_f16x3_prepared", prep->w_amax, prep->w_hi, prep->w_lo, prep->plane_bytes,
+                                   (size_t)a.Cp * a.Kw * sizeof(_Float16));
+        if (rc != SRCNN_OK) return rc;
+        SRCNN_REQUIRE_AS("srcnn_conv2d_forward_f16x3_prepared", prep->w_amax != y_amax, "w_amax and y_amax alias: they must be two words");
+    }
     if (!workspace || workspace_bytes < pl.bytes) {
         set_error("srcnn_conv2d_forward_f16x3: workspace too small (%zu < %zu)", workspace ? workspace_bytes : (size_t)0, pl.bytes);
         return SRCNN_ERR_WORKSPACE;
@@ -173,11 +191,20 @@ static int fwd_run(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, u
     a.ymax = y_amax;
 
     hipStream_t st = as_stream(stream);
-    SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, a.amax, a.ymax);
-    launch_absmax(a.w, a.Cout, a.Kw, a.Kw, a.amax + 1, st);
+    if (prep) {
+        // the GEMM reads the caller's planes; const is cast away for FwdArgs' sake, nothing writes them
+        a.w_hi = static_cast<_Float16 *>(const_cast<void *>(prep->w_hi));
+        a.w_lo = static_cast<_Float16 *>(const_cast<void *>(prep->w_lo));
+        SRCNN_LAUNCH(f16x3_clear_scales_prepared, dim3(1), dim3(64), 0, st, a.amax, a.ymax, prep->w_amax);
+    } else {
+        SRCNN_LAUNCH(f16x3_clear_scales, dim3(1), dim3(64), 0, st, a.amax, a.ymax);
+        launch_absmax(a.w, a.Cout, a.Kw, a.Kw, a.amax + 1, st);
+    }
     if (!x_amax) launch_absmax(a.x, a.Min, a.Cin, a.xcs, a.amax, st);
-    const long long groups = (long long)a.Cp * (a.Kw / 4);
-    SRCNN_LAUNCH(fwd_weight_split, dim3((unsigned)min(2048LL, (groups + 255) / 256)), dim3(256), 0, st, a);
+    if (!prep) {
+        const long long groups = (long long)a.Cp * (a.Kw / 4);
+        SRCNN_LAUNCH(fwd_weight_split, dim3((unsigned)min(2048LL, (groups + 255) / 256)), dim3(256), 0, st, a);
+    }
     dispatch_tile_4w(pl.mr, pl.nr, [&](auto mr, auto nr) {
         constexpr int MR = decltype(mr)::value, NR = decltype(nr)::value;
         if (a.ymax) SRCNN_LAUNCH((conv_fwd_f16x3_kernel<MR, NR, true>), dim3(a.mtiles * a.ntiles), dim3(256), 0, st, a);
@@ -201,13 +228,21 @@ size_t srcnn_conv2d_forward_f16x3_workspace_bytes(const srcnn_conv_fwd_f16x3_des
 
 int srcnn_conv2d_forward_f16x3(const srcnn_conv_fwd_f16x3_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
 {
-    return srcnn::fwd_run(d, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return srcnn::fwd_run(d, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 int srcnn_conv2d_forward_f16x3_maxima(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, void *workspace,
                                       size_t workspace_bytes, srcnn_stream_t stream)
 {
-    return srcnn::fwd_run(d, x_amax, y_amax, workspace, workspace_bytes, stream);
+    return srcnn::fwd_run(d, x_amax, y_amax, nullptr, workspace, workspace_bytes, stream);
+}
+
+int srcnn_conv2d_forward_f16x3_prepared(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax, const unsigned *w_amax,
+                                        const void *w_hi, const void *w_lo, size_t plane_bytes, void *workspace, size_t workspace_bytes,
+                                        srcnn_stream_t stream)
+{
+    const srcnn::FwdPrepared prep = {w_amax, w_hi, w_lo, plane_bytes};
+    return srcnn::fwd_run(d, x_amax, y_amax, &prep, workspace, workspace_bytes, stream);
 }
 
 int srcnn_absmax(const float *x, long long rows, int len, long long stride, unsigned *word, srcnn_stream_t stream)

@@ -705,7 +705,7 @@ def _fill_train_geometry(d, cw, B, H, W, OH, OW, x_cstride, y_cstride, y_coffset
 
 
 def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), splits=0, x_cstride=None, y_cstride=None, y_coffset=0,
-                    relu=None, g_out=None, out=None, tile=None, precision='f32', x_amax=None):
+                    relu=None, g_out=None, out=None, tile=None, precision='f32', x_amax=None, prepared=None):
     """Gradients of conv2d(cw, x, ..., precision='f32') (srcnn_conv2d_backward; include/srcnn_hip.h states the sums' orders).
     precision: 'f32', that exact fp32 backward, or 'f16x3', srcnn_conv2d_backward_f16x3 -- the same gradients by the 3 x f16 split
     with per-tensor power-of-two scales found on the device; the one asked for runs, never the other in its place.
@@ -716,8 +716,9 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     to write into instead of fresh tensors (every element is overwritten).  splits: K slices of the weight gradient (0 = the
     library's choice); tile: (tile_mr, tile_nr).  x_amax (precision 'f16x3' only): a 1-element int32 device tensor holding the float
     bits of max |x| over channels [0, Cin) of all B H W pixels (absmax, or a forward's y_amax): the weight gradient's max |x| pass
-    is then not launched (srcnn_conv2d_backward_f16x3_maxima); the gradients keep their bits.  Returns {name: tensor} for the names
-    in want."""
+    is then not launched (srcnn_conv2d_backward_f16x3_maxima); the gradients keep their bits.  prepared (precision 'f16x3' only):
+    the PreparedW prepare_train_weights made from cw.weight: neither the max |w| pass nor the re-layout + split is launched
+    (srcnn_conv2d_backward_f16x3_prepared); the gradients keep their bits.  Returns {name: tensor} for the names in want."""
     L = _lib.lib()
     if precision not in ('f32', 'f16x3'):
         raise ValueError("conv2d_backward: precision must be 'f32' or 'f16x3' (got %r)" % (precision,))
@@ -748,7 +749,17 @@ def conv2d_backward(cw, x, B, H, W, y, dy, OH, OW, want=('dx', 'dw', 'db'), spli
     d.precision = 0 if precision == 'f32' else 1
     nbytes = getattr(L, entry + '_workspace_bytes')(ctypes.byref(d))
     ws = _lib.workspace(nbytes, dy.device, "conv_backward")
-    if x_amax is not None:
+    if prepared is not None:
+        if precision != 'f16x3':
+            raise ValueError("conv2d_backward: prepared belongs to precision 'f16x3'")
+        _check_prepared(prepared, cw)
+        if x_amax is None and 'dw' in want:
+            F16X3_MAXIMA['scans'] += 1
+        _lib.check(L.srcnn_conv2d_backward_f16x3_prepared(ctypes.byref(d), None if x_amax is None else _amax_ptr(x_amax),
+                                                          _amax_ptr(prepared.word), prepared.wt_hi.data_ptr(), prepared.wt_lo.data_ptr(),
+                                                          prepared.plane_bytes, ws.data_ptr(), ws.numel(), _lib.stream()),
+                   entry + '_prepared')
+    elif x_amax is not None:
         _lib.check(L.srcnn_conv2d_backward_f16x3_maxima(ctypes.byref(d), _amax_ptr(x_amax), ws.data_ptr(), ws.numel(), _lib.stream()),
                    entry + '_maxima')
     else:
@@ -786,8 +797,63 @@ def absmax(x, cin=None, x_cstride=None):
     return word
 
 
+class PreparedW(object):
+    """One layer of prepare_train_weights: `weight`, the fp32 (Cout, KH, KW, Cin) tensor the planes were made from (detached); `word`,
+    a 1-element int32 view holding the float bits of max |w|; the forward planes w_hi / w_lo (Cp, KH KW, Cin) and the backward planes
+    wt_hi / wt_lo (Cin, KH KW, Cp), float16, Cp = Cout rounded up to 32; plane_bytes, the bytes of each.  Valid until the weight
+    changes: it is not a cache, whoever changes the weight prepares again."""
+    __slots__ = ('weight', 'word', 'w_hi', 'w_lo', 'wt_hi', 'wt_lo', 'plane_bytes')
+
+    def __init__(self, weight, word, w_hi, w_lo, wt_hi, wt_lo):
+        self.weight, self.word, self.w_hi, self.w_lo, self.wt_hi, self.wt_lo = weight, word, w_hi, w_lo, wt_hi, wt_lo
+        self.plane_bytes = w_hi.numel() * 2
+
+
+def _check_prepared(prepared, cw):
+    if prepared.weight.data_ptr() != cw.weight.data_ptr() or tuple(prepared.weight.shape) != (cw.cout, cw.kh, cw.kw, cw.cin):
+        raise ValueError("prepared: the planes were not made from this weight tensor (%s at %#x)"
+                         % (tuple(prepared.weight.shape), prepared.weight.data_ptr()))
+
+
+def prepare_train_weights(weights, workspace=None):
+    """max |w| and the f16x3 hi / lo planes of a LIST of weights in one srcnn_train_weights_prepare call (csrc/train_weights.hip): a
+    fixed, small number of launches whatever the list's length, nothing read by the host.  weights: contiguous float32 device
+    tensors (Cout, KH, KW, Cin) in the engine's layout, BN already folded, Cin a multiple of 32 -- what conv2d_train_f16x3 and
+    conv2d_backward take as cw.weight.  Returns one PreparedW per weight for their `prepared=`.  The words of the whole list are one
+    int32 tensor and the planes one float16 tensor, carved at 256-byte steps.  workspace: a uint8 device tensor of at least
+    srcnn_train_weights_workspace_bytes(len(weights)) bytes for the call's table (default: the shared grow-only scratch)."""
+    L = _lib.lib()
+    weights = [w.detach() for w in weights]
+    if not weights:
+        raise ValueError("prepare_train_weights: an empty list")
+    dev = weights[0].device
+    sizes = []
+    for w in weights:
+        assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous(), "contiguous float32 (Cout, KH, KW, Cin) device tensors"
+        cout, kh, kw, cin = (int(v) for v in w.shape)
+        sizes.append(-(-((cout + 31) // 32 * 32 * kh * kw * cin) // 128) * 128)          # halves of one plane, rounded up to 256 bytes
+    words = torch.empty(64 * len(weights), dtype=torch.int32, device=dev)               # one word per 256 bytes: no two layers share a line
+    planes = torch.empty(4 * sum(sizes), dtype=torch.float16, device=dev)
+    descs = (_lib.TrainWeightDesc * len(weights))()
+    out, off = [], 0
+    for i, (w, n) in enumerate(zip(weights, sizes)):
+        cout, kh, kw, cin = (int(v) for v in w.shape)
+        numel = (cout + 31) // 32 * 32 * kh * kw * cin
+        p = PreparedW(w, words[64 * i:64 * i + 1], *(planes[off + j * n:off + j * n + numel] for j in range(4)))
+        off += 4 * n
+        d = descs[i]
+        d.w, d.w_amax = w.data_ptr(), p.word.data_ptr()
+        d.w_hi, d.w_lo, d.wt_hi, d.wt_lo = p.w_hi.data_ptr(), p.w_lo.data_ptr(), p.wt_hi.data_ptr(), p.wt_lo.data_ptr()
+        d.Cout, d.KH, d.KW, d.Cin = cout, kh, kw, cin
+        out.append(p)
+    nbytes = L.srcnn_train_weights_workspace_bytes(len(weights))
+    ws = _lib.workspace(nbytes, dev, "train_weights") if workspace is None else workspace
+    _lib.check(L.srcnn_train_weights_prepare(descs, len(weights), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_train_weights_prepare")
+    return out
+
+
 def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None, y_cstride=None, y_coffset=0, relu=None, tile=None,
-                       x_amax=None, y_amax=None):
+                       x_amax=None, y_amax=None, prepared=None):
     """The training forward on the f16 matrix pipe (srcnn_conv2d_forward_f16x3): y = relu?(conv(x, w) + bias + residual) by the 3 x f16
     split with one power-of-two scale for x and one for w, both found on the device inside the call -- the scheme of
     conv2d_backward(precision='f16x3').  cw: an engine.ConvW holding the plain fp32 weights (Cout, KH, KW, Cin) (BN folded) and
@@ -796,7 +862,9 @@ def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None,
     engine, and never runs in its place or lets it run in its own.
     x_amax / y_amax: 1-element int32 device tensors (float bits), never slices of the shared workspace.  x_amax, when given, is
     max |x| over channels [0, Cin) of all B H W pixels and replaces the call's own pass over x; y_amax, when given, is overwritten
-    with max |y| over exactly what the call stores (srcnn_conv2d_forward_f16x3_maxima).  y keeps its bits either way."""
+    with max |y| over exactly what the call stores (srcnn_conv2d_forward_f16x3_maxima).  prepared: the PreparedW
+    prepare_train_weights made from cw.weight -- the call then launches neither its max |w| pass nor its weight split
+    (srcnn_conv2d_forward_f16x3_prepared).  y keeps its bits either way."""
     L = _lib.lib()
     assert cw.mode == 0 and cw.cin2 == 0, "only plain convolutions have a training forward"
     d = _lib.ConvFwdF16x3Desc()
@@ -807,7 +875,13 @@ def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None,
     ws = _lib.workspace(L.srcnn_conv2d_forward_f16x3_workspace_bytes(ctypes.byref(d)), x.device, "conv_forward_f16x3")
     if x_amax is None:
         F16X3_MAXIMA['scans'] += 1
-    if x_amax is None and y_amax is None:
+    if prepared is not None:
+        _check_prepared(prepared, cw)
+        _lib.check(L.srcnn_conv2d_forward_f16x3_prepared(ctypes.byref(d), None if x_amax is None else _amax_ptr(x_amax),
+                                                         None if y_amax is None else _amax_ptr(y_amax), _amax_ptr(prepared.word),
+                                                         prepared.w_hi.data_ptr(), prepared.w_lo.data_ptr(), prepared.plane_bytes,
+                                                         ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_forward_f16x3_prepared")
+    elif x_amax is None and y_amax is None:
         _lib.check(L.srcnn_conv2d_forward_f16x3(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d_forward_f16x3")
     else:
         _lib.check(L.srcnn_conv2d_forward_f16x3_maxima(ctypes.byref(d), None if x_amax is None else _amax_ptr(x_amax),

@@ -83,18 +83,26 @@ LOSS_NAMES = ('rpn_loss_cls', 'rpn_loss_bbox_left_right', 'RCNN_loss_cls', 'RCNN
 
 
 def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, backward_precision='f32', forward_precision='f32',
-               reuse_maxima=True):
+               reuse_maxima=True, prepared_weights=False):
     """One iteration of trainval_net.py:207-227.  batch: forward_train's nine inputs (im_left, im_right, im_info, gt_boxes_left,
     gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes).  Gradients are set to None, forward_train and
     losses.multi_task_loss build the total, backward() fills the gradients, and optimizer.step clips the MODEL's gradients to
     `clip_norm` (uncert's stays as it is, as in the reference) inside the fused update.  backward_precision, forward_precision,
-    reuse_maxima: forward_train's.  Returns device scalars: 'loss', the six
+    reuse_maxima: forward_train's.  prepared_weights: True builds a TrainWeights for the model (kept on the optimiser and reused)
+    and calls its prepare() at the start of EVERY step -- never a cache keyed on a version counter: optimizer.step writes the
+    parameters through raw pointers, which torch's counter does not see.  Returns device scalars: 'loss', the six
     terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0]."""
     optimizer.zero_grad(set_to_none=True)
     for p in model.parameters():
         p.grad = None
+    weights = None
+    if prepared_weights:
+        weights = getattr(optimizer, '_train_weights', None)
+        if weights is None or weights.model is not model:
+            weights = optimizer._train_weights = TrainWeights(model)
+        weights.prepare()
     out = forward_train(model, *batch, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision,
-                        reuse_maxima=reuse_maxima)
+                        reuse_maxima=reuse_maxima, weights=weights)
     terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
     total = losses.multi_task_loss(terms, uncert)
     total.backward()
@@ -119,18 +127,89 @@ class _Taps(object):
         return t
 
 
-def _conv(m, x, prec, relu=False, residual=None, bn=None):
+def _conv(m, x, prec, relu=False, residual=None, bn=None, weights=None):
     return autograd.conv2d_nhwc(x, m.weight, m.bias, int(m.stride[0]), int(m.padding[0]), relu, residual, None if bn is None else _bn(bn),
-                                _prec=prec)
+                                _prec=prec, prepared=None if weights is None else weights[m])
 
 
-def _bottleneck(blk, x, name, tap, prec):
+def _bottleneck(blk, x, name, tap, prec, weights=None):
     """resnet.py:66-100: relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1(x)))))))) + shortcut(x)), the ReLUs and the residual fused
     into the convolutions as the engine fuses them."""
-    t = tap(name + '.conv1', _conv(blk.conv1, x, prec, True, bn=blk.bn1))
-    t = tap(name + '.conv2', _conv(blk.conv2, t, prec, True, bn=blk.bn2))
-    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, prec, False, bn=blk.downsample[1])
-    return tap(name + '.out', _conv(blk.conv3, t, prec, True, residual=res, bn=blk.bn3))
+    t = tap(name + '.conv1', _conv(blk.conv1, x, prec, True, bn=blk.bn1, weights=weights))
+    t = tap(name + '.conv2', _conv(blk.conv2, t, prec, True, bn=blk.bn2, weights=weights))
+    res = x if not hasattr(blk, 'downsample') else _conv(blk.downsample[0], x, prec, False, bn=blk.downsample[1], weights=weights)
+    return tap(name + '.out', _conv(blk.conv3, t, prec, True, residual=res, bn=blk.bn3, weights=weights))
+
+
+def _rpn_head(rpn):
+    return (torch.cat((rpn.RPN_cls_score.weight, rpn.RPN_bbox_pred_left_right.weight), 0),
+            torch.cat((rpn.RPN_cls_score.bias, rpn.RPN_bbox_pred_left_right.bias), 0))
+
+
+def _top0_weight(top0):
+    return top0.weight.permute(0, 2, 3, 1).reshape(int(top0.weight.shape[0]), -1)          # (2048, (kh, kw, c)): the NHWC window
+
+
+def _box_heads(model):
+    return (torch.cat((model.RCNN_bbox_pred.weight, model.RCNN_dim_orien_pred.weight, model.RCNN_cls_score.weight), 0),
+            torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0))
+
+
+class TrainWeights(object):
+    """Every weight forward_train's graph layers use, folded and prepared for the f16x3 engine ONCE per step: prepare() enumerates
+    exactly the (weight, bias, bn) combinations forward_train composes -- the bottleneck convolutions of the stages with a graph
+    (their frozen BNs folded by autograd's own fold, inside the graph), the FPN layers, RPN_Conv, the concatenated RPN head, RCNN_top[0]'s
+    permuted view and RCNN_top[3], the concatenated box heads, the keypoint tower, its deconvolution in row order (i, j, co) and
+    kpts_class -- and then makes one engine.prepare_train_weights call over all of them (csrc/train_weights.hip: max |w| and the
+    four hi / lo planes of every layer in a fixed number of launches).  weights[key] is the autograd.PreparedLayer: key is the
+    module for a plain convolution, 'rpn_head', 'RCNN_top.0', 'RCNN_top.3', 'box_heads', 'RCNN_kpts.12' otherwise.  The folded
+    weights carry the graph, so prepare() belongs to ONE forward_train + backward: call it at the start of every step, after the
+    optimiser's update (train_step(prepared_weights=True) does).  The fold and the re-layout stay eager torch operators."""
+
+    def __init__(self, model):
+        self.model = model
+        self.layers = {}
+
+    def __getitem__(self, key):
+        return self.layers[key]
+
+    def enumerate(self):
+        """[(key, folded w, folded b)] in forward_train's order of first use."""
+        model, A = self.model, autograd
+        for p in trainable_parameters(model).values():
+            p.requires_grad_(True)
+        out = []
+        for li in (1, 2, 3, 4):
+            if li <= cfg.RESNET.FIXED_BLOCKS:
+                continue
+            for blk in getattr(model, 'RCNN_layer%d' % li)[0]:
+                pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
+                if hasattr(blk, 'downsample'):
+                    pairs.append((blk.downsample[0], blk.downsample[1]))
+                pairs.append((blk.conv3, blk.bn3))
+                out += [(m,) + A.fold_conv(m.weight, m.bias, _bn(bn)) for m, bn in pairs]
+        rpn = model.RCNN_rpn
+        for m in (model.RCNN_toplayer, model.RCNN_latlayer1, model.RCNN_smooth1, model.RCNN_latlayer2, model.RCNN_smooth2,
+                  model.RCNN_latlayer3, model.RCNN_smooth3, rpn.RPN_Conv):
+            out.append((m,) + A.fold_conv(m.weight, m.bias))
+        out.append(('rpn_head',) + A.fold_conv(*_rpn_head(rpn)))
+        top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
+        out.append(('RCNN_top.0',) + A.fold_linear(_top0_weight(top0), top0.bias))
+        out.append(('RCNN_top.3',) + A.fold_linear(top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias))
+        out.append(('box_heads',) + A.fold_linear(*_box_heads(model)))
+        for i in (0, 2, 4, 6, 8, 10):
+            m = model.RCNN_kpts[i]
+            out.append((m,) + A.fold_conv(m.weight, m.bias))
+        up = model.RCNN_kpts[12]
+        out.append(('RCNN_kpts.12',) + A.fold_deconv2x2(up.weight, up.bias))
+        out.append((model.kpts_class,) + A.fold_conv(model.kpts_class.weight, model.kpts_class.bias))
+        return out
+
+    def prepare(self):
+        folded = [(key, w.contiguous(), b) for key, w, b in self.enumerate()]
+        planes = engine.prepare_train_weights([w for _, w, _ in folded])
+        self.layers = {key: autograd.PreparedLayer(w, b, p) for (key, w, b), p in zip(folded, planes)}
+        return self
 
 
 def _stem(model, im_left, im_right):
@@ -201,7 +280,7 @@ def _dropout(x, generator, tap, name):
 
 
 def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes,
-                  generator=None, taps=None, backward_precision='f32', forward_precision='f32', reuse_maxima=True):
+                  generator=None, taps=None, backward_precision='f32', forward_precision='f32', reuse_maxima=True, weights=None):
     """The reference's training forward (stereo_rcnn.py:141-324).  model: a _StereoRCNN on the GPU; images (B, 3, H, W) on the
     same device; im_info (B, 3) (CPU or device), ground truth as the reference's data loader gives it.  Returns (rois_left,
     rois_right, cls_prob, bbox_pred, dim_orien_pred, kpts_prob, left_border_prob, right_border_prob, rpn_loss_cls,
@@ -216,7 +295,13 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     layers; RCNN_layer0 and the first cfg.RESNET.FIXED_BLOCKS stages, which have no graph, stay on the fp32 engine.  The two are
     independent.  reuse_maxima (default True; it matters only where a precision is 'f16x3'): each activation's max |x| is found at
     most once -- in the epilogue of the f16x3 convolution that produced it, or by one scan -- and handed to every f16x3 call that
-    consumes it (stereo_rcnn_amd.autograd); every output and gradient keeps its bits."""
+    consumes it (stereo_rcnn_amd.autograd); every output and gradient keeps its bits.  Either precision may be 'auto':
+    autograd.choose_engine picks the engine per layer and direction from the layer's GEMM size (the frozen stages stay fp32);
+    `with autograd.record_engines() as log:` around the call receives (M, N, K, forward engine, backward engine) of every
+    convolution call in call order.  weights: a
+    TrainWeights(model) whose prepare() ran for THIS call (after the last optimiser update): the layers take their folded weights
+    and their f16x3 planes from it and the f16x3 calls launch no pass over a weight; layers on the fp32 engine ignore the planes.
+    It composes with every precision and changes no bit."""
     prec = autograd.Precision(forward_precision, backward_precision, reuse_maxima)
     dev = model.RCNN_toplayer.weight.device
     if dev.type != 'cuda' or not im_left.is_cuda:
@@ -241,30 +326,32 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         frozen = li <= cfg.RESNET.FIXED_BLOCKS
         with (torch.no_grad() if frozen else contextlib.nullcontext()):
             for b, blk in enumerate(getattr(model, 'RCNN_layer%d' % li)[0]):
-                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, prec.without_graph() if frozen else prec)
+                x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, prec.without_graph() if frozen else prec,
+                                None if frozen else weights)
         c.append(x)
     c2, c3, c4, c5 = c
 
     # ---- top-down (:161-168, 178-185)
-    p5 = _conv(model.RCNN_toplayer, c5, prec)
-    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, prec)), prec)
-    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, prec)), prec)
-    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, prec)), prec)
+    wts = weights
+    prepared = (lambda key: None) if wts is None else wts.__getitem__
+    p5 = _conv(model.RCNN_toplayer, c5, prec, weights=wts)
+    p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, prec, weights=wts)), prec, weights=wts)
+    p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, prec, weights=wts)), prec, weights=wts)
+    p2 = _conv(model.RCNN_smooth3, autograd.upsample_add(p3, _conv(model.RCNN_latlayer3, c2, prec, weights=wts)), prec, weights=wts)
     p6 = autograd.subsample2(p5)
     levels = [p2, p3, p4, p5, p6]
     shapes = [(int(p.shape[1]), int(p.shape[2])) for p in levels]
 
     # ---- stereo RPN (stereo_rpn.py:73-95)
     rpn = model.RCNN_rpn
-    head_w = torch.cat((rpn.RPN_cls_score.weight, rpn.RPN_bbox_pred_left_right.weight), 0)
-    head_b = torch.cat((rpn.RPN_cls_score.bias, rpn.RPN_bbox_pred_left_right.bias), 0)
+    head_w, head_b = _rpn_head(rpn)
     n_anchors = sum(3 * h * w for h, w in shapes)
     probs = torch.empty((B, n_anchors, 2), dtype=torch.float32, device=dev)
     deltas = torch.empty((B, n_anchors, 6), dtype=torch.float32, device=dev)
     scores, bbox_preds, off = [], [], 0
     for l, (p, (h, w)) in enumerate(zip(levels, shapes)):
-        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, prec, True))                  # (2B, h, w, 512): left images, then right
-        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, _prec=prec)    # [cls 6 | bbox 18] per pixel
+        r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, prec, True, weights=wts))     # (2B, h, w, 512): left images, then right
+        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, _prec=prec, prepared=prepared('rpn_head'))  # [cls 6 | bbox 18]
         # :89,91: NHWC rows viewed as (-1, 2) / (-1, 6) -- the raw scores pair channels (0, 1) (2, 3) (4, 5)
         scores.append(hd[..., :6].reshape(B, h * w * 3, 2))
         bbox_preds.append(hd[..., 6:].reshape(B, h * w * 3, 6))
@@ -302,24 +389,25 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     left_maps, right_maps = [p[:B] for p in levels[:4]], [p[B:] for p in levels[:4]]
     feat = _roi_feat([left_maps, right_maps], [rois_left, rois_right], im_height, cfg.POOLING_SIZE)
     top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
-    w0 = top0.weight.permute(0, 2, 3, 1).reshape(int(top0.weight.shape[0]), -1)          # (2048, (kh, kw, c)): the NHWC window
-    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), w0, top0.bias, relu=True, _prec=prec))
+    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), _top0_weight(top0), top0.bias, relu=True, _prec=prec,
+                                          prepared=prepared('RCNN_top.0')))
     t = _dropout(t, generator, tap, 'dropout1')
-    t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True, _prec=prec))
+    t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True, _prec=prec,
+                                          prepared=prepared('RCNN_top.3')))
     t = _dropout(t, generator, tap, 'dropout2')                                           # .mean(3).mean(2) over a 1x1 map
     n_bbox, n_dim = int(model.RCNN_bbox_pred.weight.shape[0]), int(model.RCNN_dim_orien_pred.weight.shape[0])
-    fc = autograd.linear(t, torch.cat((model.RCNN_bbox_pred.weight, model.RCNN_dim_orien_pred.weight, model.RCNN_cls_score.weight), 0),
-                         torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0), _prec=prec)
+    fc = autograd.linear(t, *_box_heads(model), _prec=prec, prepared=prepared('box_heads'))
     bbox_all, dim_all, cls_score = fc[:, :n_bbox], fc[:, n_bbox:n_bbox + n_dim], fc[:, n_bbox + n_dim:]
     cls_prob = F.softmax(cls_score, 1)
 
     # ---- keypoint head (:260-271)
     k = _roi_feat([left_maps], [rois_left], im_height, cfg.POOLING_SIZE * 2)
     for i in (0, 2, 4, 6, 8, 10):
-        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, prec, True))
+        k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, prec, True, weights=wts))
     up = model.RCNN_kpts[12]
-    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, _prec=prec))
-    kpts_pred_all = _conv(model.kpts_class, k, prec).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
+    k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, _prec=prec,
+                                                               prepared=prepared('RCNN_kpts.12')))
+    kpts_pred_all = _conv(model.kpts_class, k, prec, weights=wts).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
     G = cfg.KPTS_GRID
     kpts_prob = F.softmax(kpts_pred_all[:, :4, :].reshape(n, 4 * G), 1)
     left_border_prob = F.softmax(kpts_pred_all[:, 4, :], 1)

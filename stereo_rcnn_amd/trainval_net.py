@@ -18,6 +18,10 @@ is bit-identical with and without it.
 every convolution / linear layer that has a graph (training.train_step's forward_precision; srcnn_conv2d_forward_f16x3).
 --no-reuse-maxima: with an f16x3 precision, every call finds max |x| of its input itself (training.train_step's
 reuse_maxima=False); by default each activation's maximum is found once and handed on.  The results are bit-identical.
+Either precision also takes `auto`: autograd.choose_engine picks f32 or f16x3 per layer and direction from the layer's GEMM size.
+--prepared-weights (logged in trainlog.txt only when set): max |w| and the f16x3 planes of every layer's weight are prepared once
+at the start of each step, in one call (training.train_step's prepared_weights=True); the f16x3 calls then launch no pass over
+a weight.  The results are bit-identical.
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -59,11 +63,14 @@ def parse_args(argv=None):
     p.add_argument('--val-label-dir', dest='val_label_dir', default=None, help='KITTI label_2 directory of the validation frames')
     p.add_argument('--val-every', dest='val_every', default=1, type=int, help='unit: epoch')
     p.add_argument('--val-precision', dest='val_precision', choices=['f16x3', 'f32'], default='f16x3')
-    p.add_argument('--backward-precision', dest='backward_precision', choices=['f32', 'f16x3'], default='f32',
+    p.add_argument('--backward-precision', dest='backward_precision', choices=['f32', 'f16x3', 'auto'], default='f32',
                    help='engine of the convolution gradients: the exact fp32 backward, or the 3 x f16 split (independent of --forward-precision)')
-    p.add_argument('--forward-precision', dest='forward_precision', choices=['f32', 'f16x3'], default='f32',
+    p.add_argument('--forward-precision', dest='forward_precision', choices=['f32', 'f16x3', 'auto'], default='f32',
                    help='engine of the training forward of the layers that have a graph: the exact fp32 engine, or the 3 x f16 split '
                         'with scales found on the device')
+    p.add_argument('--prepared-weights', dest='prepared_weights', action='store_true',
+                   help="prepare max |w| and the f16x3 planes of every layer's weight once per step, in one call, instead of inside "
+                        "every f16x3 convolution call (bit-identical results)")
     p.add_argument('--no-reuse-maxima', dest='reuse_maxima', action='store_false',
                    help="f16x3 precisions only: let every convolution call scan its input for max |x| itself instead of taking it from "
                         "the call that produced the tensor (same bits either way)")
@@ -104,6 +111,8 @@ def main(argv=None):
     log_string('backward precision: %s' % args.backward_precision)
     if args.forward_precision != 'f32':
         log_string('forward precision: %s' % args.forward_precision)
+    if args.prepared_weights:
+        log_string('prepared weights: once per step')
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
@@ -148,7 +157,7 @@ def main(argv=None):
                     break
                 res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
                                           backward_precision=args.backward_precision, forward_precision=args.forward_precision,
-                                          reuse_maxima=args.reuse_maxima)
+                                          reuse_maxima=args.reuse_maxima, prepared_weights=args.prepared_weights)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))
