@@ -16,7 +16,7 @@ the arguments the header names *_host, and those `_HOST_ARRAYS` lists.  What the
 EXTENSIONS: further headers of include/ that declare entries of the same library on top of srcnn_hip.h's types (they #include it).
 Each is parsed the same way with srcnn_hip.h's structures and handle types known; its constants and structures become attributes
 of this module like the main header's, and its signatures are bound by lib() with them.  HEADER, _SIGNATURES and
-declared_symbols() stay what srcnn_hip.h alone declares; extension_symbols() lists the rest.
+declared_symbols() stay what srcnn_hip.h alone declares; extension_symbols(header) lists what one extension header adds.
 """
 import collections
 import ctypes
@@ -170,7 +170,7 @@ globals().update(HEADER.constants)                                      # FMT_F3
 globals().update((s.__name__, s) for s in HEADER.structs.values())      # ConvDesc, ConvBwdDesc, KittiSplit, PrepLayer, ...
 _SIGNATURES = HEADER.signatures
 
-EXTENSIONS = ("srcnn_train_weights.h",)         # include/: headers on top of srcnn_hip.h (the module docstring)
+EXTENSIONS = ("srcnn_train_weights.h", "srcnn_train_fold.h")        # include/: headers on top of srcnn_hip.h (the module docstring)
 
 
 def _read_extensions():
@@ -193,7 +193,7 @@ EXTENSION_HEADERS = _read_extensions()
 _EXTENSION_SIGNATURES = collections.OrderedDict((k, v) for h in EXTENSION_HEADERS.values() for k, v in h.signatures.items())
 for _h in EXTENSION_HEADERS.values():
     globals().update(_h.constants)
-    globals().update((s.__name__, s) for s in _h.structs.values())                  # TrainWeightDesc
+    globals().update((s.__name__, s) for s in _h.structs.values())                  # TrainWeightDesc, TrainFoldDesc
 
 _lib = None
 
@@ -202,8 +202,9 @@ def declared_symbols():
     return sorted(_SIGNATURES)
 
 
-def extension_symbols():
-    return sorted(_EXTENSION_SIGNATURES)
+def extension_symbols(header=EXTENSIONS[0]):
+    """The entries ONE extension header declares (default: the first extension, srcnn_train_weights.h)."""
+    return sorted(EXTENSION_HEADERS[header].signatures)
 
 
 def lib():

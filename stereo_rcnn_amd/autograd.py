@@ -36,6 +36,11 @@ them for a list of folded weights in one call (csrc/train_weights.hip); a Prepar
 the graph), bias and planes, and a function given it launches no pass over the weight in either direction.  The bits do not change.
 Nothing here caches across optimiser steps: optim.SGD writes parameters through raw pointers, which no version counter sees, so
 whoever steps prepares again (stereo_rcnn_amd.training.TrainWeights).
+
+fold_all.  fold_conv / fold_linear / fold_deconv2x2 are torch operators per layer (a float64 fold, a permute().contiguous(), a
+torch.cat) with their autograd nodes.  fold_all(specs) is the same for a whole list of layers as ONE node over two library calls
+(csrc/train_fold.hip: the fold and its adjoint, include/srcnn_train_fold.h), with the same bits in both directions;
+TrainWeights.prepare(device_fold=True) uses it.
 """
 import collections
 import weakref
@@ -314,6 +319,65 @@ def fold_deconv2x2(weight, bias=None):
     """conv_transpose2x2's: weight (Cin, Cout, 2, 2) -> (4 Cout, 1, 1, Cin) in row order (i, j, co), the bias four times."""
     cin, cout = int(weight.shape[0]), int(weight.shape[1])
     return weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin), None if bias is None else bias.repeat(4)
+
+
+class _FoldAll(torch.autograd.Function):
+    """fold_all's node: inputs, per layer and part, the weight and (where there is one) the bias, then every frozen BN tensor;
+    outputs, per layer, the folded w and (where there is one) the folded b.  A b that is a BN's shift alone depends on no
+    parameter: it is marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, specs, *tensors):
+        ctx.set_materialize_grads(False)
+        ctx.specs, ctx.n_inputs = specs, len(tensors)
+        flat, constant = [], []
+        for s, (w, b) in zip(specs, engine.fold_train_weights(specs)):
+            flat.append(w)
+            if b is not None:
+                flat.append(b)
+                if s.parts[0][1] is None:
+                    constant.append(b)
+        ctx.mark_non_differentiable(*constant)
+        return tuple(flat)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        grads = iter(grads)
+        dws, dbs = [], []
+        for s in ctx.specs:
+            dw, db = next(grads), next(grads) if s.has_b else None
+            dws.append(None if dw is None else dw.contiguous())
+            dbs.append(None if db is None or s.parts[0][1] is None else db.contiguous())
+        out = [None]                                            # specs
+        if any(g is not None for g in dws + dbs):
+            for s, (gws, gbs) in zip(ctx.specs, engine.fold_train_weights_backward(ctx.specs, dws, dbs)):
+                for (_, b), gw, gb in zip(s.parts, gws, gbs):
+                    out += [gw] if b is None else [gw, gb]
+        return tuple(out) + (None,) * (1 + ctx.n_inputs - len(out))        # no gradient at all / the frozen BN tensors
+
+
+def fold_all(specs):
+    """fold_conv / fold_linear / fold_deconv2x2 + .contiguous() of a whole list of layers as ONE graph node over two library calls
+    (engine.fold_train_weights forward, engine.fold_train_weights_backward for all gradients at once; csrc/train_fold.hip).
+    specs: engine.FoldSpec's over the PARAMETERS.  Returns [(w, b or None)] per layer: contiguous, in the engine's layout, inside
+    the graph, with the bits of the eager folds; so are the gradients that reach the parameters.  A parameter none of whose
+    folded tensors received a gradient gets None; the frozen BN tensors get None.  The one operator left to torch is a
+    deconvolution's bias: b = bias.repeat(4), whose adjoint is a four-term float sum in an order torch does not document."""
+    specs = list(specs)
+    inner, tensors, bns = [], [], []
+    for s in specs:
+        deconv_bias = s.kind == 'deconv2x2' and s.parts[0][1] is not None
+        inner.append(engine.FoldSpec(s.kind, [(s.parts[0][0], None)]) if deconv_bias else s)
+        for w, b in inner[-1].parts:
+            tensors += [w] if b is None else [w, b]
+        bns += [] if s.bn is None else [s.bn[k] for k in ('weight', 'bias', 'running_mean', 'running_var')]
+    flat = iter(_FoldAll.apply(inner, *(tensors + bns)))
+    out = []
+    for s, i in zip(specs, inner):
+        w = next(flat)
+        b = next(flat) if i.has_b else (s.parts[0][1].repeat(4) if s.has_b else None)
+        out.append((w, b))
+    return out
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, residual=None, bn=None, backward_precision='f32', forward_precision='f32',

@@ -852,6 +852,106 @@ def prepare_train_weights(weights, workspace=None):
     return out
 
 
+class FoldSpec(object):
+    """One layer of fold_train_weights: kind, 'conv' (parts (rows, Cin, KH, KW) -> (Cout, KH, KW, Cin)), 'linear' ((rows, K) ->
+    (Cout, 1, 1, K)) or 'deconv2x2' ((Cin, Cout, 2, 2) -> (4 Cout, 1, 1, Cin), row order (i, j, co)); parts, one to three
+    (weight, bias or None) pairs concatenated along the output rows; bn, the frozen BatchNorm's dict ('weight', 'bias',
+    'running_mean', 'running_var') or None.  The tensors are the PARAMETERS as the modules hold them: contiguous float32 on the
+    device.  shape: the folded weight's; has_b: whether a folded bias exists."""
+    __slots__ = ('kind', 'parts', 'bn', 'shape', 'has_b')
+    KINDS = ('conv', 'linear', 'deconv2x2')
+
+    def __init__(self, kind, parts, bn=None):
+        if kind not in self.KINDS:
+            raise ValueError("FoldSpec: kind must be one of %s (got %r)" % (', '.join(self.KINDS), kind))
+        parts = tuple((w, b) for w, b in parts)
+        if not parts:
+            raise ValueError("FoldSpec: no parts")
+        for t in [w for w, _ in parts] + [b for _, b in parts if b is not None] + list((bn or {}).values()):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "contiguous float32 device tensors"
+        w0 = parts[0][0]
+        assert all(w.dim() == w0.dim() and w.shape[1:] == w0.shape[1:] for w, _ in parts), "the parts differ in more than their rows"
+        assert w0.dim() == (2 if kind == 'linear' else 4), "conv / deconv2x2 weights are 4-d, linear weights 2-d"
+        rows = sum(int(w.shape[0]) for w, _ in parts)
+        if kind == 'deconv2x2':
+            self.shape = (4 * int(w0.shape[1]), 1, 1, int(w0.shape[0]))
+        elif kind == 'linear':
+            self.shape = (rows, 1, 1, int(w0.shape[1]))
+        else:
+            self.shape = (rows, int(w0.shape[2]), int(w0.shape[3]), int(w0.shape[1]))
+        self.kind, self.parts, self.bn = kind, parts, bn
+        self.has_b = bn is not None or parts[0][1] is not None
+
+
+def _fold_descs(specs):
+    specs = list(specs)
+    if not specs:
+        raise ValueError("fold_train_weights: an empty list")
+    descs = (_lib.TrainFoldDesc * len(specs))()
+    for d, s in zip(descs, specs):
+        d.kind = FoldSpec.KINDS.index(s.kind)                   # _lib.TRAIN_FOLD_CONV, _LINEAR, _DECONV2X2: 0, 1, 2
+        d.n_parts = len(s.parts)
+        for p, (w, b) in enumerate(s.parts[:3]):
+            d.w[p], d.bias[p], d.rows[p] = w.data_ptr(), None if b is None else b.data_ptr(), int(w.shape[1 if s.kind == 'deconv2x2' else 0])
+        if s.bn is not None:
+            d.bn_weight, d.bn_bias = s.bn['weight'].data_ptr(), s.bn['bias'].data_ptr()
+            d.bn_mean, d.bn_var = s.bn['running_mean'].data_ptr(), s.bn['running_var'].data_ptr()
+        rows, d.KH, d.KW, d.Cin = s.shape
+        d.Cout = rows // 4 if s.kind == 'deconv2x2' else rows
+        if s.kind == 'deconv2x2':
+            d.KH = d.KW = 2
+    return specs, descs
+
+
+def fold_train_weights(specs, workspace=None):
+    """Every layer's folded weight in the engine's layout and its folded bias in ONE srcnn_train_weights_fold call
+    (csrc/train_fold.hip, include/srcnn_train_fold.h): what autograd.fold_conv / fold_linear / fold_deconv2x2 + .contiguous() (and
+    torch.cat for several parts) compute, bit for bit, in a fixed number of launches.  specs: FoldSpec's.  Returns [(w, b or None)],
+    fresh tensors without a graph (autograd.fold_all is the differentiable form).  workspace: prepare_train_weights's, of
+    srcnn_train_fold_workspace_bytes(len(specs)) bytes."""
+    L = _lib.lib()
+    specs, descs = _fold_descs(specs)
+    dev = specs[0].parts[0][0].device
+    out = []
+    for d, s in zip(descs, specs):
+        w = torch.empty(s.shape, dtype=torch.float32, device=dev)
+        b = torch.empty(s.shape[0], dtype=torch.float32, device=dev) if s.has_b else None
+        d.dst_w, d.dst_b = w.data_ptr(), None if b is None else b.data_ptr()
+        out.append((w, b))
+    ws = _lib.workspace(L.srcnn_train_fold_workspace_bytes(len(specs)), dev, "train_fold") if workspace is None else workspace
+    _lib.check(L.srcnn_train_weights_fold(descs, len(specs), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_train_weights_fold")
+    return out
+
+
+def fold_train_weights_backward(specs, dws, dbs, workspace=None):
+    """The adjoint of fold_train_weights in ONE srcnn_train_weights_fold_backward call.  dws / dbs: per layer the gradient of the
+    folded weight / bias (contiguous float32, the folded tensor's shape) or None.  Returns per layer ([dw of each part], [db of each
+    part]) in the parameters' own shapes, contiguous; None where nothing arrived (a None dw: every part's weight; a None db, or a layer
+    without a convolution bias: every part's bias -- a frozen BN's tensors receive nothing).  A deconvolution's db is refused: its
+    bias stays the caller's bias.repeat(4) (include/srcnn_train_fold.h)."""
+    L = _lib.lib()
+    specs, descs = _fold_descs(specs)
+    dws, dbs = list(dws), list(dbs)
+    assert len(dws) == len(specs) and len(dbs) == len(specs), "one dw and one db (or None) per layer"
+    dev = specs[0].parts[0][0].device
+    out = []
+    for d, s, dw, db in zip(descs, specs, dws, dbs):
+        for g, shape in ((dw, s.shape), (db, s.shape[:1])):
+            assert g is None or (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == tuple(shape)), \
+                "contiguous float32 device gradients of the folded tensors' shapes"
+        gws = [None if dw is None else torch.empty_like(w) for w, _ in s.parts]
+        gbs = [None if db is None or b is None else torch.empty_like(b) for _, b in s.parts]
+        for p in range(min(len(s.parts), 3)):
+            d.grad_w[p] = None if gws[p] is None else gws[p].data_ptr()
+            d.grad_b[p] = None if gbs[p] is None else gbs[p].data_ptr()
+        out.append((gws, gbs))
+    ptrs = lambda gs: (_lib.c_void_p * len(gs))(*[None if g is None else g.data_ptr() for g in gs])
+    ws = _lib.workspace(L.srcnn_train_fold_workspace_bytes(len(specs)), dev, "train_fold_backward") if workspace is None else workspace
+    _lib.check(L.srcnn_train_weights_fold_backward(descs, len(specs), ptrs(dws), ptrs(dbs), ws.data_ptr(), ws.numel(), _lib.stream()),
+               "srcnn_train_weights_fold_backward")
+    return out
+
+
 def conv2d_train_f16x3(cw, x, B, H, W, y, OH, OW, residual=None, x_cstride=None, y_cstride=None, y_coffset=0, relu=None, tile=None,
                        x_amax=None, y_amax=None, prepared=None):
     """The training forward on the f16 matrix pipe (srcnn_conv2d_forward_f16x3): y = relu?(conv(x, w) + bias + residual) by the 3 x f16

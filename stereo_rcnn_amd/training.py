@@ -83,15 +83,18 @@ LOSS_NAMES = ('rpn_loss_cls', 'rpn_loss_bbox_left_right', 'RCNN_loss_cls', 'RCNN
 
 
 def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, backward_precision='f32', forward_precision='f32',
-               reuse_maxima=True, prepared_weights=False):
+               reuse_maxima=True, prepared_weights=False, device_fold=False):
     """One iteration of trainval_net.py:207-227.  batch: forward_train's nine inputs (im_left, im_right, im_info, gt_boxes_left,
     gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes).  Gradients are set to None, forward_train and
     losses.multi_task_loss build the total, backward() fills the gradients, and optimizer.step clips the MODEL's gradients to
     `clip_norm` (uncert's stays as it is, as in the reference) inside the fused update.  backward_precision, forward_precision,
     reuse_maxima: forward_train's.  prepared_weights: True builds a TrainWeights for the model (kept on the optimiser and reused)
     and calls its prepare() at the start of EVERY step -- never a cache keyed on a version counter: optimizer.step writes the
-    parameters through raw pointers, which torch's counter does not see.  Returns device scalars: 'loss', the six
+    parameters through raw pointers, which torch's counter does not see.  device_fold (it needs prepared_weights=True, ValueError
+    otherwise): that prepare() folds and re-lays-out the weights on the device (TrainWeights.prepare).  Returns device scalars: 'loss', the six
     terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0]."""
+    if device_fold and not prepared_weights:
+        raise ValueError("device_fold=True needs prepared_weights=True: it is TrainWeights.prepare's fold that moves to the device")
     optimizer.zero_grad(set_to_none=True)
     for p in model.parameters():
         p.grad = None
@@ -100,7 +103,7 @@ def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, b
         weights = getattr(optimizer, '_train_weights', None)
         if weights is None or weights.model is not model:
             weights = optimizer._train_weights = TrainWeights(model)
-        weights.prepare()
+        weights.prepare(device_fold=device_fold)
     out = forward_train(model, *batch, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision,
                         reuse_maxima=reuse_maxima, weights=weights)
     terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
@@ -164,7 +167,8 @@ class TrainWeights(object):
     four hi / lo planes of every layer in a fixed number of launches).  weights[key] is the autograd.PreparedLayer: key is the
     module for a plain convolution, 'rpn_head', 'RCNN_top.0', 'RCNN_top.3', 'box_heads', 'RCNN_kpts.12' otherwise.  The folded
     weights carry the graph, so prepare() belongs to ONE forward_train + backward: call it at the start of every step, after the
-    optimiser's update (train_step(prepared_weights=True) does).  The fold and the re-layout stay eager torch operators."""
+    optimiser's update (train_step(prepared_weights=True) does).  The fold and the re-layout are eager torch operators by default;
+    prepare(device_fold=True) runs them, and their adjoint, on the device in one call each."""
 
     def __init__(self, model):
         self.model = model
@@ -205,8 +209,49 @@ class TrainWeights(object):
         out.append((model.kpts_class,) + A.fold_conv(model.kpts_class.weight, model.kpts_class.bias))
         return out
 
-    def prepare(self):
-        folded = [(key, w.contiguous(), b) for key, w, b in self.enumerate()]
+    def specs(self):
+        """[(key, engine.FoldSpec)]: enumerate()'s layers, same keys, same order, named by their PARAMETERS for autograd.fold_all."""
+        model, S = self.model, engine.FoldSpec
+        for p in trainable_parameters(model).values():
+            p.requires_grad_(True)
+        out = []
+        for li in (1, 2, 3, 4):
+            if li <= cfg.RESNET.FIXED_BLOCKS:
+                continue
+            for blk in getattr(model, 'RCNN_layer%d' % li)[0]:
+                pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
+                if hasattr(blk, 'downsample'):
+                    pairs.append((blk.downsample[0], blk.downsample[1]))
+                pairs.append((blk.conv3, blk.bn3))
+                out += [(m, S('conv', [(m.weight, m.bias)], _bn(bn))) for m, bn in pairs]
+        rpn = model.RCNN_rpn
+        for m in (model.RCNN_toplayer, model.RCNN_latlayer1, model.RCNN_smooth1, model.RCNN_latlayer2, model.RCNN_smooth2,
+                  model.RCNN_latlayer3, model.RCNN_smooth3, rpn.RPN_Conv):
+            out.append((m, S('conv', [(m.weight, m.bias)])))
+        out.append(('rpn_head', S('conv', [(m.weight, m.bias) for m in (rpn.RPN_cls_score, rpn.RPN_bbox_pred_left_right)])))
+        top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
+        out.append(('RCNN_top.0', S('conv', [(top0.weight, top0.bias)])))           # viewed (2048, 1, 1, 49 * 512) by prepare()
+        out.append(('RCNN_top.3', S('conv', [(top3.weight, top3.bias)])))           # 1x1: the linear layer's (out, 1, 1, K)
+        out.append(('box_heads', S('linear', [(m.weight, m.bias) for m in (model.RCNN_bbox_pred, model.RCNN_dim_orien_pred,
+                                                                          model.RCNN_cls_score)])))
+        for i in (0, 2, 4, 6, 8, 10):
+            m = model.RCNN_kpts[i]
+            out.append((m, S('conv', [(m.weight, m.bias)])))
+        up = model.RCNN_kpts[12]
+        out.append(('RCNN_kpts.12', S('deconv2x2', [(up.weight, up.bias)])))
+        out.append((model.kpts_class, S('conv', [(model.kpts_class.weight, model.kpts_class.bias)])))
+        return out
+
+    def prepare(self, device_fold=False):
+        """device_fold: True replaces enumerate()'s eager folds (per layer a float64 fold, a permute().contiguous(), a torch.cat) by
+        ONE autograd.fold_all over the same keys in the same order -- two library calls per step, forward and adjoint
+        (csrc/train_fold.hip).  Every folded tensor and every parameter gradient keeps its bits."""
+        if device_fold:
+            named = self.specs()
+            folded = [(key, w.view(int(w.shape[0]), 1, 1, -1) if key == 'RCNN_top.0' else w, b)
+                      for (key, _), (w, b) in zip(named, autograd.fold_all([s for _, s in named]))]
+        else:
+            folded = [(key, w.contiguous(), b) for key, w, b in self.enumerate()]
         planes = engine.prepare_train_weights([w for _, w, _ in folded])
         self.layers = {key: autograd.PreparedLayer(w, b, p) for (key, w, b), p in zip(folded, planes)}
         return self

@@ -22,6 +22,9 @@ Either precision also takes `auto`: autograd.choose_engine picks f32 or f16x3 pe
 --prepared-weights (logged in trainlog.txt only when set): max |w| and the f16x3 planes of every layer's weight are prepared once
 at the start of each step, in one call (training.train_step's prepared_weights=True); the f16x3 calls then launch no pass over
 a weight.  The results are bit-identical.
+--device-fold (implies --prepared-weights; logged in trainlog.txt only when set): the frozen-BN fold and the re-layout of every
+weight, and their adjoint, run on the device in one call each (training.train_step's device_fold=True; csrc/train_fold.hip) in
+place of the per-layer torch operators.  The results are bit-identical.
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -71,10 +74,15 @@ def parse_args(argv=None):
     p.add_argument('--prepared-weights', dest='prepared_weights', action='store_true',
                    help="prepare max |w| and the f16x3 planes of every layer's weight once per step, in one call, instead of inside "
                         "every f16x3 convolution call (bit-identical results)")
+    p.add_argument('--device-fold', dest='device_fold', action='store_true',
+                   help="fold the frozen BNs and re-lay-out every weight on the device, one call per direction, in place of the "
+                        "per-layer torch operators (implies --prepared-weights; bit-identical results)")
     p.add_argument('--no-reuse-maxima', dest='reuse_maxima', action='store_false',
                    help="f16x3 precisions only: let every convolution call scan its input for max |x| itself instead of taking it from "
                         "the call that produced the tensor (same bits either way)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    args.prepared_weights = args.prepared_weights or args.device_fold
+    return args
 
 
 def main(argv=None):
@@ -113,6 +121,8 @@ def main(argv=None):
         log_string('forward precision: %s' % args.forward_precision)
     if args.prepared_weights:
         log_string('prepared weights: once per step')
+    if args.device_fold:
+        log_string('device fold: BN fold and weight re-layout in one call per direction')
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
@@ -157,7 +167,8 @@ def main(argv=None):
                     break
                 res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
                                           backward_precision=args.backward_precision, forward_precision=args.forward_precision,
-                                          reuse_maxima=args.reuse_maxima, prepared_weights=args.prepared_weights)
+                                          reuse_maxima=args.reuse_maxima, prepared_weights=args.prepared_weights,
+                                          device_fold=args.device_fold)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))
