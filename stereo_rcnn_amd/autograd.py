@@ -321,6 +321,18 @@ def fold_deconv2x2(weight, bias=None):
     return weight.permute(2, 3, 1, 0).reshape(4 * cout, 1, 1, cin), None if bias is None else bias.repeat(4)
 
 
+def fold_spec(spec):
+    """One engine.FoldSpec folded by the eager operators above: its parts' weights (and biases) concatenated along the rows, then
+    fold_conv / fold_linear / fold_deconv2x2 by its kind.  Returns (w, b or None), w in the folded shape spec.shape (a view
+    wherever the fold is one), both inside the graph.  fold_all is the same for a whole list on the device."""
+    ws, bs = [w for w, _ in spec.parts], [b for _, b in spec.parts]
+    w = ws[0] if len(ws) == 1 else torch.cat(ws, 0)
+    b = None if bs[0] is None else bs[0] if len(bs) == 1 else torch.cat(bs, 0)
+    if spec.kind == 'conv':
+        return fold_conv(w, b, spec.bn)
+    return fold_linear(w, b) if spec.kind == 'linear' else fold_deconv2x2(w, b)
+
+
 class _FoldAll(torch.autograd.Function):
     """fold_all's node: inputs, per layer and part, the weight and (where there is one) the bias, then every frozen BN tensor;
     outputs, per layer, the folded w and (where there is one) the folded b.  A b that is a BN's shift alone depends on no

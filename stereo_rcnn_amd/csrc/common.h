@@ -50,7 +50,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // blocks of a grid-stride launch over `total` work items: enough to cover them once, at most `cap`
 inline int grid_for(size_t total, int threads, size_t cap) { return (int)std::min<size_t>((total + threads - 1) / threads, cap); }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// p is a multiple of a (a power of two); nullptr is aligned to everything
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline bool aligned16(const void *p) { return aligned_to(p, 16); }
 
 // flat index of a (B, H, W, G) tensor -> its coordinates (G: channel groups of whatever width the caller works on)
 struct NhwcIndex { int b, h, w, g; };

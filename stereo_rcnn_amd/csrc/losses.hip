@@ -323,7 +323,6 @@ static int ce_lanes_per_row(int cols)
     return lpr;
 }
 
-static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 static int smooth_l1_args(SmoothL1Args &a, const char *who, const float *pred, const int *selector, int n_sel, const float *target,
                           const float *w_in, int w_in_per_row, const float *w_out, int w_out_per_row, long long rows, int D, float sigma)
@@ -382,7 +381,7 @@ int srcnn_cross_entropy(const float *logits, long long rows, int cols, long long
     hipStream_t st = as_stream(stream);
     if (blocks > 0) {
         if (cols == 2) {
-            if (row_stride % 2 == 0 && aligned8(logits))
+            if (row_stride % 2 == 0 && aligned_to(logits, 8))
                 SRCNN_LAUNCH(ce2_forward_kernel<true>, (unsigned)blocks, LOSS_THREADS, 0, st, logits, rows, row_stride, labels, weights, partial);
             else
                 SRCNN_LAUNCH(ce2_forward_kernel<false>, (unsigned)blocks, LOSS_THREADS, 0, st, logits, rows, row_stride, labels, weights, partial);
@@ -411,7 +410,7 @@ int srcnn_cross_entropy_backward(const float *logits, long long rows, int cols, 
     if (blocks == 0) return SRCNN_OK;
     hipStream_t st = as_stream(stream);
     if (cols == 2) {
-        if (row_stride % 2 == 0 && grad_stride % 2 == 0 && aligned8(logits) && aligned8(grad_logits))
+        if (row_stride % 2 == 0 && grad_stride % 2 == 0 && aligned_to(logits, 8) && aligned_to(grad_logits, 8))
             SRCNN_LAUNCH(ce2_backward_kernel<true>, (unsigned)blocks, LOSS_THREADS, 0, st, logits, rows, row_stride, labels, weights, mode, norm,
                          grad_loss, grad_logits, grad_stride);
         else

@@ -8,7 +8,7 @@
 //
 // The tensor list travels in the kernel's argument block (by value, at most SRCNN_OPT_TENSORS_PER_LAUNCH entries, tensors without
 // elements left out on the host): no device-side table, no upload.  A tensor is cut into chunks of SRCNN_OPT_CHUNK elements, a
-// workgroup takes one chunk at a time and finds the chunk's tensor by a binary search over the running chunk counts (uniform
+// workgroup takes one chunk at a time and finds the chunk's tensor by layer_list.h's search over the running chunk counts (uniform
 // over the workgroup).  Thread t of 256 owns the local elements 4 (256 j + t) + k, j, k = 0..3: one float4 per j where every
 // pointer of the tensor is 16-byte aligned (chunk starts are multiples of 4096 elements, so a chunk is aligned as its tensor is),
 // single floats otherwise and where a float4 would cross the tensor's end.
@@ -20,7 +20,7 @@
 //            four wavefront sums ((w0 + w1) + w2) + w3 and writes workspace[chunk number in the whole list];
 //   stage 2  one workgroup, float64: thread t adds workspace[t], workspace[t + 256], .. in that order starting from 0, the same
 //            butterfly and four-term sum in double; thread 0 writes (float)sqrt(sum) and the coefficient.
-#include "common.h"
+#include "layer_list.h"
 
 #include <climits>
 #include <cmath>
@@ -68,18 +68,6 @@ struct StepArgs {
 
 static_assert(sizeof(GradArgs) <= 4096 && sizeof(StepArgs) <= 4096, "the tensor list must fit HIP's kernel-argument block");
 
-// the first i with c < chunk_end[i]; c < chunk_end[n - 1]
-__device__ __forceinline__ int tensor_of_chunk(const int *chunk_end, int n, int c)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (c < chunk_end[mid]) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
 #pragma unroll
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_norm_partial_kernel(GradArgs
     const int tid = threadIdx.x;
     const int total = a.chunk_end[a.n - 1];
     for (int c = blockIdx.x; c < total; c += gridDim.x) {
-        const int i = tensor_of_chunk(a.chunk_end, a.n, c);
+        const int i = first_run_above(a.chunk_end, a.n, c);
         const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
         const float *g = a.t[i].g + start;
         const long long left = a.t[i].numel - start;                 // >= 1: the elements from the chunk's start to the tensor's end
@@ -156,7 +144,7 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_scale_kernel(GradArgs a, con
     const int tid = threadIdx.x;
     const int total = a.chunk_end[a.n - 1];
     for (int c = blockIdx.x; c < total; c += gridDim.x) {
-        const int i = tensor_of_chunk(a.chunk_end, a.n, c);
+        const int i = first_run_above(a.chunk_end, a.n, c);
         const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
         float *g = a.t[i].g + start;
         const long long left = a.t[i].numel - start;
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_step_kernel(StepArgs a)
     const int total = a.chunk_end[a.n - 1];
     const float coef = a.coef ? *a.coef : 1.0f;
     for (int c = blockIdx.x; c < total; c += gridDim.x) {
-        const int i = tensor_of_chunk(a.chunk_end, a.n, c);
+        const int i = first_run_above(a.chunk_end, a.n, c);
         const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
         const long long left = a.t[i].numel - start;
         const int flags = a.t[i].flags;
@@ -238,8 +226,6 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_step_kernel(StepArgs a)
         }
     }
 }
-
-static bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static long long chunks_of(long long numel) { return (numel + OPT_CHUNK - 1) / OPT_CHUNK; }
 

@@ -7,8 +7,8 @@
 //                              the engine's layout; the bias; max |w'| of the layer
 //   pass B  prep_split_kernel  k from the exponent and mantissa of the max, hi = f16(w' 2^k), lo = f16(w' 2^k - hi), the fragment
 //                              layout of a fused head from the same hi / lo, k to the caller's device array
-// The layer descriptors travel in the kernels' argument blocks, at most SRCNN_PREP_LAYERS_PER_LAUNCH per launch (csrc/optim.hip's
-// scheme): no device table, no upload.
+// The layer descriptors travel in the kernels' argument blocks, at most SRCNN_PREP_LAYERS_PER_LAUNCH per launch (layer_list.h): no
+// device table, no upload.
 //
 // Pass A's unit of work is RB destination rows x CC input channels with RB * CC * taps <= PREP_TILE floats: the source of such a
 // unit is contiguous per row ((Cout, Cin, KH, KW): CC * taps floats from channel c0 on), it is read in source order -- 16 bytes
@@ -20,7 +20,8 @@
 // The max is an integer max over the bit patterns of |w'| (they order like the values, and every NaN pattern lies above +inf, so
 // a NaN wins as it does in torch.max): lanes, then the four wavefronts through LDS, then one integer atomicMax per workgroup on the
 // layer's word of the workspace -- order independent, so the same bits on every run; no float atomics anywhere.
-#include "common.h"
+#include "bn_fold.h"
+#include "layer_list.h"
 
 #include <hip/hip_fp16.h>
 
@@ -46,17 +47,6 @@ struct PrepArgs {
 };
 static_assert(sizeof(PrepArgs) <= 4096, "the layer list must fit HIP's kernel-argument block");
 
-__device__ __forceinline__ int layer_of_block(const int *block_end, int n, int b)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (b < block_end[mid]) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 __host__ __device__ inline int prep_rows(const srcnn_prep_layer &L)
 {
     if (L.form == SRCNN_PREP_DECONV2X2) return 4 * L.cout[0];
@@ -76,33 +66,21 @@ __host__ __device__ inline long long prep_row_len(const srcnn_prep_layer &L)
     return L.form == SRCNN_PREP_STEM ? 224 : (long long)prep_chan(L) * prep_taps(L);
 }
 
-// fold_bn: s = g / sqrt(v + eps) in float64, every operation rounded once
+// BN `which` of the layer through bn_fold.h: the scale of row co (1 without a BN), its folded bias, a folded weight
 __device__ __forceinline__ double bn_scale(const srcnn_prep_layer &L, int which, int co)
 {
-#pragma clang fp contract(off)
-    if (!L.bn_g[which]) return 1.0;
-    const double v = (double)L.bn_v[which][co] + 1e-5;
-    return (double)L.bn_g[which][co] / sqrt(v);
+    return L.bn_g[which] ? bn_scale(L.bn_g[which], L.bn_v[which], co) : 1.0;
 }
 
 __device__ __forceinline__ float bn_bias(const srcnn_prep_layer &L, int which, int co, double s)
 {
-#pragma clang fp contract(off)
-    const double ms = (double)L.bn_m[which][co] * s;
-    return (float)((double)L.bn_b[which][co] - ms);
+    return (float)bn_shift(L.bn_b[which], L.bn_m[which], co, s);
 }
 
-__device__ __forceinline__ float fold(float w, double s, bool bn)
-{
-#pragma clang fp contract(off)
-    if (!bn) return w;
-    const double p = (double)w * s;
-    return (float)p;
-}
+__device__ __forceinline__ float fold(float w, double s, bool bn) { return bn ? bn_mul(w, s) : w; }
 
-__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-
-// source tensor and row inside it of destination row `row` of a CONV layer (sources concatenated along Cout)
+// source tensor and row inside it of destination row `row` of a CONV layer (sources concatenated along Cout): layer_list.h's
+// part_of_row RESTATED, because calling it moves prep_fold_kernel's instruction stream (profiles/train_list_helpers_ab.txt)
 __device__ __forceinline__ void conv_source(const srcnn_prep_layer &L, int row, int &s, int &co)
 {
     s = 0, co = row;
@@ -112,13 +90,15 @@ __device__ __forceinline__ void conv_source(const srcnn_prep_layer &L, int row, 
     }
 }
 
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
 __global__ __launch_bounds__(PREP_THREADS) void prep_fold_kernel(const PrepArgs a)
 {
     __shared__ __attribute__((aligned(16))) float tile[PREP_TILE];
     __shared__ double sc[2][PREP_MAX_RB];
     __shared__ unsigned wmax[PREP_THREADS / 64];
     const int t = threadIdx.x;
-    const int li = layer_of_block(a.block_end, a.n, blockIdx.x);
+    const int li = first_run_above(a.block_end, a.n, blockIdx.x);
     const srcnn_prep_layer &L = a.l[li];
     const int unit = blockIdx.x - (li ? a.block_end[li - 1] : 0);
     const int form = L.form, rows = prep_rows(L), chan = prep_chan(L), T = prep_taps(L);
@@ -276,7 +256,7 @@ struct alignas(16) Half8 {
 __global__ __launch_bounds__(PREP_THREADS) void prep_split_kernel(const PrepArgs a)
 {
     const int t = threadIdx.x;
-    const int li = layer_of_block(a.block_end, a.n, blockIdx.x);
+    const int li = first_run_above(a.block_end, a.n, blockIdx.x);
     const srcnn_prep_layer &L = a.l[li];
     const int unit = blockIdx.x - (li ? a.block_end[li - 1] : 0);
     const int g = a.layer_base + li;
@@ -334,8 +314,6 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_split_kernel(const PrepArgs
     }
 }
 
-static bool prep_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // nullptr, or what is wrong with layer i of the list
 static const char *check_layer(const srcnn_prep_layer *all, int i)
 {
@@ -344,8 +322,8 @@ static const char *check_layer(const srcnn_prep_layer *all, int i)
     if (!L.dst_w) return "null dst_w";
     if ((L.dst_hi == nullptr) != (L.dst_lo == nullptr)) return "dst_hi and dst_lo go together";
     if (L.dst_frag && !L.dst_hi) return "dst_frag needs dst_hi / dst_lo";
-    if (!prep_aligned(L.dst_w, 4) || !prep_aligned(L.dst_b, 4) || !prep_aligned(L.dst_hi, 2) || !prep_aligned(L.dst_lo, 2)
-        || !prep_aligned(L.dst_frag, 2))
+    if (!aligned_to(L.dst_w, 4) || !aligned_to(L.dst_b, 4) || !aligned_to(L.dst_hi, 2) || !aligned_to(L.dst_lo, 2)
+        || !aligned_to(L.dst_frag, 2))
         return "misaligned destination";
     const int nsrc_want = L.form == SRCNN_PREP_SHORTCUT ? 2 : (L.form == SRCNN_PREP_CONV ? 0 : 1);
     if (L.n_src < 1 || L.n_src > 3 || (nsrc_want && L.n_src != nsrc_want)) return "n_src does not fit the form";
@@ -388,7 +366,7 @@ static const char *check_layer(const srcnn_prep_layer *all, int i)
     } else {
         for (int s = 0; s < L.n_src; ++s) {
             if (!L.w[s]) return "null source weight";
-            if (!prep_aligned(L.w[s], 4) || !prep_aligned(L.b[s], 4)) return "misaligned source";
+            if (!aligned_to(L.w[s], 4) || !aligned_to(L.b[s], 4)) return "misaligned source";
         }
         if (L.form == SRCNN_PREP_CONV && !bn0) {
             for (int s = 1; s < L.n_src; ++s)
@@ -423,7 +401,7 @@ int srcnn_prep_weights(const srcnn_prep_layer *layers_host, int n_layers, int *k
     SRCNN_REQUIRE(layers_host, "null layers_host");
     SRCNN_REQUIRE(n_layers >= 1, "n_layers must be >= 1");
     SRCNN_REQUIRE(k_out && workspace, "null k_out / workspace");
-    SRCNN_REQUIRE(prep_aligned(k_out, 4) && prep_aligned(workspace, 4), "k_out / workspace not 4-byte aligned");
+    SRCNN_REQUIRE(aligned_to(k_out, 4) && aligned_to(workspace, 4), "k_out / workspace not 4-byte aligned");
     for (int i = 0; i < n_layers; ++i) {
         const char *m = check_layer(layers_host, i);
         if (m) {
@@ -457,9 +435,9 @@ int srcnn_prep_weights(const srcnn_prep_layer *layers_host, int n_layers, int *k
                     if (rb > rows) rb = rows;
                 }
                 a.rb[i] = (short)rb, a.cc[i] = (short)cc;
-                bool in16 = L.alias_of < 0, out16 = prep_aligned(L.dst_w, 16) && prep_aligned(L.dst_hi, 16) && prep_aligned(L.dst_lo, 16)
-                                                   && prep_aligned(L.dst_frag, 16);
-                for (int s = 0; s < L.n_src && in16; ++s) in16 = prep_aligned(L.w[s], 16);
+                bool in16 = L.alias_of < 0, out16 = aligned_to(L.dst_w, 16) && aligned_to(L.dst_hi, 16) && aligned_to(L.dst_lo, 16)
+                                                   && aligned_to(L.dst_frag, 16);
+                for (int s = 0; s < L.n_src && in16; ++s) in16 = aligned_to(L.w[s], 16);
                 if (L.form == SRCNN_PREP_SHORTCUT) {
                     in16 = in16 && L.cin % 4 == 0 && L.cin2 % 4 == 0 && cc % 4 == 0;
                     out16 = out16 && L.cin % 4 == 0 && L.cin2 % 4 == 0 && cc % 4 == 0;

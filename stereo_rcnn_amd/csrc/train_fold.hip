@@ -1,11 +1,11 @@
 // Training: the frozen-BN fold and the re-layout of EVERY layer's weight on the device, and its adjoint, each in a fixed number of
 // launches (include/srcnn_train_fold.h states the contract).  What stereo_rcnn_amd.autograd's fold_conv / fold_linear /
 // fold_deconv2x2 + .contiguous() + torch.cat do per layer with eager operators, and what torch autograd does on the way back
-// through them.  The float64 fold is csrc/prep_weights.hip's (one rounding per operation, contraction off), so the results carry
-// the eager path's bits.
+// through them.  The float64 fold is bn_fold.h's, which csrc/prep_weights.hip calls too (one rounding per operation, contraction
+// off), so the results carry the eager path's bits.
 //
 // THE LIST travels as csrc/train_weights.hip's does: TF_LPL layers per kernel-argument block into a table in the workspace
-// (tf_table_kernel), then ONE launch of tf_kernel<direction> over the running unit counts of the whole table.
+// (layer_list.h's row_table_kernel), then ONE launch of tf_kernel<direction> over the running unit counts of the whole table.
 //
 // A unit is RB output rows x CC input channels (all T = KH KW taps), RB CC T <= TF_TILE floats, CC a multiple of 32 (the host
 // chooses RB and CC per layer: prep_weights.hip's cut along the source's contiguous side).  On the PARAMETER side
@@ -19,11 +19,10 @@
 // The deconvolution ((Cin, Cout, 2, 2) -> row (ij, co), column ci) is a full transpose with a row permutation: its unit is 32 ci x
 // up to 32 co x 4 ij, rows of the LDS tile padded by 4 floats.
 // The rows' biases are written by the units of the first channel chunk.
-#include "common.h"
+#include "bn_fold.h"
+#include "layer_list.h"
 
 #include "../../include/srcnn_train_fold.h"
-
-#include <cstdint>
 
 namespace srcnn {
 
@@ -46,69 +45,21 @@ struct TfRow {
 };
 static_assert(sizeof(TfRow) == 144, "the documented workspace record");
 
-struct TfBlock {
-    TfRow r[TF_LPL];
-    int n, base;                                   // rows of this block, number of its first row in the table
-};
-static_assert(sizeof(TfBlock) <= 4096 - sizeof(void *), "the layer list must fit HIP's kernel-argument block");
+static_assert(sizeof(RowBlock<TfRow, TF_LPL>) <= 4096 - sizeof(void *), "the layer list must fit HIP's kernel-argument block");
 
-__global__ __launch_bounds__(64) void tf_table_kernel(const TfBlock b, TfRow *table)
-{
-    const int i = threadIdx.x;
-    if (i < b.n) table[b.base + i] = b.r[i];
-}
-
-// the first row whose running unit count exceeds u; u < the last row's
-__device__ __forceinline__ int tf_row_of(const TfRow *table, int n, int u)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (u < table[mid].unit_end) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// part and row inside it of output row `row` (parts concatenated along the rows)
-__device__ __forceinline__ void tf_source(const TfRow &L, int row, int &p, int &co)
-{
-    p = 0, co = row;
-    if (L.nparts > 1 && co >= L.rows[0]) {
-        co -= L.rows[0], p = 1;
-        if (L.nparts > 2 && co >= L.rows[1]) co -= L.rows[1], p = 2;
-    }
-}
-
-// s = g / sqrt(v + eps) in float64, every operation rounded once
-__device__ __forceinline__ double tf_scale(const TfRow &L, int co)
-{
-#pragma clang fp contract(off)
-    const double v = (double)L.bn_v[co] + 1e-5;
-    return (double)L.bn_g[co] / sqrt(v);
-}
-
+// the folded bias of row co under the BN of scale s: the shift, plus the scaled bias of a convolution that has one
 __device__ __forceinline__ float tf_bias(const TfRow &L, int co, double s)
 {
 #pragma clang fp contract(off)
-    const double ms = (double)L.bn_m[co] * s;
-    const double shift = (double)L.bn_b[co] - ms;
+    const double shift = bn_shift(L.bn_b, L.bn_m, co, s);
     if (!L.part_b[0]) return (float)shift;
     const double bs = (double)L.part_b[0][co] * s;
-    const double sum = bs + shift;
-    return (float)sum;
-}
-
-__device__ __forceinline__ float tf_mul(float w, double s)
-{
-#pragma clang fp contract(off)
-    const double p = (double)w * s;
-    return (float)p;
+    return (float)(bs + shift);
 }
 
 __device__ __forceinline__ float4 tf_mul4(float4 v, double s)
 {
-    return make_float4(tf_mul(v.x, s), tf_mul(v.y, s), tf_mul(v.z, s), tf_mul(v.w, s));
+    return make_float4(bn_mul(v.x, s), bn_mul(v.y, s), bn_mul(v.z, s), bn_mul(v.w, s));
 }
 
 template <bool BWD>
@@ -166,7 +117,7 @@ __global__ __launch_bounds__(TF_THREADS) void tf_kernel(const TfRow *table, int 
     __shared__ __attribute__((aligned(16))) float tile[TF_TILE + 4 * TF_DC];
     __shared__ double sc[TF_MAX_RB];
     const int t = threadIdx.x;
-    const int li = tf_row_of(table, n, blockIdx.x);
+    const int li = first_run_above(table, &TfRow::unit_end, n, blockIdx.x);
     const TfRow L = table[li];
     const int unit = blockIdx.x - (li ? table[li - 1].unit_end : 0);
     if (L.kind == SRCNN_TRAIN_FOLD_DECONV2X2) {
@@ -183,12 +134,12 @@ __global__ __launch_bounds__(TF_THREADS) void tf_kernel(const TfRow *table, int 
     if (t < nr) {
         const int row = r0 + t;
         int p, co;
-        tf_source(L, row, p, co);
-        const double s = bn ? tf_scale(L, co) : 1.0;
+        part_of_row(L.nparts, L.rows, row, p, co);
+        const double s = bn ? bn_scale(L.bn_g, L.bn_v, co) : 1.0;
         sc[t] = s;
         if (ch == 0 && L.eng_b) {
             if (!BWD) L.eng_b[row] = bn ? tf_bias(L, co, s) : L.part_b[p][co];
-            else L.part_b[p][co] = bn ? tf_mul(L.eng_b[row], s) : L.eng_b[row];
+            else L.part_b[p][co] = bn ? bn_mul(L.eng_b[row], s) : L.eng_b[row];
         }
     }
     __syncthreads();
@@ -202,7 +153,7 @@ __global__ __launch_bounds__(TF_THREADS) void tf_kernel(const TfRow *table, int 
         rl = q / q_row;
         const int j = (q - rl * q_row) << 2;
         int p, co;
-        tf_source(L, r0 + rl, p, co);
+        part_of_row(L.nparts, L.rows, r0 + rl, p, co);
         g = L.part_w[p] + ((size_t)co * L.cin + c0) * T + j;
         s = tile + rl * per_row + j;
     };
@@ -241,8 +192,6 @@ __global__ __launch_bounds__(TF_THREADS) void tf_kernel(const TfRow *table, int 
     }
 }
 
-static bool tf_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // nullptr, or what is wrong with the layer; dw / db: the backward's gradients of the folded tensors (forward: unused)
 static const char *tf_check_layer(const srcnn_train_fold_desc &L, bool backward, const float *dw, const float *db)
 {
@@ -264,34 +213,34 @@ static const char *tf_check_layer(const srcnn_train_fold_desc &L, bool backward,
     const bool any_bn = L.bn_weight || L.bn_bias || L.bn_mean || L.bn_var, bn = L.bn_weight && L.bn_bias && L.bn_mean && L.bn_var;
     if (any_bn && !bn) return "null pointer: a frozen BN needs all of bn_weight, bn_bias, bn_mean, bn_var";
     if (bn && (L.n_parts != 1 || L.kind == SRCNN_TRAIN_FOLD_DECONV2X2)) return "a frozen BN folds into a single convolution part";
-    if (!tf_aligned(L.bn_weight, 4) || !tf_aligned(L.bn_bias, 4) || !tf_aligned(L.bn_mean, 4) || !tf_aligned(L.bn_var, 4))
+    if (!aligned_to(L.bn_weight, 4) || !aligned_to(L.bn_bias, 4) || !aligned_to(L.bn_mean, 4) || !aligned_to(L.bn_var, 4))
         return "the BN tensors must be 4-byte aligned";
     const bool bias = L.bias[0] != nullptr;
     for (int p = 0; p < L.n_parts; ++p) {
         if (!backward) {                                    // the backward reads no weight
             if (!L.w[p]) return "null pointer: w of a part";
-            if (!tf_aligned(L.w[p], 16)) return "w must be 16-byte aligned (vector loads)";
+            if (!aligned_to(L.w[p], 16)) return "w must be 16-byte aligned (vector loads)";
         }
         if ((L.bias[p] != nullptr) != bias) return "every part carries a bias, or none";
-        if (!tf_aligned(L.bias[p], 4)) return "bias must be 4-byte aligned";
+        if (!aligned_to(L.bias[p], 4)) return "bias must be 4-byte aligned";
         if (backward && dw) {
             if (!L.grad_w[p]) return "null pointer: grad_w of a part";
-            if (!tf_aligned(L.grad_w[p], 16)) return "grad_w must be 16-byte aligned (vector stores)";
+            if (!aligned_to(L.grad_w[p], 16)) return "grad_w must be 16-byte aligned (vector stores)";
         }
         if (backward && db && bias) {
             if (!L.grad_b[p]) return "null pointer: grad_b of a part";
-            if (!tf_aligned(L.grad_b[p], 4)) return "grad_b must be 4-byte aligned";
+            if (!aligned_to(L.grad_b[p], 4)) return "grad_b must be 4-byte aligned";
         }
     }
     if (!backward) {
         if (!L.dst_w) return "null pointer: dst_w";
-        if (!tf_aligned(L.dst_w, 16)) return "dst_w must be 16-byte aligned (vector stores)";
+        if (!aligned_to(L.dst_w, 16)) return "dst_w must be 16-byte aligned (vector stores)";
         if ((bn || bias) && !L.dst_b) return "null pointer: dst_b (a BN or a bias leaves a folded bias)";
         if (!bn && !bias && L.dst_b) return "dst_b without a BN or a bias";
-        if (!tf_aligned(L.dst_b, 4)) return "dst_b must be 4-byte aligned";
+        if (!aligned_to(L.dst_b, 4)) return "dst_b must be 4-byte aligned";
     } else {
-        if (!tf_aligned(dw, 16)) return "dw_folded must be 16-byte aligned (vector loads)";
-        if (!tf_aligned(db, 4)) return "db_folded must be 4-byte aligned";
+        if (!aligned_to(dw, 16)) return "dw_folded must be 16-byte aligned (vector loads)";
+        if (!aligned_to(db, 4)) return "db_folded must be 4-byte aligned";
         if (db && L.kind == SRCNN_TRAIN_FOLD_DECONV2X2) return "db_folded of a deconvolution is not taken: its bias stays the caller's repeat(4)";
     }
     return nullptr;
@@ -303,7 +252,7 @@ static int tf_run(const char *who, const srcnn_train_fold_desc *layers_host, int
     SRCNN_REQUIRE_AS(who, layers_host != nullptr, "null layers_host");
     SRCNN_REQUIRE_AS(who, n_layers >= 1, "n_layers must be >= 1");
     SRCNN_REQUIRE_AS(who, workspace != nullptr, "null workspace");
-    SRCNN_REQUIRE_AS(who, tf_aligned(workspace, 16), "workspace must be 16-byte aligned");
+    SRCNN_REQUIRE_AS(who, aligned_to(workspace, 16), "workspace must be 16-byte aligned");
     SRCNN_REQUIRE_AS(who, !backward || (dw && db), "null dw_folded_host / db_folded_host (the arrays; their entries may be null)");
     for (int i = 0; i < n_layers; ++i) {
         const char *m = tf_check_layer(layers_host[i], backward, backward ? dw[i] : nullptr, backward ? db[i] : nullptr);
@@ -322,7 +271,7 @@ static int tf_run(const char *who, const srcnn_train_fold_desc *layers_host, int
     TfRow *table = static_cast<TfRow *>(workspace);
     long long units = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        TfBlock b;
+        RowBlock<TfRow, TF_LPL> b;
         b.n = 0, b.base = 0;
         long long run = 0;
         for (int i = 0; i < n_layers; ++i) {
@@ -352,10 +301,7 @@ static int tf_run(const char *who, const srcnn_train_fold_desc *layers_host, int
             if (!r.eng_w && !r.eng_b) u = 0;                // (backward) a layer without gradients
             run += u;
             r.unit_end = (int)run;
-            if (++b.n == TF_LPL || i == n_layers - 1) {
-                if (pass == 1) SRCNN_LAUNCH(tf_table_kernel, dim3(1), dim3(64), 0, st, b, table);
-                b.base += b.n, b.n = 0;
-            }
+            push_row<false>(b, i == n_layers - 1, pass == 1 ? table : nullptr, st);
         }
         if (pass == 0) {
             units = run;

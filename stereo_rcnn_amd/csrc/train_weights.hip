@@ -5,10 +5,9 @@
 // conv_forward_f16x3.hip / conv_backward_f16x3.hip read the results instead.  pow2_scale and split_f16 are conv_f16x3_scaled.h's, so
 // the planes carry the bits those kernels write.
 //
-// THE LIST travels in kernel-argument blocks (csrc/optim.hip's and csrc/prep_weights.hip's scheme: by value, nothing is uploaded
-// by the host runtime), TW_LPL layers per block, but only as far as a table in the workspace: tw_table_kernel writes its block's
-// rows there and clears the rows' max words.  The two kernels that do the work read the table and are ONE launch each for the whole
-// list, so their grids are balanced over all layers at once:
+// THE LIST travels in kernel-argument blocks (layer_list.h), TW_LPL layers per block, as far as a table in the workspace:
+// row_table_kernel writes its block's rows there and clears the rows' max words.  The two kernels that do the work read the
+// table and are ONE launch each for the whole list, so their grids are balanced over all layers at once:
 //   tw_absmax_kernel   a layer is TW_MAX_CHUNK-float chunks; workgroup = one chunk, its layer found by a binary search over the
 //                      rows' running chunk counts (uniform over the workgroup: scalar loads).  float4 loads, wave_absmax_to_word:
 //                      one integer atomicMax on the float bits per wave with a non-zero maximum.
@@ -21,6 +20,7 @@
 //                      2-byte LDS reads: the transpose).  The next K tile's load is issued before the stores.
 // The clear cannot share a launch with the atomicMax (that would need a device-scope fence); it shares one with the table rows.
 #include "conv_f16x3_scaled.h"
+#include "layer_list.h"
 
 namespace srcnn {
 
@@ -39,38 +39,12 @@ struct TwRow {
 };
 static_assert(sizeof(TwRow) == 80, "the documented workspace record");
 
-struct TwBlock {
-    TwRow r[TW_LPL];
-    int n, base;                           // rows of this block, number of its first row in the table
-};
-static_assert(sizeof(TwBlock) <= 4096 - sizeof(void *), "the layer list must fit HIP's kernel-argument block");
-
-__global__ __launch_bounds__(64) void tw_table_kernel(const TwBlock b, TwRow *table)
-{
-    const int i = threadIdx.x;
-    if (i < b.n) {
-        table[b.base + i] = b.r[i];
-        *b.r[i].word = 0u;
-    }
-}
-
-// the first row whose running count (max_end or plane_end) exceeds u; u < the last row's
-template <int TwRow::*END>
-__device__ __forceinline__ int tw_row_of(const TwRow *table, int n, int u)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (u < table[mid].*END) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
+static_assert(sizeof(RowBlock<TwRow, TW_LPL>) <= 4096 - sizeof(void *), "the layer list must fit HIP's kernel-argument block");
 
 __global__ __launch_bounds__(256) void tw_absmax_kernel(const TwRow *table, int n)
 {
     const int t = threadIdx.x;
-    const int li = tw_row_of<&TwRow::max_end>(table, n, blockIdx.x);
+    const int li = first_run_above(table, &TwRow::max_end, n, blockIdx.x);
     const TwRow L = table[li];
     const int chunk = blockIdx.x - (li ? table[li - 1].max_end : 0);
     const long long groups = (long long)L.cout * L.taps * L.cin / 4;         // Cin % 32 == 0
@@ -92,7 +66,7 @@ __global__ __launch_bounds__(256) void tw_planes_kernel(const TwRow *table, int 
 {
     __shared__ __attribute__((aligned(16))) _Float16 sh[2][32][TW_SROW];
     const int t = threadIdx.x;
-    const int li = tw_row_of<&TwRow::plane_end>(table, n, blockIdx.x);
+    const int li = first_run_above(table, &TwRow::plane_end, n, blockIdx.x);
     const TwRow L = table[li];
     const int unit = blockIdx.x - (li ? table[li - 1].plane_end : 0);
     const int rb = unit / L.kunits, ku = unit - rb * L.kunits;
@@ -130,17 +104,15 @@ __global__ __launch_bounds__(256) void tw_planes_kernel(const TwRow *table, int 
     }
 }
 
-static bool tw_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // nullptr, or what is wrong with the layer
 static const char *tw_check_layer(const srcnn_train_weight_desc &L)
 {
     if (!L.w) return "null pointer: w";
     if (!L.w_amax) return "null pointer: w_amax";
     if (!L.w_hi || !L.w_lo || !L.wt_hi || !L.wt_lo) return "null pointer: a plane (w_hi, w_lo, wt_hi, wt_lo)";
-    if (!tw_aligned(L.w, 16)) return "w must be 16-byte aligned (vector loads)";
-    if (!tw_aligned(L.w_amax, 4)) return "w_amax must be 4-byte aligned";
-    if (!tw_aligned(L.w_hi, 16) || !tw_aligned(L.w_lo, 16) || !tw_aligned(L.wt_hi, 16) || !tw_aligned(L.wt_lo, 16))
+    if (!aligned_to(L.w, 16)) return "w must be 16-byte aligned (vector loads)";
+    if (!aligned_to(L.w_amax, 4)) return "w_amax must be 4-byte aligned";
+    if (!aligned_to(L.w_hi, 16) || !aligned_to(L.w_lo, 16) || !aligned_to(L.wt_hi, 16) || !aligned_to(L.wt_lo, 16))
         return "the planes must be 16-byte aligned (vector stores)";
     if (L.Cout <= 0 || L.KH <= 0 || L.KW <= 0 || L.Cin <= 0) return "bad shape: sizes must be positive";
     if (L.Cin % BK != 0) return "Cin must be a positive multiple of 32";
@@ -166,7 +138,7 @@ int srcnn_train_weights_prepare(const srcnn_train_weight_desc *layers_host, int 
     SRCNN_REQUIRE(layers_host != nullptr, "null layers_host");
     SRCNN_REQUIRE(n_layers >= 1, "n_layers must be >= 1");
     SRCNN_REQUIRE(workspace != nullptr, "null workspace");
-    SRCNN_REQUIRE(tw_aligned(workspace, 16), "workspace must be 16-byte aligned");
+    SRCNN_REQUIRE(aligned_to(workspace, 16), "workspace must be 16-byte aligned");
     long long chunks = 0, units = 0;
     for (int i = 0; i < n_layers; ++i) {
         const char *m = tw_check_layer(layers_host[i]);
@@ -187,7 +159,7 @@ int srcnn_train_weights_prepare(const srcnn_train_weight_desc *layers_host, int 
 
     hipStream_t st = as_stream(stream);
     TwRow *table = static_cast<TwRow *>(workspace);
-    TwBlock b;
+    RowBlock<TwRow, TW_LPL> b;
     b.n = 0, b.base = 0;
     chunks = units = 0;
     for (int i = 0; i < n_layers; ++i) {
@@ -201,10 +173,7 @@ int srcnn_train_weights_prepare(const srcnn_train_weight_desc *layers_host, int 
         chunks += ((long long)r.cout * r.taps * r.cin + TW_MAX_CHUNK - 1) / TW_MAX_CHUNK;
         units += (long long)(r.cp / BK) * r.kunits;
         r.max_end = (int)chunks, r.plane_end = (int)units;
-        if (++b.n == TW_LPL || i == n_layers - 1) {
-            SRCNN_LAUNCH(tw_table_kernel, dim3(1), dim3(64), 0, st, b, table);
-            b.base += b.n, b.n = 0;
-        }
+        push_row<true>(b, i == n_layers - 1, table, st);
     }
     SRCNN_LAUNCH(tw_absmax_kernel, dim3((unsigned)chunks), dim3(256), 0, st, (const TwRow *)table, n_layers);
     SRCNN_LAUNCH(tw_planes_kernel, dim3((unsigned)units), dim3(256), 0, st, (const TwRow *)table, n_layers);

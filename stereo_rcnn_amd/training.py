@@ -144,26 +144,17 @@ def _bottleneck(blk, x, name, tap, prec, weights=None):
     return tap(name + '.out', _conv(blk.conv3, t, prec, True, residual=res, bn=blk.bn3, weights=weights))
 
 
-def _rpn_head(rpn):
-    return (torch.cat((rpn.RPN_cls_score.weight, rpn.RPN_bbox_pred_left_right.weight), 0),
-            torch.cat((rpn.RPN_cls_score.bias, rpn.RPN_bbox_pred_left_right.bias), 0))
-
-
-def _top0_weight(top0):
-    return top0.weight.permute(0, 2, 3, 1).reshape(int(top0.weight.shape[0]), -1)          # (2048, (kh, kw, c)): the NHWC window
-
-
-def _box_heads(model):
-    return (torch.cat((model.RCNN_bbox_pred.weight, model.RCNN_dim_orien_pred.weight, model.RCNN_cls_score.weight), 0),
-            torch.cat((model.RCNN_bbox_pred.bias, model.RCNN_dim_orien_pred.bias, model.RCNN_cls_score.bias), 0))
+def _linear(layer, x, prec, relu=False):
+    """autograd.linear over a PreparedLayer of TrainWeights: its w (out, 1, 1, K) is the linear layer's (out, K)."""
+    return autograd.linear(x, layer.w.view(int(layer.w.shape[0]), -1), layer.b, relu=relu, _prec=prec, prepared=layer)
 
 
 class TrainWeights(object):
-    """Every weight forward_train's graph layers use, folded and prepared for the f16x3 engine ONCE per step: prepare() enumerates
+    """Every weight forward_train's graph layers use, folded and prepared for the f16x3 engine ONCE per step: specs() lists
     exactly the (weight, bias, bn) combinations forward_train composes -- the bottleneck convolutions of the stages with a graph
     (their frozen BNs folded by autograd's own fold, inside the graph), the FPN layers, RPN_Conv, the concatenated RPN head, RCNN_top[0]'s
     permuted view and RCNN_top[3], the concatenated box heads, the keypoint tower, its deconvolution in row order (i, j, co) and
-    kpts_class -- and then makes one engine.prepare_train_weights call over all of them (csrc/train_weights.hip: max |w| and the
+    kpts_class --, fold() folds them, and prepare() then makes one engine.prepare_train_weights call over all of them (csrc/train_weights.hip: max |w| and the
     four hi / lo planes of every layer in a fixed number of launches).  weights[key] is the autograd.PreparedLayer: key is the
     module for a plain convolution, 'rpn_head', 'RCNN_top.0', 'RCNN_top.3', 'box_heads', 'RCNN_kpts.12' otherwise.  The folded
     weights carry the graph, so prepare() belongs to ONE forward_train + backward: call it at the start of every step, after the
@@ -178,39 +169,12 @@ class TrainWeights(object):
         return self.layers[key]
 
     def enumerate(self):
-        """[(key, folded w, folded b)] in forward_train's order of first use."""
-        model, A = self.model, autograd
-        for p in trainable_parameters(model).values():
-            p.requires_grad_(True)
-        out = []
-        for li in (1, 2, 3, 4):
-            if li <= cfg.RESNET.FIXED_BLOCKS:
-                continue
-            for blk in getattr(model, 'RCNN_layer%d' % li)[0]:
-                pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
-                if hasattr(blk, 'downsample'):
-                    pairs.append((blk.downsample[0], blk.downsample[1]))
-                pairs.append((blk.conv3, blk.bn3))
-                out += [(m,) + A.fold_conv(m.weight, m.bias, _bn(bn)) for m, bn in pairs]
-        rpn = model.RCNN_rpn
-        for m in (model.RCNN_toplayer, model.RCNN_latlayer1, model.RCNN_smooth1, model.RCNN_latlayer2, model.RCNN_smooth2,
-                  model.RCNN_latlayer3, model.RCNN_smooth3, rpn.RPN_Conv):
-            out.append((m,) + A.fold_conv(m.weight, m.bias))
-        out.append(('rpn_head',) + A.fold_conv(*_rpn_head(rpn)))
-        top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
-        out.append(('RCNN_top.0',) + A.fold_linear(_top0_weight(top0), top0.bias))
-        out.append(('RCNN_top.3',) + A.fold_linear(top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias))
-        out.append(('box_heads',) + A.fold_linear(*_box_heads(model)))
-        for i in (0, 2, 4, 6, 8, 10):
-            m = model.RCNN_kpts[i]
-            out.append((m,) + A.fold_conv(m.weight, m.bias))
-        up = model.RCNN_kpts[12]
-        out.append(('RCNN_kpts.12',) + A.fold_deconv2x2(up.weight, up.bias))
-        out.append((model.kpts_class,) + A.fold_conv(model.kpts_class.weight, model.kpts_class.bias))
-        return out
+        """[(key, folded w, folded b)] in forward_train's order of first use: specs() folded by eager torch operators."""
+        return [(key,) + autograd.fold_spec(s) for key, s in self.specs()]
 
     def specs(self):
-        """[(key, engine.FoldSpec)]: enumerate()'s layers, same keys, same order, named by their PARAMETERS for autograd.fold_all."""
+        """[(key, engine.FoldSpec)] in forward_train's order of first use: THE inventory of the graph layers, each named by its
+        PARAMETERS (parts are concatenated along the output rows).  Both folds, and through them forward_train, read it."""
         model, S = self.model, engine.FoldSpec
         for p in trainable_parameters(model).values():
             p.requires_grad_(True)
@@ -230,7 +194,7 @@ class TrainWeights(object):
             out.append((m, S('conv', [(m.weight, m.bias)])))
         out.append(('rpn_head', S('conv', [(m.weight, m.bias) for m in (rpn.RPN_cls_score, rpn.RPN_bbox_pred_left_right)])))
         top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
-        out.append(('RCNN_top.0', S('conv', [(top0.weight, top0.bias)])))           # viewed (2048, 1, 1, 49 * 512) by prepare()
+        out.append(('RCNN_top.0', S('conv', [(top0.weight, top0.bias)])))           # viewed (2048, 1, 1, 49 * 512) by fold()
         out.append(('RCNN_top.3', S('conv', [(top3.weight, top3.bias)])))           # 1x1: the linear layer's (out, 1, 1, K)
         out.append(('box_heads', S('linear', [(m.weight, m.bias) for m in (model.RCNN_bbox_pred, model.RCNN_dim_orien_pred,
                                                                           model.RCNN_cls_score)])))
@@ -242,18 +206,26 @@ class TrainWeights(object):
         out.append((model.kpts_class, S('conv', [(model.kpts_class.weight, model.kpts_class.bias)])))
         return out
 
+    def fold(self, device_fold=False):
+        """Every layer folded, without planes (PreparedLayer.planes None: the f16x3 calls make their own).  device_fold: False folds
+        layer by layer with eager torch operators (autograd.fold_spec: what enumerate() returns); True replaces them (per layer a float64 fold, a
+        permute().contiguous(), a torch.cat) by ONE autograd.fold_all over specs() -- two library calls per step, forward and adjoint
+        (csrc/train_fold.hip).  Every folded tensor and every parameter gradient has the same bits either way."""
+        named = self.specs()
+        folded = autograd.fold_all([s for _, s in named]) if device_fold else [autograd.fold_spec(s) for _, s in named]
+        self.layers = {}
+        for (key, _), (w, b) in zip(named, folded):
+            w = w.contiguous()
+            if key == 'RCNN_top.0':
+                w = w.view(int(w.shape[0]), 1, 1, -1)           # the 7x7/7 conv sees one window: a linear layer over (kh, kw, c)
+            self.layers[key] = autograd.PreparedLayer(w, b, None)
+        return self
+
     def prepare(self, device_fold=False):
-        """device_fold: True replaces enumerate()'s eager folds (per layer a float64 fold, a permute().contiguous(), a torch.cat) by
-        ONE autograd.fold_all over the same keys in the same order -- two library calls per step, forward and adjoint
-        (csrc/train_fold.hip).  Every folded tensor and every parameter gradient keeps its bits."""
-        if device_fold:
-            named = self.specs()
-            folded = [(key, w.view(int(w.shape[0]), 1, 1, -1) if key == 'RCNN_top.0' else w, b)
-                      for (key, _), (w, b) in zip(named, autograd.fold_all([s for _, s in named]))]
-        else:
-            folded = [(key, w.contiguous(), b) for key, w, b in self.enumerate()]
-        planes = engine.prepare_train_weights([w for _, w, _ in folded])
-        self.layers = {key: autograd.PreparedLayer(w, b, p) for (key, w, b), p in zip(folded, planes)}
+        """fold(device_fold), then the planes of every folded weight in one engine.prepare_train_weights call."""
+        self.fold(device_fold)
+        planes = engine.prepare_train_weights([layer.w for layer in self.layers.values()])
+        self.layers = {key: layer._replace(planes=p) for (key, layer), p in zip(self.layers.items(), planes)}
         return self
 
 
@@ -346,14 +318,13 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     convolution call in call order.  weights: a
     TrainWeights(model) whose prepare() ran for THIS call (after the last optimiser update): the layers take their folded weights
     and their f16x3 planes from it and the f16x3 calls launch no pass over a weight; layers on the fp32 engine ignore the planes.
-    It composes with every precision and changes no bit."""
+    It composes with every precision and changes no bit.  None: a TrainWeights made and folded for this call, without planes."""
     prec = autograd.Precision(forward_precision, backward_precision, reuse_maxima)
     dev = model.RCNN_toplayer.weight.device
     if dev.type != 'cuda' or not im_left.is_cuda:
         raise NotImplementedError
     tap = _Taps(taps if isinstance(taps, dict) else None)
-    for p in trainable_parameters(model).values():
-        p.requires_grad_(True)
+    wts = weights if weights is not None else TrainWeights(model).fold()     # (specs() switches the trainable parameters' requires_grad on)
     B = int(im_left.shape[0])
     im_info_host = im_info.detach().cpu() if im_info.is_cuda else im_info.detach()
     im_height = float(im_info_host[0][0])
@@ -372,13 +343,11 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         with (torch.no_grad() if frozen else contextlib.nullcontext()):
             for b, blk in enumerate(getattr(model, 'RCNN_layer%d' % li)[0]):
                 x = _bottleneck(blk, x, 'RCNN_layer%d.0.%d' % (li, b), tap, prec.without_graph() if frozen else prec,
-                                None if frozen else weights)
+                                None if frozen else wts)
         c.append(x)
     c2, c3, c4, c5 = c
 
     # ---- top-down (:161-168, 178-185)
-    wts = weights
-    prepared = (lambda key: None) if wts is None else wts.__getitem__
     p5 = _conv(model.RCNN_toplayer, c5, prec, weights=wts)
     p4 = _conv(model.RCNN_smooth1, autograd.upsample_add(p5, _conv(model.RCNN_latlayer1, c4, prec, weights=wts)), prec, weights=wts)
     p3 = _conv(model.RCNN_smooth2, autograd.upsample_add(p4, _conv(model.RCNN_latlayer2, c3, prec, weights=wts)), prec, weights=wts)
@@ -389,14 +358,14 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
 
     # ---- stereo RPN (stereo_rpn.py:73-95)
     rpn = model.RCNN_rpn
-    head_w, head_b = _rpn_head(rpn)
+    head = wts['rpn_head']
     n_anchors = sum(3 * h * w for h, w in shapes)
     probs = torch.empty((B, n_anchors, 2), dtype=torch.float32, device=dev)
     deltas = torch.empty((B, n_anchors, 6), dtype=torch.float32, device=dev)
     scores, bbox_preds, off = [], [], 0
     for l, (p, (h, w)) in enumerate(zip(levels, shapes)):
         r = tap('RPN_Conv.%d' % l, _conv(rpn.RPN_Conv, p, prec, True, weights=wts))     # (2B, h, w, 512): left images, then right
-        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head_w, head_b, _prec=prec, prepared=prepared('rpn_head'))  # [cls 6 | bbox 18]
+        hd = autograd.conv2d_nhwc(torch.cat((r[:B], r[B:]), 3), head.w.permute(0, 3, 1, 2), head.b, _prec=prec, prepared=head)  # [cls 6 | bbox 18]
         # :89,91: NHWC rows viewed as (-1, 2) / (-1, 6) -- the raw scores pair channels (0, 1) (2, 3) (4, 5)
         scores.append(hd[..., :6].reshape(B, h * w * 3, 2))
         bbox_preds.append(hd[..., 6:].reshape(B, h * w * 3, 6))
@@ -433,15 +402,12 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
     # ---- box head (:248-257): 7x7 left | right -> RCNN_top as two GEMMs (the 7x7/7 conv sees one window) -> three linear heads
     left_maps, right_maps = [p[:B] for p in levels[:4]], [p[B:] for p in levels[:4]]
     feat = _roi_feat([left_maps, right_maps], [rois_left, rois_right], im_height, cfg.POOLING_SIZE)
-    top0, top3 = model.RCNN_top[0], model.RCNN_top[3]
-    t = tap('RCNN_top.0', autograd.linear(feat.reshape(n, -1), _top0_weight(top0), top0.bias, relu=True, _prec=prec,
-                                          prepared=prepared('RCNN_top.0')))
+    t = tap('RCNN_top.0', _linear(wts['RCNN_top.0'], feat.reshape(n, -1), prec, relu=True))
     t = _dropout(t, generator, tap, 'dropout1')
-    t = tap('RCNN_top.3', autograd.linear(t, top3.weight.reshape(int(top3.weight.shape[0]), -1), top3.bias, relu=True, _prec=prec,
-                                          prepared=prepared('RCNN_top.3')))
+    t = tap('RCNN_top.3', _linear(wts['RCNN_top.3'], t, prec, relu=True))
     t = _dropout(t, generator, tap, 'dropout2')                                           # .mean(3).mean(2) over a 1x1 map
     n_bbox, n_dim = int(model.RCNN_bbox_pred.weight.shape[0]), int(model.RCNN_dim_orien_pred.weight.shape[0])
-    fc = autograd.linear(t, *_box_heads(model), _prec=prec, prepared=prepared('box_heads'))
+    fc = _linear(wts['box_heads'], t, prec)
     bbox_all, dim_all, cls_score = fc[:, :n_bbox], fc[:, n_bbox:n_bbox + n_dim], fc[:, n_bbox + n_dim:]
     cls_prob = F.softmax(cls_score, 1)
 
@@ -451,7 +417,7 @@ def forward_train(model, im_left, im_right, im_info, gt_boxes_left, gt_boxes_rig
         k = tap('RCNN_kpts.%d' % i, _conv(model.RCNN_kpts[i], k, prec, True, weights=wts))
     up = model.RCNN_kpts[12]
     k = tap('RCNN_kpts.12', autograd.conv_transpose2x2(k, up.weight, up.bias, relu=True, _prec=prec,
-                                                               prepared=prepared('RCNN_kpts.12')))
+                                                               prepared=wts['RCNN_kpts.12']))
     kpts_pred_all = _conv(model.kpts_class, k, prec, weights=wts).sum(1).permute(0, 2, 1).contiguous()       # (n, 28, 28, 6) -> sum over H -> (n, 6, G)
     G = cfg.KPTS_GRID
     kpts_prob = F.softmax(kpts_pred_all[:, :4, :].reshape(n, 4 * G), 1)
