@@ -241,6 +241,11 @@ typedef struct srcnn_conv_desc {
     int up_format, up_H, up_W;
 } srcnn_conv_desc;
 SRCNN_API size_t srcnn_conv2d_workspace_bytes(const srcnn_conv_desc *d);
+/* The plan srcnn_conv2d would launch for d: plan_host[5] = (tile_mr, tile_nr, waves, stages, splits), waves and stages as the
+ * launch table sees them (the engines without tile variants report 4 and 2).  An override the library does not implement for
+ * this convolution is answered by the heuristic plan, never by an error: this is how a caller learns which one ran.  Nothing is
+ * launched and no stream is touched. */
+SRCNN_API int srcnn_conv2d_plan(const srcnn_conv_desc *d, int *plan_host);
 SRCNN_API int srcnn_conv2d(const srcnn_conv_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
 
 /* CHAIN: up to three convolutions over the SAME output rows in ONE launch (SPLIT16 f16x3 engine, SPLIT16 in and out, mode 0,

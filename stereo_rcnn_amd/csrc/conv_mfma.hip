@@ -201,7 +201,7 @@ __global__ void splitk_reduce_kernel(const ConvArgs p, int splits)
 
 static Plan make_plan(int M, int N, int nkt, int mode)
 {
-    Plan pl{1, 1, 1, nkt};
+    Plan pl{1, 1, 1, nkt, 4, 2};   // waves and stages written out: the SPLIT16 launch table switches on them for this plan too
     const long target = 512;   // >= 2 workgroups per CU
     if (!choose_tile_4w(M, N, &pl.mr, &pl.nr)) {
         long blocks = (long)cdiv(M, 64) * cdiv(N, 64);
@@ -377,6 +377,16 @@ int conv_fill_args(const srcnn_conv_desc *d, ConvArgs &a)
     return SRCNN_OK;
 }
 
+// The descriptor's kernel arguments and the plan its launch takes: the one place srcnn_conv2d, its workspace query and its plan
+// query get them from.
+static int conv_args_and_plan(const srcnn_conv_desc *d, ConvArgs &a, Plan &pl)
+{
+    const int rc = conv_fill_args(d, a);
+    if (rc != SRCNN_OK) return rc;
+    pl = plan_for(d, a);
+    return SRCNN_OK;
+}
+
 }  // namespace srcnn
 
 extern "C" {
@@ -385,19 +395,35 @@ size_t srcnn_conv2d_workspace_bytes(const srcnn_conv_desc *d)
 {
     using namespace srcnn;
     ConvArgs a;
-    if (conv_fill_args(d, a) != SRCNN_OK) return 0;
-    Plan pl = plan_for(d, a);
+    Plan pl;
+    if (conv_args_and_plan(d, a, pl) != SRCNN_OK) return 0;
     if (pl.splits <= 1) return 256;
     return align_up((size_t)pl.splits * a.M * a.Cout * sizeof(float), 256);
+}
+
+int srcnn_conv2d_plan(const srcnn_conv_desc *d, int *plan_host)
+{
+    using namespace srcnn;
+    SRCNN_REQUIRE(plan_host, "null pointer");
+    ConvArgs a;
+    Plan pl;
+    const int rc = conv_args_and_plan(d, a, pl);
+    if (rc != SRCNN_OK) return rc;
+    plan_host[0] = pl.mr;
+    plan_host[1] = pl.nr;
+    plan_host[2] = pl.waves == 8 ? 8 : 4;        // what launch_conv_f16s switches on
+    plan_host[3] = pl.stages;
+    plan_host[4] = pl.splits;
+    return SRCNN_OK;
 }
 
 int srcnn_conv2d(const srcnn_conv_desc *d, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
 {
     using namespace srcnn;
     ConvArgs a;
-    int rc = conv_fill_args(d, a);
+    Plan pl;
+    int rc = conv_args_and_plan(d, a, pl);
     if (rc != SRCNN_OK) return rc;
-    Plan pl = plan_for(d, a);
     a.kt_per_split = pl.kt_per_split;
     a.mtiles = cdiv(a.M, 64 * pl.mr);
     a.ntiles = cdiv(a.Cout, 64 * pl.nr);

@@ -551,9 +551,11 @@ def _choose_plan(d, cw, precision, device, plan=None, lim=None):
     choice to the library's heuristic.  plan: the caller's explicit plan, if any (tests, tools, fused launches).  lim: m_limit_mul of
     a row-limited launch -- the limit itself is not in d yet, the tuner puts its own there."""
     if d.up_top and plan is not None and tuple(plan) != (0, 0, 0, 0, 0):
-        # the addition lives in the conv kernel's epilogue of every tile but 256x256, never in the split-K reduction: an explicit
-        # plan is rewritten here (not silently replaced by the library's heuristic), so that the returned plan is the one that ran
-        plan = ((4, 2, 8, 3) if tuple(plan[:2]) == (4, 4) else tuple(plan[:4])) + (1,)
+        # the addition lives in the conv kernel's epilogue of every tile but 256x256 and the 4-wave 256x128 / 128x256 (the tiles
+        # with the vector epilogue only: conv_f16s_plan_ok), never in the split-K reduction: an explicit plan is rewritten here
+        # (not silently replaced by the library's heuristic), so that the returned plan is the one that ran
+        big = tuple(plan[:2]) == (4, 4) or (tuple(plan[:3]) in ((4, 2, 4), (2, 4, 4)))
+        plan = ((4, 2, 8, 3) if big else tuple(plan[:4])) + (1,)
     if d.head_w:                          # the fp32-FMA fused head lives in the 256x256 tile, whatever was asked for
         return (4, 4, 8, 2, 1)
     if plan is not None:                  # explicit
@@ -689,6 +691,15 @@ def conv2d(cw, x, B, H, W, y, OH, OW, x_cstride=None, y_cstride=None, y_coffset=
     ws = _lib.workspace(L.srcnn_conv2d_workspace_bytes(ctypes.byref(d)), x.device, "conv")
     _issue(lambda: L.srcnn_conv2d(ctypes.byref(d), ws.data_ptr(), ws.numel(), _lib.stream()), "srcnn_conv2d", name)
     return used
+
+
+def resolved_plan(d):
+    """The plan (tile_mr, tile_nr, waves, stages, splits) the library launches for the filled descriptor d (srcnn_conv2d_plan).
+    It differs from the plan d asks for where the library does not implement that one for this convolution and answers with its
+    heuristic plan; a zero plan resolves to the heuristic plan itself.  Nothing is launched."""
+    out = (ctypes.c_int * 5)()
+    _lib.check(_lib.lib().srcnn_conv2d_plan(ctypes.byref(d), out), "srcnn_conv2d_plan")
+    return tuple(out)
 
 
 def _fill_train_geometry(d, cw, B, H, W, OH, OW, x_cstride, y_cstride, y_coffset, relu, tile):

@@ -67,6 +67,32 @@ def test_workspace_query_and_argument_errors_without_gpu(lib_path):
     assert L.srcnn_conv2d_chain_supported(2, 8, 2, 2, 2) == 1 and L.srcnn_conv2d_chain_supported(3, 8, 2, 2, 2) == 0
 
 
+def test_conv_plan_query_without_gpu(lib_path):
+    """srcnn_conv2d_plan launches nothing, so the exact-fp32 engine's answers are checkable on a CPU-only host: the heuristic plan
+    has waves 4 and stages 2 written out, an implemented override comes back with its split-K slices as the launch forms them
+    (27 K tiles: 4 slices of 7, 7, 7, 6; a request beyond the K tiles clamps), an override this engine lacks is answered by the
+    heuristic plan, and the workspace query sizes what the plan query reports."""
+    from stereo_rcnn_amd import _lib, engine
+    L = _lib.lib()
+    d = _lib.ConvDesc()
+    d.x, d.w, d.y = 1, 1, 1
+    d.B, d.H, d.W, d.Cin, d.x_cstride = 2, 23, 37, 96, 96
+    d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad = 23, 37, 200, 3, 3, 1, 1
+    d.y_cstride = d.res_cstride = 200
+    M = 2 * 23 * 37
+    heuristic = engine.resolved_plan(d)
+    assert heuristic[:4] == (1, 1, 4, 2) and 1 <= heuristic[4] <= 27 // 8
+    for plan, want in [((2, 2, 4, 2, 4), (2, 2, 4, 2, 4)), ((2, 1, 4, 2, 3), (2, 1, 4, 2, 3)), ((1, 2, 0, 0, 0), (1, 2, 4, 2, 1)),
+                       ((1, 1, 4, 2, 99), (1, 1, 4, 2, 27)), ((4, 4, 8, 2, 1), heuristic), ((2, 2, 8, 4, 1), heuristic)]:
+        engine._set_plan(d, plan)
+        assert engine.resolved_plan(d) == want, plan
+        assert L.srcnn_conv2d_workspace_bytes(ctypes.byref(d)) == (-(-M * 200 * 4 * want[4] // 256) * 256 if want[4] > 1 else 256), plan
+    assert L.srcnn_conv2d_plan(ctypes.byref(d), None) == -1
+    d.Cin = 48
+    with pytest.raises(RuntimeError, match='multiple of 32'):
+        engine.resolved_plan(d)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from stereo_rcnn_amd import _lib
     monkeypatch.setattr(_lib, '_lib', None)

@@ -153,7 +153,19 @@ def test_pyramid_roi_align_fused(dev, A, pad_c):
     assert torch.equal(out2[:37].view(torch.int32), out[:37].view(torch.int32)) and bool((out2[37:].view(torch.int32) == 0x7FC0BEEF).all())
 
 
-def _conv_case(dev, B, H, W, cin, cout, k, stride, pad, relu, res, bn, seed, precision='f32'):
+def _assert_plan_ran(used, desc, nkt, never_split=False, mode1=False):
+    """`used` -- an implemented (tile_mr, tile_nr, waves, stages, splits) request -- is the plan the library launches for the
+    descriptor `desc` filled with it (srcnn_conv2d_plan): the same tile, waves and stages, and the split-K slices plan_for forms from
+    the request over nkt K tiles (one with a second input, the fused top-down addition or mode 1).  A silent fallback to the
+    heuristic plan fails here."""
+    from stereo_rcnn_amd import engine
+    import conv_f16s_cases
+    got = engine.resolved_plan(desc)
+    assert got == conv_f16s_cases.expected_plan(used, nkt, mode1, never_split), (used, got)
+
+
+def _conv_case(dev, B, H, W, cin, cout, k, stride, pad, relu, res, bn, seed, precision='f32', expect_plan=None):
+    """expect_plan ('f16s'): the plan the launch must run with -- both the one conv2d returns and the one the library resolves."""
     from stereo_rcnn_amd import engine
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, cin, H, W, generator=g)
@@ -180,7 +192,11 @@ def _conv_case(dev, B, H, W, cin, cout, k, stride, pad, relu, res, bn, seed, pre
         fo = 1 if cout % 8 == 0 else 0
         xs = engine.act_convert(xd, 0, 1)
         rs = engine.act_convert(rd, 0, 1) if res else None
-        engine.conv2d(cw, xs, B, H, W, y, OH, OW, residual=rs, precision='f16x3', x_fmt=1, y_fmt=fo, res_fmt=1 if res else 0)
+        kw = dict(residual=rs, precision='f16x3', x_fmt=1, y_fmt=fo, res_fmt=1 if res else 0)
+        used = engine.conv2d(cw, xs, B, H, W, y, OH, OW, **kw)
+        if expect_plan is not None:
+            assert tuple(used) == tuple(expect_plan), (used, expect_plan)
+            _assert_plan_ran(used, engine.conv2d(cw, xs, B, H, W, y, OH, OW, plan=used, desc_only=True, **kw), cin * k * k // 32)
         y = engine.act_convert(y, fo, 0) if fo else y
     else:
         engine.conv2d(cw, xd, B, H, W, y, OH, OW, residual=rd, precision=precision)
@@ -219,7 +235,9 @@ def test_conv_engine_vs_torch_cpu(dev, case, precision):
     (1, 12, 40, 32, 64, 1, 1, 0, True, False, True),      # K = 1 tile
 ])
 def test_conv_f16s_every_plan(dev, plan, case):
-    """Forces each launch plan of the DMA-ring kernel (csrc/conv_f16s.hip) instead of the autotuned one."""
+    """Forces each launch plan of the DMA-ring kernel (csrc/conv_f16s.hip) instead of the autotuned one, and asks the library
+    (srcnn_conv2d_plan) that the forced plan is the one it launches: every case here has channel counts the vector epilogue takes,
+    so no instantiation may fall back."""
     from stereo_rcnn_amd import engine
     saved_tuned, saved_flag = dict(engine._TUNED), engine.AUTOTUNE
 
@@ -228,7 +246,7 @@ def test_conv_f16s_every_plan(dev, plan, case):
             return plan
     engine._TUNED = Forced()
     try:
-        _conv_case(dev, *case, seed=11, precision='f16s')
+        _conv_case(dev, *case, seed=11, precision='f16s', expect_plan=plan)
     finally:
         engine._TUNED, engine.AUTOTUNE = saved_tuned, saved_flag
 
@@ -353,7 +371,9 @@ def test_deconv2x2_every_4wave_tile(dev, precision):
 def test_conv_with_projection_shortcut_as_second_operand(dev, plan, case):
     """srcnn_conv_desc.x2 (engine.prep_conv_shortcut): relu(bn3(conv3(t)) + bn_d(downsample(x))) of a bottleneck's first block
     (resnet.py:86-100) as ONE launch over K = [channels of t | channels of x] against torch on the CPU, both BNs folded; every
-    tile plan that may carry it (a split-K or 256x256 request falls back / is ignored: the result must still be right)."""
+    tile plan that may carry it (a split-K or 256x256 request falls back / is ignored: the result must still be right).  The
+    library is asked which plan it launches (srcnn_conv2d_plan): the requested -- or tuned -- tile, waves and stages in one slice,
+    and for the 256x256 request, which conv_f16s_plan_ok refuses with a second input, exactly what the zero plan resolves to."""
     from stereo_rcnn_amd import engine
     B, OH, OW, cin, cin2, cout, s2 = case
     g = torch.Generator().manual_seed(cin + cout + s2)
@@ -371,7 +391,15 @@ def test_conv_with_projection_shortcut_as_second_operand(dev, plan, case):
     ts = engine.act_convert(t.to(dev).permute(0, 2, 3, 1).contiguous(), 0, 1)
     xs = engine.act_convert(x.to(dev).permute(0, 2, 3, 1).contiguous(), 0, 1)
     y = torch.empty((B, OH, OW, cout), device=dev)
-    engine.conv2d(cw, ts, B, OH, OW, y, OH, OW, precision='f16x3', x_fmt=1, y_fmt=1, x2=xs, H2=H2, W2=W2, plan=plan)
+    kw = dict(precision='f16x3', x_fmt=1, y_fmt=1, x2=xs, H2=H2, W2=W2)
+    used = engine.conv2d(cw, ts, B, OH, OW, y, OH, OW, plan=plan, **kw)
+    desc = lambda pl: engine.conv2d(cw, ts, B, OH, OW, y, OH, OW, plan=pl, desc_only=True, **kw)
+    assert plan is None or tuple(used) == plan
+    if tuple(used[:2]) == (4, 4):
+        assert engine.resolved_plan(desc(used)) == engine.resolved_plan(desc((0, 0, 0, 0, 0)))
+    else:
+        assert used[0] > 0, used                                     # the tuner's own choice is a plan, too
+        _assert_plan_ran(used, desc(used), (cin + cin2) // 32, never_split=True)
     got = engine.act_convert(y, 1, 0).permute(0, 3, 1, 2).cpu()
     err = float((got - ref).abs().max())
     assert err < 2e-5 * max(1.0, float(ref.abs().max())), err
@@ -921,13 +949,15 @@ def test_fused_rpn_head_partial_form_equals_two_launches(dev, plan, B, H, W):
 
 
 @pytest.mark.parametrize("plan", [(1, 1, 4, 2, 1), (2, 1, 4, 2, 1), (2, 2, 4, 2, 1), (2, 2, 8, 4, 1), (4, 2, 8, 3, 1), (4, 4, 8, 2, 1), (1, 1, 4, 4, 3),
-                                  None])
+                                  None, (4, 4, 4, 2, 1), (4, 2, 4, 2, 1), (4, 2, 4, 3, 1), (2, 4, 4, 2, 1), (2, 4, 4, 3, 1)])
 @pytest.mark.parametrize("B,H,W,TH,TW,cin", [(2, 38, 125, 19, 63, 64), (2, 11, 17, 6, 9, 96), (1, 5, 1, 3, 1, 32), (1, 7, 9, 7, 9, 32)])
 def test_fused_upsample_add_in_the_lateral_conv_equals_two_launches(dev, plan, B, H, W, TH, TW, cin):
     """srcnn_conv_desc.up_top (the FPN top-down addition of stereo_rcnn.py:91-108 inside the lateral 1x1 conv's epilogue) against
     the two launches it replaces -- srcnn_conv2d into a float32 lateral map, then srcnn_upsample_add: bit-identical, on every tile
-    the kernel has it for (engine.conv2d turns a request for the 256x256 tile into 256x128 and a split-K plan into its unsplit form), odd map
-    sizes (KITTI's 38x125 from 19x63), a one-column map, and a top map of the output's own size (all weights 1 / 0)."""
+    the kernel has it for (engine.conv2d turns a request for a 256x256 tile, or for 256x128 / 128x256 on 4 waves -- the tiles with
+    the vector epilogue only --, into 256x128 on 8 waves and a split-K plan into its unsplit form), odd map
+    sizes (KITTI's 38x125 from 19x63), a one-column map, and a top map of the output's own size (all weights 1 / 0).  The plan
+    conv2d returns is the plan the library launches (srcnn_conv2d_plan): an explicit request is never silently replaced."""
     from stereo_rcnn_amd import _lib, engine
     g = torch.Generator().manual_seed(H * 7 + W)
     S = _lib.FMT_SPLIT16
@@ -942,6 +972,12 @@ def test_fused_upsample_add_in_the_lateral_conv_equals_two_launches(dev, plan, B
     got = torch.zeros_like(want)
     used = engine.conv2d(cw, x, B, H, W, got, H, W, precision='f16x3', x_fmt=S, y_fmt=S, plan=plan, up=(top, TH, TW, S))
     assert used[4] == 1 and used[:2] != (4, 4), used
+    if plan is not None:
+        big = plan[:2] == (4, 4) or plan[:3] in ((4, 2, 4), (2, 4, 4))
+        assert tuple(used) == ((4, 2, 8, 3, 1) if big else plan[:4] + (1,)), (plan, used)
+    assert used[0] > 0, used
+    _assert_plan_ran(used, engine.conv2d(cw, x, B, H, W, got, H, W, precision='f16x3', x_fmt=S, y_fmt=S, plan=used, up=(top, TH, TW, S),
+                                         desc_only=True), cin // 32, never_split=True)
     # the two launches on the plan the fused launch actually ran with (another tile may add the K products in another order)
     used0 = engine.conv2d(cw, x, B, H, W, lat, H, W, precision='f16x3', x_fmt=S, y_fmt=0, plan=used)
     engine.upsample_add(top, TH, TW, lat, B, H, W, C, want, top_fmt=S, y_fmt=S)
