@@ -21,12 +21,18 @@ using namespace boxsolve;
 enum { C_SCORE = 0, C_BOXL = 1, C_BOXR = 5, C_DIM = 9, C_SIN = 12, C_COS = 13, C_KPT = 14, C_BORDER = 17, C_ROI = 19,
        C_ST4 = 20, C_POSE4 = 21, C_ALIGN = 25, C_DISP = 26, C_POSE = 27, C_ALPHA = 31 };
 
+// rows in use: the record's count word, at most the n rows it has room for
+SRCNN_HD int record_rows(const float *rec, int n)
+{
+    return min((int)rec[0], n);
+}
+
 // kitti_utils.py:398-437 + demo.py:261-265.  One workgroup per image record: phase 1, one thread per image column walks the
 // detections in order (a column's "depth line" value only depends on the boxes that cover it, in their order); phase 2, one
 // thread per detection scans its columns; the replacement test of demo.py follows.
 __global__ void infer_boundary_kernel(float *__restrict__ rec, int n, int cols, int im_w, double *__restrict__ line)
 {
-    const int k = min((int)rec[0], n);
+    const int k = record_rows(rec, n);
     for (int col = threadIdx.x; col <= im_w; col += blockDim.x) {
         double pixel = 0.0;
         for (int i = 0; i < k; ++i) {
@@ -64,52 +70,44 @@ struct Calib {
     int im_h, im_w;
 };
 
-SRCNN_HD inline void load5(const float *p, double *o)
+SRCNN_HD void load5(const float *p, double *o)
 {
     for (int i = 0; i < 5; ++i) o[i] = (double)p[i];
 }
 
+// Who runs a record row.  ScalarLane: one thread (lane 0 of the scalar kernels, a host thread) runs box_solver.h's solver and stores.
+// WaveLane: all 64 lanes of the workgroup's one wavefront run the row (same loads, same control flow) with the residuals of every
+// cost / gradient evaluation across them (box_solver_wave.h); lane 0 stores.
+struct ScalarLane {
+    static constexpr bool DISP_FIRST = true;       // solve3_row stores the disparity before the solve, as the scalar form always did
+    SRCNN_HD bool writer() const { return true; }
+    SRCNN_HD int solve4(const Calib &c, double alpha, const double *dim, const double *bl, const double *br, const double *kp,
+                        double *st) const
+    { return solve_4dof(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, br, kp, st, nullptr, true); }
+    SRCNN_HD double solve3(const Calib &c, double alpha, const double *dim, const double *bl, double dis, const double *kp,
+                           double *st) const
+    { return solve_3dof(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, dis, kp, st, nullptr); }
+};
+
+struct WaveLane {
+    static constexpr bool DISP_FIRST = false;
+    int lane;
+    __device__ bool writer() const { return lane == 0; }
+    __device__ int solve4(const Calib &c, double alpha, const double *dim, const double *bl, const double *br, const double *kp,
+                          double *st) const
+    { return solve_4dof_wave(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, br, kp, st, true, lane); }
+    __device__ double solve3(const Calib &c, double alpha, const double *dim, const double *bl, double dis, const double *kp,
+                             double *st) const
+    { return solve_3dof_wave(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, dis, kp, st, lane); }
+};
+
 // demo.py:282-302 for detection i of a record: (status, x, y, z, theta), poses kept in float32 as `poses_all`.
 // Host and device run this same function (the host build through srcnn_solve_4dof_records_host).
-SRCNN_HD inline void solve4_row(float *rec, int n, int cols, const Calib &c, float eval_thresh, double *state4, int i)
+template <class Who>
+SRCNN_HD void solve4_row(float *rec, int n, int cols, const Calib &c, float eval_thresh, double *state4, const Who &who, int i)
 {
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
-    float *row = rec + (size_t)(1 + i) * cols;
-    double *out = state4 + (size_t)i * 4;
-    out[0] = out[1] = out[2] = out[3] = 0.0;
-    if (i >= k) return;
-    row[C_ST4] = 0.f;
-    row[C_ALIGN] = 0.f;
-    if (!(row[C_SCORE] > eval_thresh)) return;
-    double bl[5], br[5], dim[5], kp[5];
-    load5(row + C_BOXL, bl);
-    load5(row + C_BOXR, br);
-    load5(row + C_DIM, dim);
-    load5(row + C_KPT, kp);
-    const double alpha = atan2((double)row[C_SIN], (double)row[C_COS]);          // demo.py:288-290
-    double st[4];
-    const int status = solve_4dof(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, br, kp, st, nullptr, true);
-    for (int q = 0; q < 4; ++q) out[q] = st[q];
-    row[C_ST4] = (float)status;
-    for (int q = 0; q < 4; ++q) row[C_POSE4 + q] = (float)st[q];                  // poses[0..2], poses[6]
-    for (int q = 0; q < 4; ++q) row[C_POSE + q] = (float)st[q];
-    row[C_ALPHA] = (float)alpha;                                                  // poses[7]
-}
-
-__global__ void solve4_kernel(float *__restrict__ rec, int n, int cols, Calib c, float eval_thresh, double *__restrict__ state4)
-{
-    if (threadIdx.x == 0) solve4_row(rec, n, cols, c, eval_thresh, state4, blockIdx.x);
-}
-
-// solve4_row with the residuals of every evaluation across the lanes of the workgroup's one wavefront: all 64 lanes run the
-// row (same loads, same control flow), lane 0 stores.  __launch_bounds__(64): the optimiser state of four nested line-search
-// levels wants ~200 VGPRs; at the default bound (1024 threads, 128 VGPRs) the scalar kernel spills 94 of them to scratch.
-__global__ void __launch_bounds__(64) solve4_wave_kernel(float *__restrict__ rec, int n, int cols, Calib c, float eval_thresh,
-                                                         double *__restrict__ state4)
-{
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const bool writer = lane == 0;
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
+    const bool writer = who.writer();
+    const int k = record_rows(rec, n);
     float *row = rec + (size_t)(1 + i) * cols;
     double *out = state4 + (size_t)i * 4;
     if (writer) out[0] = out[1] = out[2] = out[3] = 0.0;
@@ -120,17 +118,30 @@ __global__ void __launch_bounds__(64) solve4_wave_kernel(float *__restrict__ rec
     load5(row + C_BOXR, br);
     load5(row + C_DIM, dim);
     load5(row + C_KPT, kp);
-    const double alpha = atan2((double)row[C_SIN], (double)row[C_COS]);
-    if (writer) row[C_ST4] = row[C_ALIGN] = 0.f;
+    const double alpha = atan2((double)row[C_SIN], (double)row[C_COS]);          // demo.py:288-290
+    if (writer) row[C_ST4] = row[C_ALIGN] = 0.f;      // after the loads: every lane reads the row, one lane writes it
     if (!scored) return;
     double st[4];
-    const int status = solve_4dof_wave(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, br, kp, st, true, lane);
+    const int status = who.solve4(c, alpha, dim, bl, br, kp, st);
     if (!writer) return;
     for (int q = 0; q < 4; ++q) out[q] = st[q];
     row[C_ST4] = (float)status;
-    for (int q = 0; q < 4; ++q) row[C_POSE4 + q] = (float)st[q];
+    for (int q = 0; q < 4; ++q) row[C_POSE4 + q] = (float)st[q];                  // poses[0..2], poses[6]
     for (int q = 0; q < 4; ++q) row[C_POSE + q] = (float)st[q];
-    row[C_ALPHA] = (float)alpha;
+    row[C_ALPHA] = (float)alpha;                                                  // poses[7]
+}
+
+__global__ void solve4_kernel(float *__restrict__ rec, int n, int cols, Calib c, float eval_thresh, double *__restrict__ state4)
+{
+    if (threadIdx.x == 0) solve4_row(rec, n, cols, c, eval_thresh, state4, ScalarLane{}, blockIdx.x);
+}
+
+// __launch_bounds__(64): the optimiser state of four nested line-search levels wants ~200 VGPRs; at the default bound (1024
+// threads, 128 VGPRs) the scalar kernel spills 94 of them to scratch.
+__global__ void __launch_bounds__(64) solve4_wave_kernel(float *__restrict__ rec, int n, int cols, Calib c, float eval_thresh,
+                                                         double *__restrict__ state4)
+{
+    solve4_row(rec, n, cols, c, eval_thresh, state4, WaveLane{(int)threadIdx.x}, blockIdx.x);
 }
 
 // gather of what align_parallel takes (demo.py:306-308): boxes (n,4), borders (n,2), poses (n,7), valid (n)
@@ -139,7 +150,7 @@ __global__ void align_inputs_kernel(const float *__restrict__ rec, int n, int co
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int k = min((int)rec[0], n);
+    const int k = record_rows(rec, n);
     const float *row = rec + (size_t)(1 + i) * cols;
     const bool ok = i < k && row[C_ST4] > 0.f;
     valid[i] = ok ? 1.f : 0.f;
@@ -156,26 +167,29 @@ __global__ void align_inputs_kernel(const float *__restrict__ rec, int n, int co
 }
 
 // demo.py:311-319: objects the alignment succeeded on are re-solved with z fixed by the aligned disparity
-SRCNN_HD inline void solve3_row(float *rec, int n, int cols, const Calib &c, const float *align_status, const float *best_dis,
-                                double *state, int i)
+template <class Who>
+SRCNN_HD void solve3_row(float *rec, int n, int cols, const Calib &c, const float *align_status, const float *best_dis,
+                         double *state, const Who &who, int i)
 {
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
-    if (i >= k) return;
+    const bool writer = who.writer();
+    if (i >= record_rows(rec, n)) return;
     float *row = rec + (size_t)(1 + i) * cols;
     double *out = state + (size_t)i * 4;
     if (!(row[C_ST4] > 0.f)) return;
     const float ast = align_status ? align_status[i] : 0.f;
-    row[C_ALIGN] = ast;
+    if (writer) row[C_ALIGN] = ast;
     if (!(ast > 0.f)) return;            // (ast < 0: lattice overflow, reported to the host through the record)
-    row[C_DISP] = best_dis[i];
+    const float dis = best_dis[i];
+    if (Who::DISP_FIRST) row[C_DISP] = dis;
     double bl[5], dim[5], kp[5];
     load5(row + C_BOXL, bl);
     load5(row + C_DIM, dim);
     load5(row + C_KPT, kp);
     double st[3];
     // alpha and dim are read back from the float32 `poses_all` (demo.py:313-316)
-    const double z = solve_3dof(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, (double)row[C_ALPHA], dim, bl, (double)best_dis[i], kp,
-                                st, nullptr);
+    const double z = who.solve3(c, (double)row[C_ALPHA], dim, bl, (double)dis, kp, st);
+    if (!writer) return;
+    if (!Who::DISP_FIRST) row[C_DISP] = dis;
     out[0] = st[0]; out[1] = st[1]; out[2] = z; out[3] = st[2];
     for (int q = 0; q < 4; ++q) row[C_POSE + q] = (float)out[q];
 }
@@ -183,36 +197,14 @@ SRCNN_HD inline void solve3_row(float *rec, int n, int cols, const Calib &c, con
 __global__ void solve3_kernel(float *__restrict__ rec, int n, int cols, Calib c, const float *__restrict__ align_status,
                               const float *__restrict__ best_dis, double *__restrict__ state)
 {
-    if (threadIdx.x == 0) solve3_row(rec, n, cols, c, align_status, best_dis, state, blockIdx.x);
+    if (threadIdx.x == 0) solve3_row(rec, n, cols, c, align_status, best_dis, state, ScalarLane{}, blockIdx.x);
 }
 
-// solve3_row, residuals across lanes (see solve4_wave_kernel)
 __global__ void __launch_bounds__(64) solve3_wave_kernel(float *__restrict__ rec, int n, int cols, Calib c,
                                                          const float *__restrict__ align_status,
                                                          const float *__restrict__ best_dis, double *__restrict__ state)
 {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const bool writer = lane == 0;
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
-    if (i >= k) return;
-    float *row = rec + (size_t)(1 + i) * cols;
-    double *out = state + (size_t)i * 4;
-    if (!(row[C_ST4] > 0.f)) return;
-    const float ast = align_status ? align_status[i] : 0.f;
-    if (writer) row[C_ALIGN] = ast;
-    if (!(ast > 0.f)) return;
-    const float dis = best_dis[i];
-    double bl[5], dim[5], kp[5];
-    load5(row + C_BOXL, bl);
-    load5(row + C_DIM, dim);
-    load5(row + C_KPT, kp);
-    const double alpha = (double)row[C_ALPHA];
-    double st[3];
-    const double z = solve_3dof_wave(c.im_h, c.im_w, c.f, c.cx, c.cy, c.base, alpha, dim, bl, (double)dis, kp, st, lane);
-    if (!writer) return;
-    row[C_DISP] = dis;
-    out[0] = st[0]; out[1] = st[1]; out[2] = z; out[3] = st[2];
-    for (int q = 0; q < 4; ++q) row[C_POSE + q] = (float)out[q];
+    solve3_row(rec, n, cols, c, align_status, best_dis, state, WaveLane{(int)threadIdx.x}, blockIdx.x);
 }
 
 // rows [0, n) of a host record over host threads: one per 8 rows, at most 16 -- and at most `threads` when the caller gives a budget
@@ -369,9 +361,9 @@ int srcnn_solve_4dof_records_host(float *rec, int n, int rec_cols, int im_h, int
     using namespace srcnn;
     SRCNN_REQUIRE(rec && state4 && n > 0 && rec_cols >= SRCNN_REC_COLS, "bad args (rec_cols >= SRCNN_REC_COLS)");
     const Calib c = make_calib(im_h, im_w, p2_00, p2_02, p2_12, p2_03_minus_p3_03);
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
+    const int k = record_rows(rec, n);
     for (int i = k > 0 ? k : 0; i < n; ++i) state4[(size_t)i * 4] = state4[(size_t)i * 4 + 1] = state4[(size_t)i * 4 + 2] = state4[(size_t)i * 4 + 3] = 0.0;
-    host_rows(k, threads, [&](int i) { solve4_row(rec, n, rec_cols, c, eval_thresh, state4, i); });
+    host_rows(k, threads, [&](int i) { solve4_row(rec, n, rec_cols, c, eval_thresh, state4, ScalarLane{}, i); });
     return SRCNN_OK;
 }
 
@@ -383,8 +375,8 @@ int srcnn_solve_3dof_records_host(float *rec, int n, int rec_cols, int im_h, int
     SRCNN_REQUIRE(rec && state && n > 0 && rec_cols >= SRCNN_REC_COLS, "bad args (rec_cols >= SRCNN_REC_COLS)");
     SRCNN_REQUIRE((align_status == nullptr) == (best_dis == nullptr), "align_status and best_dis come together");
     const Calib c = make_calib(im_h, im_w, p2_00, p2_02, p2_12, p2_03_minus_p3_03);
-    const int k = (int)rec[0] < n ? (int)rec[0] : n;
-    host_rows(k, threads, [&](int i) { solve3_row(rec, n, rec_cols, c, align_status, best_dis, state, i); });
+    const int k = record_rows(rec, n);
+    host_rows(k, threads, [&](int i) { solve3_row(rec, n, rec_cols, c, align_status, best_dis, state, ScalarLane{}, i); });
     return SRCNN_OK;
 }
 

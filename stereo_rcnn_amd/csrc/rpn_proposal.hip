@@ -16,11 +16,14 @@
 //   3-4. batched NMS        (nms.hip) over 2*B problems, left/right in lockstep with joint early exit.
 //   5. intersect_pad_kernel sorted-set intersection, first `post` rows, zero padding.
 #include "common.h"
+#include "box_decode.h"
+#include "rpn_score.h"
 
 namespace srcnn {
 
 // ------------------------------------------------------------------ RPN scoring
-// head rows: [0,6) cls logits, [6,24) deltas.  probs index (b, off + loc*3 + a, {0,1}).
+// head rows: [0,6) cls logits, [6,24) deltas.  probs index (b, off + loc*3 + a, {0,1}).  The per-location arithmetic of all three
+// kernels is rpn_score.h's rpn_pair_softmax_store.
 __global__ void rpn_score_kernel(const float *__restrict__ head, int B, int hw, int hcs, float *__restrict__ probs,
                                  float *__restrict__ deltas, int level_off, int a_total)
 {
@@ -28,28 +31,13 @@ __global__ void rpn_score_kernel(const float *__restrict__ head, int B, int hw, 
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += blockDim.x * gridDim.x) {
         const int b = idx / hw, loc = idx - b * hw;
         const float *h = head + (size_t)idx * hcs;
-        float pr[6];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {   // softmax over the channel pair (c, c+3)  (stereo_rpn.py:81-83)
-            const float s0 = h[c], s1 = h[c + 3];
-            const float m = fmaxf(s0, s1);
-            const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-            const float sum = e0 + e1;
-            pr[c] = e0 / sum;
-            pr[c + 3] = e1 / sum;
-        }
         const size_t base = (size_t)b * a_total + level_off + (size_t)loc * 3;
-        float *po = probs + base * 2;      // NHWC flatten pairs CONSECUTIVE channels (:89-90)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) po[c] = pr[c];
-        float *dl = deltas + base * 6;
-#pragma unroll
-        for (int c = 0; c < 18; ++c) dl[c] = h[6 + c];
+        rpn_pair_softmax_store(h, probs + base * 2, deltas + base * 6);
     }
 }
 
 // All pyramid levels in ONE launch (the five per-level launches sat at the ~5 us launch floor): the level of a location is found
-// from the cumulative location counts; per location the arithmetic is rpn_score_kernel's, expression for expression.
+// from the cumulative location counts.
 struct RpnLevels {
     const float *head[5];
     int cum[6];        // cumulative locations per image: level l owns [cum[l], cum[l + 1])
@@ -63,27 +51,10 @@ __global__ void rpn_score_levels_kernel(RpnLevels lv, int B, int hcs, float *__r
     const int total = B * per;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += blockDim.x * gridDim.x) {
         const int b = idx / per, g = idx - b * per;
-        int l = 0;
-        while (l + 1 < lv.n && g >= lv.cum[l + 1]) ++l;
+        const int l = level_of(lv.cum, lv.n, g);
         const int hw = lv.cum[l + 1] - lv.cum[l], loc = g - lv.cum[l];
-        const float *h = lv.head[l] + ((size_t)b * hw + loc) * hcs;
-        float pr[6];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float s0 = h[c], s1 = h[c + 3];
-            const float m = fmaxf(s0, s1);
-            const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-            const float sum = e0 + e1;
-            pr[c] = e0 / sum;
-            pr[c + 3] = e1 / sum;
-        }
         const size_t base = (size_t)b * a_total + ((size_t)lv.cum[l] + loc) * 3;     // anchors of a level start at 3 x its first location
-        float *po = probs + base * 2;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) po[c] = pr[c];
-        float *dl = deltas + base * 6;
-#pragma unroll
-        for (int c = 0; c < 18; ++c) dl[c] = h[6 + c];
+        rpn_pair_softmax_store(lv.head[l] + ((size_t)b * hw + loc) * hcs, probs + base * 2, deltas + base * 6);
     }
 }
 
@@ -104,8 +75,7 @@ __global__ void rpn_score_parts_kernel(RpnParts lv, int B, const float *__restri
     const int total = B * per;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += blockDim.x * gridDim.x) {
         const int b = idx / per, g = idx - b * per;
-        int l = 0;
-        while (l + 1 < lv.n && g >= lv.cum[l + 1]) ++l;
+        const int l = level_of(lv.cum, lv.n, g);
         const int hw = lv.cum[l + 1] - lv.cum[l], loc = g - lv.cum[l];
         const float *p0 = lv.part[l] + ((size_t)b * hw + loc) * 24;
         float h[24];
@@ -118,23 +88,8 @@ __global__ void rpn_score_parts_kernel(RpnParts lv, int B, const float *__restri
             }
             h[c] = s.x + bias[c]; h[c + 1] = s.y + bias[c + 1]; h[c + 2] = s.z + bias[c + 2]; h[c + 3] = s.w + bias[c + 3];
         }
-        float pr[6];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float s0 = h[c], s1 = h[c + 3];
-            const float m = fmaxf(s0, s1);
-            const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-            const float sum = e0 + e1;
-            pr[c] = e0 / sum;
-            pr[c + 3] = e1 / sum;
-        }
         const size_t base = (size_t)b * a_total + ((size_t)lv.cum[l] + loc) * 3;
-        float *po = probs + base * 2;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) po[c] = pr[c];
-        float *dl = deltas + base * 6;
-#pragma unroll
-        for (int c = 0; c < 18; ++c) dl[c] = h[6 + c];
+        rpn_pair_softmax_store(h, probs + base * 2, deltas + base * 6);
     }
 }
 
@@ -363,24 +318,6 @@ struct LevelTable {
     int nl;
 };
 
-__device__ __forceinline__ void decode_one(const float ax1, const float ay1, const float ax2, const float ay2,
-                                           float dx, float dy, float dw, float dh, float wmax, float hmax, float *o)
-{
-    // bbox_transform.py:81-104, float32, one rounding per operation (no contraction)
-    const float widths = ax2 - ax1 + 1.0f;
-    const float heights = ay2 - ay1 + 1.0f;
-    const float ctr_x = ax1 + 0.5f * widths;
-    const float ctr_y = ay1 + 0.5f * heights;
-    const float pcx = dx * widths + ctr_x;
-    const float pcy = dy * heights + ctr_y;
-    const float pw = expf(dw) * widths;
-    const float ph = expf(dh) * heights;
-    o[0] = fminf(fmaxf(pcx - 0.5f * pw, 0.f), wmax);   // clip_boxes :177-185
-    o[1] = fminf(fmaxf(pcy - 0.5f * ph, 0.f), hmax);
-    o[2] = fminf(fmaxf(pcx + 0.5f * pw, 0.f), wmax);
-    o[3] = fminf(fmaxf(pcy + 0.5f * ph, 0.f), hmax);
-}
-
 // dets: (B, 2, n, 5): [b][0] = left, [b][1] = right
 __global__ void gather_decode_kernel(const float *__restrict__ probs, const float *__restrict__ deltas, int A, int B,
                                      int n, int K, const int *__restrict__ order, LevelTable lt,
@@ -390,8 +327,7 @@ __global__ void gather_decode_kernel(const float *__restrict__ probs, const floa
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += blockDim.x * gridDim.x) {
         const int b = idx / n, r = idx - b * n;
         const int ai = order[(size_t)b * K + r];
-        int l = 0;
-        while (l + 1 < lt.nl && ai >= lt.off[l + 1]) ++l;
+        const int l = level_of(lt.off, lt.nl, ai);
         const int local = ai - lt.off[l];
         const int a = local % 3, loc = local / 3;
         const int x = loc % lt.w[l], y = loc / lt.w[l];
@@ -403,8 +339,8 @@ __global__ void gather_decode_kernel(const float *__restrict__ probs, const floa
         const float score = probs[((size_t)b * A + ai) * 2 + 1];
         float *ol = dets + (((size_t)b * 2 + 0) * n + r) * 5;
         float *orr = dets + (((size_t)b * 2 + 1) * n + r) * 5;
-        decode_one(ax1, ay1, ax2, ay2, d[0], d[1], d[2], d[3], wmax, hmax, ol);     // left : (dx, dy, dw, dh)
-        decode_one(ax1, ay1, ax2, ay2, d[4], d[1], d[5], d[3], wmax, hmax, orr);    // right: (dx_r, dy, dw_r, dh)
+        decode_clip_box(ax1, ay1, ax2, ay2, d[0], d[1], d[2], d[3], wmax, hmax, ol);     // left : (dx, dy, dw, dh)
+        decode_clip_box(ax1, ay1, ax2, ay2, d[4], d[1], d[5], d[3], wmax, hmax, orr);    // right: (dx_r, dy, dw_r, dh)
         ol[4] = score;
         orr[4] = score;
     }

@@ -258,7 +258,8 @@ def test_gather_rows_across_a_block(dev):
     idx = rng.integers(0, 50, 37).astype(np.int32)
     idx[[0, 20, 36]] = -1
     dst = _canary((38, 7), dev)
-    _lib.check(L.srcnn_gather_rows(_d(src, dev).data_ptr(), _d(idx, dev).data_ptr(), 37, 7, dst.data_ptr(), _lib.stream()))
+    srcd, idxd = _d(src, dev), _d(idx, dev)                   # both alive across the call: a freed temporary's block may be handed out again
+    _lib.check(L.srcnn_gather_rows(srcd.data_ptr(), idxd.data_ptr(), 37, 7, dst.data_ptr(), _lib.stream()))
     dst = dst.cpu().numpy()
     assert np.array_equal(_bits(dst[:37]), _bits(src[np.maximum(idx, 0)])) and (dst[37] == CANARY).all()
 
@@ -372,7 +373,8 @@ def test_nms_batched_with_differing_valid_counts(dev, n_valid):
     keep, num = _canary((nb, n), dev, torch.int32, -5), _canary((nb + 1,), dev, torch.int32, -5)
     need = L.srcnn_nms_batched_workspace_bytes(nb, n)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _lib.check(L.srcnn_nms_batched(keep.data_ptr(), _d(dets, dev).data_ptr(), num.data_ptr(), _d(np.array(n_valid, np.int32), dev).data_ptr(),
+    detsd, nvd = _d(dets, dev), _d(np.array(n_valid, np.int32), dev)      # both alive across the call (see test_gather_rows_across_a_block)
+    _lib.check(L.srcnn_nms_batched(keep.data_ptr(), detsd.data_ptr(), num.data_ptr(), nvd.data_ptr(),
                                    nb, n, 5, 0.7, ws.data_ptr(), need, _lib.stream()))
     keep, num = keep.cpu().numpy(), num.cpu().numpy()
     assert num[nb] == -5
@@ -674,3 +676,52 @@ def test_rpn_score_levels_and_parts_vs_float64(dev, B):
     for h, hw in zip(sums, LEVEL_HW):
         _rpn_check('small.rpn_score_parts / bound', pr[:B], dl[:B], h, slice(off, off + 3 * hw))
         off += 3 * hw
+
+
+def test_rpn_score_forms_write_identical_bits(dev):
+    """The three RPN score entry points run one body (csrc/rpn_score.h): srcnn_rpn_score per level, srcnn_rpn_score_levels, and
+    srcnn_rpn_score_parts with one plane per level and an all-zero bias write the same bits to probs and deltas; so does _parts
+    with a second, all-zero plane behind padding.  (x + 0.0f == x bit for bit unless x is -0.0, which normal deviates are not.)
+    Levels of 6, 2 and 1 locations: the last is a single location at the end of the level search."""
+    _lib, L = _L()
+    B, level_hw = 2, [6, 2, 1]
+    nl, A = len(level_hw), 3 * sum(level_hw)
+    assert A == 27
+    rng = np.random.default_rng(77)
+    heads = [rng.normal(0, 4, (B, hw, 24)).astype(np.float32) for hw in level_hw]
+    assert not any(np.signbit(h[h == 0]).any() for h in heads)
+    hd = [_d(h, dev) for h in heads]
+    hws = (ctypes.c_int * nl)(*level_hw)
+    new = lambda: (_canary((B + 1, A, 2), dev), _canary((B + 1, A, 6), dev))
+    got = {}
+    pr, dl = new()
+    off = 0
+    for t, hw in zip(hd, level_hw):
+        _lib.check(L.srcnn_rpn_score(t.data_ptr(), B, hw, 24, pr.data_ptr(), dl.data_ptr(), off, A, _lib.stream()))
+        off += 3 * hw
+    got['per level'] = (pr.cpu().numpy(), dl.cpu().numpy())
+    pr, dl = new()
+    ptrs = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in hd])
+    _lib.check(L.srcnn_rpn_score_levels(ptrs, hws, nl, B, 24, pr.data_ptr(), dl.data_ptr(), A, _lib.stream()))
+    got['levels'] = (pr.cpu().numpy(), dl.cpu().numpy())
+    bias = torch.zeros(24, dtype=torch.float32, device=dev)
+    for planes in (1, 2):
+        bufs, sizes = [], []
+        for h, hw in zip(heads, level_hw):
+            plane = B * hw * 24 + (8 if planes == 2 else 0)              # padding between the planes
+            buf = np.full((planes, plane), 1e6, np.float32)
+            buf[0, :B * hw * 24] = h.ravel()
+            if planes == 2:
+                buf[1, :B * hw * 24] = 0.0
+            bufs.append(_d(buf, dev))
+            sizes.append(plane)
+        pr, dl = new()
+        pp = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in bufs])
+        npp = (ctypes.c_int * nl)(*([planes] * nl))
+        pl = (ctypes.c_longlong * nl)(*sizes)
+        _lib.check(L.srcnn_rpn_score_parts(pp, npp, pl, hws, nl, B, bias.data_ptr(), pr.data_ptr(), dl.data_ptr(), A, _lib.stream()))
+        got['parts, %d plane(s)' % planes] = (pr.cpu().numpy(), dl.cpu().numpy())
+    p0, d0 = got['per level']
+    assert (p0[B] == CANARY).all() and (d0[B] == CANARY).all() and (p0[:B] != CANARY).all() and (d0[:B] != CANARY).all()
+    for name, (p, d) in got.items():
+        assert np.array_equal(_bits(p), _bits(p0)) and np.array_equal(_bits(d), _bits(d0)), name
