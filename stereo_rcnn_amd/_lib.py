@@ -170,7 +170,7 @@ globals().update(HEADER.constants)                                      # FMT_F3
 globals().update((s.__name__, s) for s in HEADER.structs.values())      # ConvDesc, ConvBwdDesc, KittiSplit, PrepLayer, ...
 _SIGNATURES = HEADER.signatures
 
-EXTENSIONS = ("srcnn_train_weights.h", "srcnn_train_fold.h")        # include/: headers on top of srcnn_hip.h (the module docstring)
+EXTENSIONS = ("srcnn_train_weights.h", "srcnn_train_fold.h", "srcnn_optim_guard.h")        # include/: headers on top of srcnn_hip.h (the module docstring)
 
 
 def _read_extensions():

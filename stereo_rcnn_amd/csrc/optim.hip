@@ -20,7 +20,13 @@
 //            four wavefront sums ((w0 + w1) + w2) + w3 and writes workspace[chunk number in the whole list];
 //   stage 2  one workgroup, float64: thread t adds workspace[t], workspace[t + 256], .. in that order starting from 0, the same
 //            butterfly and four-term sum in double; thread 0 writes (float)sqrt(sum) and the coefficient.
+//
+// srcnn_grad_norm_guarded / srcnn_sgd_step_guarded (include/srcnn_optim_guard.h) are the same two passes over gradients that
+// several backward passes summed: every gradient enters as g * grad_scale, the norm leaves a third word (1 where it is finite), and
+// the update runs only under that word, so one Inf or NaN in a gradient costs one step and not the run.
 #include "layer_list.h"
+
+#include "../../include/srcnn_optim_guard.h"
 
 #include <climits>
 #include <cmath>
@@ -227,6 +233,138 @@ __global__ __launch_bounds__(OPT_THREADS) void sgd_step_kernel(StepArgs a)
     }
 }
 
+// ---- the guarded pair (include/srcnn_optim_guard.h): the kernels above with g * scale in the place of g, the norm's finiteness
+// as a third word, and the update under that word.  They stand beside the kernels above, which keep their code.
+
+__global__ __launch_bounds__(OPT_THREADS) void grad_norm_guarded_partial_kernel(GradArgs a, float scale, float *__restrict__ partial)
+{
+    __shared__ float red[OPT_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int total = a.chunk_end[a.n - 1];
+    for (int c = blockIdx.x; c < total; c += gridDim.x) {
+        const int i = first_run_above(a.chunk_end, a.n, c);
+        const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
+        const float *g = a.t[i].g + start;
+        const long long left = a.t[i].numel - start;
+        const bool vec = a.vec[i] != 0;
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < OPT_PER_THREAD; ++j) {
+            const int e = (j * OPT_THREADS + tid) * 4;
+            if (vec && e + 4 <= left) {
+                float4 v = *reinterpret_cast<const float4 *>(g + e);
+                v.x = __fmul_rn(v.x, scale), v.y = __fmul_rn(v.y, scale), v.z = __fmul_rn(v.z, scale), v.w = __fmul_rn(v.w, scale);
+                s = __fadd_rn(s, __fmul_rn(v.x, v.x));
+                s = __fadd_rn(s, __fmul_rn(v.y, v.y));
+                s = __fadd_rn(s, __fmul_rn(v.z, v.z));
+                s = __fadd_rn(s, __fmul_rn(v.w, v.w));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e + k < left) {
+                        const float x = __fmul_rn(g[e + k], scale);
+                        s = __fadd_rn(s, __fmul_rn(x, x));
+                    }
+            }
+        }
+        s = wave_sum_f32(s);
+        if ((tid & 63) == 0) red[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) partial[a.chunk_base + c] = __fadd_rn(__fadd_rn(__fadd_rn(red[0], red[1]), red[2]), red[3]);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void grad_norm_guarded_finish_kernel(const float *__restrict__ partial, long long count,
+                                                                                float clip_norm, float *__restrict__ out)
+{
+    __shared__ double red[OPT_THREADS / 64];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (long long i = tid; i < count; i += OPT_THREADS) s = s + (double)partial[i];
+    s = wave_sum_f64(s);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        const float norm = (float)sqrt(((red[0] + red[1]) + red[2]) + red[3]);
+        out[0] = norm;
+        // clip_norm = +inf says "do not clip": inf / inf would be NaN
+        out[1] = isinf(clip_norm) ? 1.0f : __fdiv_rn(clip_norm, norm > clip_norm ? norm : clip_norm);
+        out[2] = isfinite(norm) ? 1.0f : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void sgd_step_guarded_kernel(StepArgs a, float scale, const float *__restrict__ ok,
+                                                                        unsigned *skipped)
+{
+    const int tid = threadIdx.x;
+    const int total = a.chunk_end[a.n - 1];
+    const bool use_m = a.momentum != 0.0f, first = a.first_step != 0;
+    if (*ok == 0.0f) {                                               // the same word for every thread of the grid: a uniform branch
+        if (skipped && blockIdx.x == 0 && tid == 0) *skipped = *skipped + 1u;
+        if (!(use_m && first)) return;
+        // uninitialised momentum buffers: zeros, so that the next step's momentum * m + d is the d a first step stores
+        for (int c = blockIdx.x; c < total; c += gridDim.x) {
+            const int i = first_run_above(a.chunk_end, a.n, c);
+            const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
+            const long long left = a.t[i].numel - start;
+            float *m = a.t[i].m + start;
+            const bool vec = (a.t[i].flags & OPT_VEC) != 0;
+#pragma unroll
+            for (int j = 0; j < OPT_PER_THREAD; ++j) {
+                const int e = (j * OPT_THREADS + tid) * 4;
+                if (vec && e + 4 <= left) {
+                    *reinterpret_cast<float4 *>(m + e) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (e + q < left) m[e + q] = 0.0f;
+                }
+            }
+        }
+        return;
+    }
+    const float coef = a.coef ? *a.coef : 1.0f;
+    for (int c = blockIdx.x; c < total; c += gridDim.x) {
+        const int i = first_run_above(a.chunk_end, a.n, c);
+        const long long start = (long long)(c - (i ? a.chunk_end[i - 1] : 0)) * OPT_CHUNK;
+        const long long left = a.t[i].numel - start;
+        const int flags = a.t[i].flags;
+        SgdScalars s;
+        s.coef = coef, s.wd = a.t[i].wd, s.momentum = a.momentum, s.lr = a.t[i].lr;
+        s.clip = a.coef != nullptr && (flags & OPT_CLIPPED), s.decay = s.wd != 0.0f, s.use_m = use_m, s.first = first;
+        float *p = a.t[i].p + start;
+        const float *g = a.t[i].g + start;
+        float *m = s.use_m ? a.t[i].m + start : nullptr;
+        const bool vec = (flags & OPT_VEC) != 0;
+#pragma unroll
+        for (int j = 0; j < OPT_PER_THREAD; ++j) {
+            const int e = (j * OPT_THREADS + tid) * 4;
+            if (vec && e + 4 <= left) {
+                float4 pv = *reinterpret_cast<const float4 *>(p + e);
+                const float4 gv = *reinterpret_cast<const float4 *>(g + e);
+                float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (s.use_m && !s.first) mv = *reinterpret_cast<const float4 *>(m + e);
+                sgd_element(s, pv.x, __fmul_rn(gv.x, scale), mv.x);
+                sgd_element(s, pv.y, __fmul_rn(gv.y, scale), mv.y);
+                sgd_element(s, pv.z, __fmul_rn(gv.z, scale), mv.z);
+                sgd_element(s, pv.w, __fmul_rn(gv.w, scale), mv.w);
+                if (s.use_m) *reinterpret_cast<float4 *>(m + e) = mv;
+                *reinterpret_cast<float4 *>(p + e) = pv;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (e + q < left) {
+                        float pe = p[e + q], me = (s.use_m && !s.first) ? m[e + q] : 0.0f;
+                        sgd_element(s, pe, __fmul_rn(g[e + q], scale), me);
+                        if (s.use_m) m[e + q] = me;
+                        p[e + q] = pe;
+                    }
+            }
+        }
+    }
+}
+
 static long long chunks_of(long long numel) { return (numel + OPT_CHUNK - 1) / OPT_CHUNK; }
 
 // the list's chunk count, or -1: a null list, n_tensors <= 0, a negative numel, more than INT_MAX chunks
@@ -381,6 +519,76 @@ int srcnn_sgd_step(float *const *p_host, const float *const *g_host, float *cons
     }
     if (a.n > 0) SRCNN_LAUNCH(sgd_step_kernel, grid_of(chunks), OPT_THREADS, 0, st, a);
     return check_launch("srcnn_sgd_step");
+}
+
+int srcnn_grad_norm_guarded(const float *const *g_host, const long long *numel_host, int n_tensors, float clip_norm, float grad_scale,
+                            float *out, void *workspace, size_t workspace_bytes, srcnn_stream_t stream)
+{
+    using namespace srcnn;
+    SRCNN_OPT_CHECK(check_list(n_tensors, numel_host));
+    SRCNN_REQUIRE(g_host, "null g_host");
+    SRCNN_OPT_CHECK(check_pointers(reinterpret_cast<const void *const *>(g_host), numel_host, n_tensors, "null gradient pointer",
+                                   "gradient pointer not 4-byte aligned"));
+    SRCNN_REQUIRE(clip_norm > 0.0f, "clip_norm must be > 0 (+infinity: do not clip)");
+    SRCNN_REQUIRE(grad_scale > 0.0f && std::isfinite(grad_scale), "grad_scale must be > 0 and finite");
+    SRCNN_REQUIRE(out && workspace, "null out / workspace");
+    SRCNN_REQUIRE(aligned_to(out, 4) && aligned_to(workspace, 4), "out / workspace not 4-byte aligned");
+    if (workspace_bytes < srcnn_grad_norm_workspace_bytes(n_tensors, numel_host)) {
+        set_error("srcnn_grad_norm_guarded: workspace too small (srcnn_grad_norm_workspace_bytes)");
+        return SRCNN_ERR_WORKSPACE;
+    }
+    float *partial = static_cast<float *>(workspace);
+    hipStream_t st = as_stream(stream);
+    for_each_grad_launch(const_cast<float *const *>(reinterpret_cast<const float *const *>(g_host)), numel_host, n_tensors, [&](const GradArgs &a) {
+        SRCNN_LAUNCH(grad_norm_guarded_partial_kernel, grid_of(a.chunk_end[a.n - 1]), OPT_THREADS, 0, st, a, grad_scale, partial);
+    });
+    SRCNN_LAUNCH(grad_norm_guarded_finish_kernel, 1, OPT_THREADS, 0, st, (const float *)partial, list_chunks(n_tensors, numel_host), clip_norm,
+                 out);
+    return check_launch("srcnn_grad_norm_guarded");
+}
+
+int srcnn_sgd_step_guarded(float *const *p_host, const float *const *g_host, float *const *m_host, const long long *numel_host,
+                           const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors, float momentum,
+                           int first_step, float grad_scale, const float *coef, const float *ok, unsigned *skipped, srcnn_stream_t stream)
+{
+    using namespace srcnn;
+    SRCNN_OPT_CHECK(check_list(n_tensors, numel_host));
+    SRCNN_REQUIRE(p_host && g_host && lr_host && weight_decay_host, "null p_host / g_host / lr_host / weight_decay_host");
+    SRCNN_REQUIRE(momentum >= 0.0f && std::isfinite(momentum), "momentum must be >= 0 and finite");
+    SRCNN_REQUIRE(momentum == 0.0f || m_host, "momentum != 0 needs m_host (the momentum buffers)");
+    SRCNN_OPT_CHECK(check_pointers(reinterpret_cast<const void *const *>(p_host), numel_host, n_tensors, "null parameter pointer",
+                                   "parameter pointer not 4-byte aligned"));
+    SRCNN_OPT_CHECK(check_pointers(reinterpret_cast<const void *const *>(g_host), numel_host, n_tensors, "null gradient pointer",
+                                   "gradient pointer not 4-byte aligned"));
+    if (momentum != 0.0f)
+        SRCNN_OPT_CHECK(check_pointers(reinterpret_cast<const void *const *>(m_host), numel_host, n_tensors,
+                                       "null momentum buffer pointer (momentum != 0)", "momentum buffer pointer not 4-byte aligned"));
+    SRCNN_REQUIRE(grad_scale > 0.0f && std::isfinite(grad_scale), "grad_scale must be > 0 and finite");
+    SRCNN_REQUIRE(aligned_to(coef, 4), "coef not 4-byte aligned");
+    SRCNN_REQUIRE(ok && aligned_to(ok, 4), "null or misaligned ok");
+    SRCNN_REQUIRE(aligned_to(skipped, 4), "skipped not 4-byte aligned");
+    hipStream_t st = as_stream(stream);
+    StepArgs a;
+    a.n = 0, a.first_step = first_step, a.momentum = momentum, a.coef = coef;
+    int chunks = 0;
+    unsigned *count = skipped;                                       // the call's first launch counts a skipped step, no other one
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel_host[i] == 0) continue;
+        StepTensor &t = a.t[a.n];
+        t.p = p_host[i], t.g = g_host[i], t.m = momentum != 0.0f ? m_host[i] : nullptr;
+        t.numel = numel_host[i], t.lr = lr_host[i], t.wd = weight_decay_host[i], t.pad = 0;
+        const bool vec = aligned_to(t.p, 16) && aligned_to(t.g, 16) && aligned_to(t.m, 16);
+        t.flags = (vec ? OPT_VEC : 0) | ((!clipped_host || clipped_host[i]) ? OPT_CLIPPED : 0);
+        chunks += (int)chunks_of(numel_host[i]);
+        a.chunk_end[a.n] = chunks;
+        if (++a.n == OPT_TPL) {
+            SRCNN_LAUNCH(sgd_step_guarded_kernel, grid_of(chunks), OPT_THREADS, 0, st, a, grad_scale, ok, count);
+            count = nullptr;
+            a.n = 0, chunks = 0;
+        }
+    }
+    if (a.n > 0) SRCNN_LAUNCH(sgd_step_guarded_kernel, grid_of(chunks), OPT_THREADS, 0, st, a, grad_scale, ok, count);
+    return check_launch("srcnn_sgd_step_guarded");
 }
 
 }  // extern "C"

@@ -34,12 +34,11 @@ def _numels(tensors):
     return (ctypes.c_longlong * len(tensors))(*[t.numel() for t in tensors])
 
 
-def grad_norm(grads, clip_norm):
-    """(2,) float32 device tensor {L2 norm over every element of `grads`, clip_norm / max(norm, clip_norm)}: clip_gradient's two
-    numbers (net_utils.py:39-46), summed in the defined order of include/srcnn_hip.h and left on the device."""
+def _norm(entry, grads, words, *scalars):
+    """One norm entry over `grads`: its `words` float32 results as a device tensor."""
     grads = list(grads)
     if not grads:
-        raise ValueError("grad_norm: no gradients")
+        raise ValueError("%s: no gradients" % entry)
     for g in grads:
         _check_tensor(g, "gradient")
     L = _lib.lib()
@@ -47,10 +46,22 @@ def grad_norm(grads, clip_norm):
     numel = _numels(grads)
     nbytes = L.srcnn_grad_norm_workspace_bytes(len(grads), numel)
     ws = _lib.workspace(nbytes, dev, key="optim")
-    out = torch.empty(2, dtype=torch.float32, device=dev)
-    _lib.check(L.srcnn_grad_norm(_pointers(grads), numel, len(grads), float(clip_norm), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _lib.stream()), "srcnn_grad_norm")
+    out = torch.empty(words, dtype=torch.float32, device=dev)
+    _lib.check(getattr(L, entry)(_pointers(grads), numel, len(grads), *scalars, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
+               entry)
     return out
+
+
+def grad_norm(grads, clip_norm):
+    """(2,) float32 device tensor {L2 norm over every element of `grads`, clip_norm / max(norm, clip_norm)}: clip_gradient's two
+    numbers (net_utils.py:39-46), summed in the defined order of include/srcnn_hip.h and left on the device."""
+    return _norm("srcnn_grad_norm", grads, 2, float(clip_norm))
+
+
+def grad_norm_guarded(grads, clip_norm, grad_scale=1.0):
+    """(3,) float32 device tensor {L2 norm of grad_scale * g over `grads`, clip_norm / max(norm, clip_norm), 1 where the norm is
+    finite else 0} (include/srcnn_optim_guard.h).  clip_norm float('inf'): the coefficient is 1."""
+    return _norm("srcnn_grad_norm_guarded", grads, 3, float(clip_norm), float(grad_scale))
 
 
 def scale_grads(grads, coef):
@@ -68,7 +79,18 @@ class SGD(torch.optim.Optimizer):
     step(clip_norm=None, clip_params=None): with clip_norm, the global norm of the gradients of `clip_params` (default: every
     parameter of the optimiser) is taken first and those parameters' gradients enter the update multiplied by
     clip_norm / max(norm, clip_norm); the other parameters (the reference's `uncert`) use their gradient as it is.  The
-    (norm, coefficient) pair stays on the device as `self.last_norm`."""
+    (norm, coefficient) pair stays on the device as `self.last_norm`.
+
+    step(..., guard=True, grad_scale=s) (keywords; include/srcnn_optim_guard.h): every gradient enters as g * s (s = 1 / N after N
+    backward passes have summed into .grad), and the whole update -- the unclipped parameters' too -- runs only where the norm of
+    the scaled gradients is finite: on an Inf, a NaN or an overflowing norm no parameter and no momentum buffer changes (a buffer
+    created by that very step becomes zeros, which makes the next step the first one) and `self.skipped_steps`, a one-element
+    int32 device tensor created at the first such call, goes up by one.  step never reads it, or anything else, from the device.
+    `self.last_norm` is then (norm, coefficient, ok).  The word `ok` comes from the norm over `clip_params`; where nothing is
+    clipped (clip_norm None, or no clip parameter has a gradient) it comes from a norm over EVERY gradient taken with a clip_norm
+    of +infinity, whose coefficient is 1 and is not used.  Either keyword alone selects this path: a grad_scale other than 1 is
+    always guarded.  With guard=False and grad_scale=1 the calls are exactly those of the plain step.  The counter is no part of
+    state_dict()."""
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
         if lr < 0.0:
@@ -85,9 +107,13 @@ class SGD(torch.optim.Optimizer):
                         differentiable=False, fused=None)
         super().__init__(params, defaults)
         self.last_norm = None
+        self.skipped_steps = None
 
     @torch.no_grad()
-    def step(self, clip_norm=None, clip_params=None, closure=None):
+    def step(self, clip_norm=None, clip_params=None, closure=None, *, guard=False, grad_scale=1.0):
+        grad_scale = float(grad_scale)
+        if not 0.0 < grad_scale < float('inf'):
+            raise ValueError("grad_scale must be > 0 and finite, got %r" % grad_scale)
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -119,21 +145,35 @@ class SGD(torch.optim.Optimizer):
                 every.append(p)
         if not every:
             return loss
-        coef = None
+        guarded = bool(guard) or float(grad_scale) != 1.0
+        coef, ok, clip_ids = None, None, set()
         if clip_norm is not None:
             clipped = every if clip_params is None else [p for p in clip_params if p.grad is not None]
             clip_ids = set(id(p) for p in clipped)
-            if clipped:
+            if clipped and guarded:
+                self.last_norm = grad_norm_guarded([p.grad for p in clipped], clip_norm, grad_scale)
+                coef, ok = self.last_norm[1:2], self.last_norm[2:]
+            elif clipped:
                 self.last_norm = grad_norm([p.grad for p in clipped], clip_norm)
                 coef = self.last_norm[1:]
+        if guarded and ok is None:
+            self.last_norm = grad_norm_guarded([p.grad for p in every], float('inf'), grad_scale)
+            ok = self.last_norm[2:]
+        if guarded and self.skipped_steps is None:
+            self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=every[0].device)
         L = _lib.lib()
+        count = self.skipped_steps.data_ptr() if guarded else None      # the step's first call counts a skipped step, no other one
         for (momentum, first), entries in buckets.items():
             ps = [e[0] for e in entries]
             n = len(ps)
             flags = (ctypes.c_int * n)(*[int(coef is not None and id(p) in clip_ids) for p in ps])
-            _lib.check(L.srcnn_sgd_step(_pointers(ps), _pointers([p.grad for p in ps]),
-                                        _pointers([e[1] for e in entries]) if momentum != 0 else None, _numels(ps),
-                                        (ctypes.c_float * n)(*[e[2] for e in entries]), (ctypes.c_float * n)(*[e[3] for e in entries]),
-                                        flags, n, momentum, int(first), None if coef is None else coef.data_ptr(), _lib.stream()),
-                       "srcnn_sgd_step")
+            lists = (_pointers(ps), _pointers([p.grad for p in ps]), _pointers([e[1] for e in entries]) if momentum != 0 else None,
+                     _numels(ps), (ctypes.c_float * n)(*[e[2] for e in entries]), (ctypes.c_float * n)(*[e[3] for e in entries]), flags, n,
+                     momentum, int(first))
+            if guarded:
+                _lib.check(L.srcnn_sgd_step_guarded(*lists, float(grad_scale), None if coef is None else coef.data_ptr(), ok.data_ptr(),
+                                                    count, _lib.stream()), "srcnn_sgd_step_guarded")
+                count = None
+            else:
+                _lib.check(L.srcnn_sgd_step(*lists, None if coef is None else coef.data_ptr(), _lib.stream()), "srcnn_sgd_step")
         return loss

@@ -83,7 +83,7 @@ LOSS_NAMES = ('rpn_loss_cls', 'rpn_loss_bbox_left_right', 'RCNN_loss_cls', 'RCNN
 
 
 def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, backward_precision='f32', forward_precision='f32',
-               reuse_maxima=True, prepared_weights=False, device_fold=False):
+               reuse_maxima=True, prepared_weights=False, device_fold=False, accum_steps=1, guard=False):
     """One iteration of trainval_net.py:207-227.  batch: forward_train's nine inputs (im_left, im_right, im_info, gt_boxes_left,
     gt_boxes_right, gt_boxes_merge, gt_dim_orien, gt_kpts, num_boxes).  Gradients are set to None, forward_train and
     losses.multi_task_loss build the total, backward() fills the gradients, and optimizer.step clips the MODEL's gradients to
@@ -92,9 +92,25 @@ def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, b
     and calls its prepare() at the start of EVERY step -- never a cache keyed on a version counter: optimizer.step writes the
     parameters through raw pointers, which torch's counter does not see.  device_fold (it needs prepared_weights=True, ValueError
     otherwise): that prepare() folds and re-lays-out the weights on the device (TrainWeights.prepare).  Returns device scalars: 'loss', the six
-    terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0]."""
+    terms by name, 'grad_norm' (the model's gradient norm before clipping).  The only host read is forward_train's im_info[0][0].
+
+    accum_steps = N > 1: `batch` is a sequence of N such batches (images of different sizes are fine: nothing is padded).  For each,
+    in order, forward_train, the multi-task loss and backward() run, autograd summing into .grad; ONE optimizer.step with
+    grad_scale = 1 / N follows, the update of the mean gradient, clipped by the mean gradient's norm ('grad_norm').  `generator`
+    goes on from micro-batch to micro-batch.  prepare() runs once per train_step (the weights do not change in between; every
+    backward but the last keeps the fold's graph).  Each returned scalar is the mean over the micro-batches: summed in order, then
+    multiplied by 1 / N, on the device.  The host reads im_info[0][0] once per micro-batch and nothing else.
+    guard=True: optim.SGD.step's guard -- where a gradient is not finite the step changes no parameter and no momentum buffer;
+    the result also carries 'ok' (device float, 1 or 0) and 'skipped_steps' (the optimiser's device counter).
+    accum_steps=1, guard=False is the plain step, call for call."""
     if device_fold and not prepared_weights:
         raise ValueError("device_fold=True needs prepared_weights=True: it is TrainWeights.prepare's fold that moves to the device")
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError("accum_steps must be >= 1, got %d" % accum_steps)
+    batches = [batch] if accum_steps == 1 else list(batch)
+    if len(batches) != accum_steps:
+        raise ValueError("accum_steps = %d needs a sequence of %d batches, got %d" % (accum_steps, accum_steps, len(batches)))
     optimizer.zero_grad(set_to_none=True)
     for p in model.parameters():
         p.grad = None
@@ -104,15 +120,28 @@ def train_step(model, optimizer, uncert, batch, clip_norm=10., generator=None, b
         if weights is None or weights.model is not model:
             weights = optimizer._train_weights = TrainWeights(model)
         weights.prepare(device_fold=device_fold)
-    out = forward_train(model, *batch, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision,
-                        reuse_maxima=reuse_maxima, weights=weights)
-    terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
-    total = losses.multi_task_loss(terms, uncert)
-    total.backward()
-    optimizer.step(clip_norm=clip_norm, clip_params=[p for p in model.parameters() if p.requires_grad])
-    result = {'loss': total.detach()}
-    result.update((name, t.detach()) for name, t in zip(LOSS_NAMES, terms))
+    sums = None
+    for i, one in enumerate(batches):
+        out = forward_train(model, *one, generator=generator, backward_precision=backward_precision, forward_precision=forward_precision,
+                            reuse_maxima=reuse_maxima, weights=weights)
+        terms = list(out[8:14])                     # scalars: the reference's .mean() of each is the identity on one device
+        total = losses.multi_task_loss(terms, uncert)
+        # the prepared weights' fold is one graph under every micro-batch's: it is released by the last backward
+        total.backward(retain_graph=weights is not None and i + 1 < accum_steps)
+        values = [total.detach()] + [t.detach() for t in terms]
+        sums = values if sums is None else [s + v for s, v in zip(sums, values)]
+    clip_params = [p for p in model.parameters() if p.requires_grad]
+    if accum_steps == 1 and not guard:
+        optimizer.step(clip_norm=clip_norm, clip_params=clip_params)
+    else:
+        optimizer.step(clip_norm=clip_norm, clip_params=clip_params, guard=guard, grad_scale=1.0 / accum_steps)
+        if accum_steps > 1:
+            sums = [s * (1.0 / accum_steps) for s in sums]
+    result = dict(zip(('loss',) + LOSS_NAMES, sums))
     result['grad_norm'] = optimizer.last_norm[0] if clip_norm is not None else None
+    if guard:
+        result['ok'] = optimizer.last_norm[2]
+        result['skipped_steps'] = optimizer.skipped_steps
     return result
 
 

@@ -25,6 +25,13 @@ a weight.  The results are bit-identical.
 --device-fold (implies --prepared-weights; logged in trainlog.txt only when set): the frozen-BN fold and the re-layout of every
 weight, and their adjoint, run on the device in one call each (training.train_step's device_fold=True; csrc/train_fold.hip) in
 place of the per-layer torch operators.  The results are bit-identical.
+--accum N (default 1; logged in trainlog.txt only when set): N consecutive loader batches form one step -- N forwards and
+backwards summing their gradients, one update with their mean (training.train_step's accum_steps=N); iterations count steps, and
+a trailing group of fewer than N batches at an epoch's end is not trained on.  The way to a larger effective batch at --bs 1:
+no image is padded.
+--guard (default off; logged in trainlog.txt only when set): the update is skipped, on the device, where a gradient is not finite
+(training.train_step's guard=True; csrc/optim.hip): one Inf or NaN costs one step and not the run.  The count of skipped steps is
+read and logged with the losses every --disp_interval iterations, and nowhere else.
 
 The model starts from the reference's random initialisation (_init_weights) unless --init names a state dict (an ImageNet-
 initialised or earlier Stereo R-CNN checkpoint): the reference's `pretrained=True` reads a caffe ResNet file this project does not ship.
@@ -80,9 +87,25 @@ def parse_args(argv=None):
     p.add_argument('--no-reuse-maxima', dest='reuse_maxima', action='store_false',
                    help="f16x3 precisions only: let every convolution call scan its input for max |x| itself instead of taking it from "
                         "the call that produced the tensor (same bits either way)")
+    p.add_argument('--accum', dest='accum', default=1, type=int,
+                   help='loader batches per optimiser step: their gradients are summed on the device and the update uses the mean')
+    p.add_argument('--guard', dest='guard', action='store_true',
+                   help='skip the update, on the device, of a step whose gradients are not all finite; the count is logged with the losses')
     args = p.parse_args(argv)
+    if args.accum < 1:
+        p.error('--accum must be >= 1')
     args.prepared_weights = args.prepared_weights or args.device_fold
     return args
+
+
+def _groups(batches, n):
+    """Lists of n consecutive items of `batches`; a trailing shorter group is dropped."""
+    group = []
+    for b in batches:
+        group.append(b)
+        if len(group) == n:
+            yield group
+            group = []
 
 
 def main(argv=None):
@@ -123,6 +146,10 @@ def main(argv=None):
         log_string('prepared weights: once per step')
     if args.device_fold:
         log_string('device fold: BN fold and weight re-layout in one call per direction')
+    if args.accum != 1:
+        log_string('gradient accumulation: %d batches per step' % args.accum)
+    if args.guard:
+        log_string('guard: steps with non-finite gradients are skipped on the device')
     model = resnet(kitti.CLASSES, args.net, pretrained=False)
     model.create_architecture()
     if args.init:
@@ -146,7 +173,7 @@ def main(argv=None):
     gen_dev = torch.Generator(device=dev).manual_seed(seed)
     loader = data.TrainLoader(roidb, ratio_index, args.batch_size, dev, generator=gen_host, workers=args.num_workers,
                               prefetch=args.prefetch)
-    iters_per_epoch = int(train_size / args.batch_size)
+    iters_per_epoch = int(train_size / args.batch_size) // args.accum
     validate = None
     if args.val_split:
         if not args.val_label_dir:
@@ -162,19 +189,23 @@ def main(argv=None):
                 net_utils.adjust_learning_rate(optimizer, args.lr_decay_gamma)
                 lr *= args.lr_decay_gamma
             step = -1
-            for step, batch in enumerate(loader):
+            for step, group in enumerate(_groups(loader, args.accum)):
                 if step >= iters_per_epoch:              # trainval_net.py:183,194: the leftover samples are not trained on
                     break
+                batch = group[0] if args.accum == 1 else group
                 res = training.train_step(model, optimizer, uncert, batch, clip_norm=10., generator=gen_dev,
                                           backward_precision=args.backward_precision, forward_precision=args.forward_precision,
                                           reuse_maxima=args.reuse_maxima, prepared_weights=args.prepared_weights,
-                                          device_fold=args.device_fold)
+                                          device_fold=args.device_fold, accum_steps=args.accum, guard=args.guard)
                 if args.disp_interval > 0 and step % args.disp_interval == 0:
                     vals = {k: float(v) for k, v in res.items() if v is not None}          # the only host reads of the loop
                     log_string('[epoch %2d][iter %4d/%4d] loss: %.4f, lr: %.2e' % (epoch, step, iters_per_epoch, vals['loss'], lr))
                     log_string('\t\t\tuncert: ' + ', '.join('%.4f' % v for v in uncert.detach().cpu().tolist()))
                     log_string('\t\t\trpn_cls: %.4f, rpn_box_left_right: %.4f, rcnn_cls: %.4f, rcnn_box_left_right %.4f, dim_orien %.4f, '
                                'kpts %.4f, grad norm %.3f' % tuple([vals[k] for k in training.LOSS_NAMES] + [vals['grad_norm']]))
+                    if args.guard:
+                        log_string('\t\t\tskipped steps: %d%s' % (int(vals['skipped_steps']),
+                                                                 '' if vals['ok'] != 0 else ' (this step was skipped: its gradients were not finite)'))
             save_name = os.path.join(args.save_dir, 'stereo_rcnn_{}_{}.pth'.format(epoch, min(step, iters_per_epoch - 1)))
             net_utils.save_checkpoint({'epoch': epoch + 1, 'model': model.state_dict(), 'optimizer': optimizer.state_dict(),
                                        'uncert': uncert.detach().clone()}, save_name)

@@ -38,6 +38,7 @@ COMMANDS = [      # (family regex, how the family is produced)
     (r'^loader_bench', 'python tools/loader_bench.py   (one training batch assembly, csrc/loader.hip against eager torch; the loader\'s sustained pairs/s against the train_step rate)'),
     (r'^overlay_bench', 'python tools/overlay_bench.py   (the result picture of one pair: csrc/overlay.hip against numpy + PIL ImageDraw on the host)'),
     (r'^optim_bench', 'python tools/optim_bench.py   (optim.SGD.step(clip_norm=10.) against the reference\'s clip_gradient + torch.optim.SGD.step() on R-101\'s trainable shapes)'),
+    (r'^optim_guard_bench', 'python tools/optim_guard_bench.py   (optim.SGD.step(clip_norm=10., guard=True) against optim.SGD.step(clip_norm=10.) on R-101\'s trainable shapes, alternating)'),
     (r'^conv_microbench', 'SWEEP=1 python tools/conv_bench.py f16s | f32'),
 ]
 
