@@ -145,24 +145,24 @@ class SGD(torch.optim.Optimizer):
                 every.append(p)
         if not every:
             return loss
-        guarded = bool(guard) or float(grad_scale) != 1.0
-        coef, ok, clip_ids = None, None, set()
+        guarded = bool(guard) or grad_scale != 1.0
+        coef, clip_ids = None, set()
         if clip_norm is not None:
             clipped = every if clip_params is None else [p for p in clip_params if p.grad is not None]
             clip_ids = set(id(p) for p in clipped)
-            if clipped and guarded:
-                self.last_norm = grad_norm_guarded([p.grad for p in clipped], clip_norm, grad_scale)
-                coef, ok = self.last_norm[1:2], self.last_norm[2:]
-            elif clipped:
-                self.last_norm = grad_norm([p.grad for p in clipped], clip_norm)
-                coef = self.last_norm[1:]
-        if guarded and ok is None:
-            self.last_norm = grad_norm_guarded([p.grad for p in every], float('inf'), grad_scale)
-            ok = self.last_norm[2:]
-        if guarded and self.skipped_steps is None:
-            self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=every[0].device)
-        L = _lib.lib()
-        count = self.skipped_steps.data_ptr() if guarded else None      # the step's first call counts a skipped step, no other one
+            if clipped:
+                grads = [p.grad for p in clipped]
+                self.last_norm = grad_norm_guarded(grads, clip_norm, grad_scale) if guarded else grad_norm(grads, clip_norm)
+                coef = self.last_norm[1:2].data_ptr()
+        # what the guarded entry takes beyond the plain one's arguments: (grad_scale,) before coef, (ok, skipped) after it
+        before, after = (), ()
+        if guarded:
+            if coef is None:
+                self.last_norm = grad_norm_guarded([p.grad for p in every], float('inf'), grad_scale)
+            if self.skipped_steps is None:
+                self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=every[0].device)
+            before, after = (grad_scale,), (self.last_norm[2:].data_ptr(), self.skipped_steps.data_ptr())
+        entry = "srcnn_sgd_step_guarded" if guarded else "srcnn_sgd_step"
         for (momentum, first), entries in buckets.items():
             ps = [e[0] for e in entries]
             n = len(ps)
@@ -170,10 +170,7 @@ class SGD(torch.optim.Optimizer):
             lists = (_pointers(ps), _pointers([p.grad for p in ps]), _pointers([e[1] for e in entries]) if momentum != 0 else None,
                      _numels(ps), (ctypes.c_float * n)(*[e[2] for e in entries]), (ctypes.c_float * n)(*[e[3] for e in entries]), flags, n,
                      momentum, int(first))
+            _lib.check(getattr(_lib.lib(), entry)(*lists, *before, coef, *after, _lib.stream()), entry)
             if guarded:
-                _lib.check(L.srcnn_sgd_step_guarded(*lists, float(grad_scale), None if coef is None else coef.data_ptr(), ok.data_ptr(),
-                                                    count, _lib.stream()), "srcnn_sgd_step_guarded")
-                count = None
-            else:
-                _lib.check(L.srcnn_sgd_step(*lists, None if coef is None else coef.data_ptr(), _lib.stream()), "srcnn_sgd_step")
+                after = (after[0], None)                                # the step's first call counts a skipped step, no other one
         return loss

@@ -6,8 +6,9 @@ without elements, one whose gradient is None, a 4-byte-aligned view (offset of o
 and m, and TENSORS_PER_LAUNCH + 3 small tensors so that the list spans launches.  Parameters, gradients and (from the second step
 on) momentum buffers are slices of one arena filled with a guard value, at least 16 guard floats on both sides of every slice.
 
-Parameters and momentum buffers must be BIT-EQUAL to the float32 restatement fed the kernel's own coefficient; the norm is
-compared with float64 within optim_ref.norm_bound(); only the comparison with torch.optim.SGD has a measured tolerance
+Parameters and momentum buffers must be BIT-EQUAL to the float32 restatement fed the kernel's own coefficient; the norm and the
+coefficient are BIT-EQUAL to the restatement of the two summation stages (optim_ref.grad_norm_f32) and the norm is also compared
+with float64 within optim_ref.norm_bound(); only the comparison with torch.optim.SGD has a measured tolerance
 (tests/optim_tolerances.py)."""
 import copy
 
@@ -129,7 +130,9 @@ def run_steps(lib, dev, momentum, clip_norm=CLIP, check=True):
         if not check:
             continue
         if clip_norm is not None:
-            want = R.norm_f64([g for i, g in enumerate(gs) if _hyper(i)[2] and i != NO_GRAD])
+            in_norm = [g for i, g in enumerate(gs) if _hyper(i)[2] and i != NO_GRAD]           # clip_params with a gradient, in list order
+            assert _bits_equal(opt.last_norm, np.array(R.grad_norm_f32(in_norm, clip_norm))), ('norm, coefficient', step)
+            want = R.norm_f64(in_norm)
             rel = abs(float(norm) - want) / want
             print('step %d: norm %.9g (float64 %.9g), relative error %.3e (bound %.3e), coefficient %.9g' % (step, norm, want, rel, R.norm_bound(), coef))
             assert rel <= R.norm_bound()
@@ -283,6 +286,27 @@ def test_adjust_learning_rate_and_clip_gradient(lib, dev):
                 assert np.array_equal(_u32(p.grad), frozen)             # requires_grad False: neither counted nor scaled
             else:
                 assert _bits_equal(p.grad, (gs[name] * coef).astype(np.float32)), name
+
+
+@pytest.mark.parametrize('coef', [0.37, 1.0])
+def test_scale_grads_over_the_list(lib, dev, coef):
+    """srcnn_grad_scale over the module's list (chunk tails, a tensor without elements, a 4-byte-aligned view, more tensors than
+    one launch takes): g * float32(coef), one rounding; a coefficient of exactly 1 is the kernel's early return, no bit moves."""
+    from stereo_rcnn_amd import optim
+    sizes = _sizes(lib)
+    arena = Arena(dev, sum(sizes) + 40 * len(sizes))
+    gs = _grads(sizes, 0, 1.0)
+    slices = []
+    for i, g in enumerate(gs):
+        t = arena.take(g.size, odd=(i == VIEW_G))
+        t.copy_(torch.from_numpy(g))
+        slices.append(t)
+    k = torch.tensor([coef], dtype=torch.float32, device=dev)
+    optim.scale_grads(slices, k)
+    for i, (t, g) in enumerate(zip(slices, gs)):
+        want = g if coef == 1.0 else (g * np.float32(coef)).astype(np.float32)
+        assert _bits_equal(t, want), (i, sizes[i])
+    assert _bits_equal(k, [coef]) and arena.guards_intact()
 
 
 def test_index_past_2_31(lib, dev):

@@ -39,6 +39,7 @@ COMMANDS = [      # (family regex, how the family is produced)
     (r'^overlay_bench', 'python tools/overlay_bench.py   (the result picture of one pair: csrc/overlay.hip against numpy + PIL ImageDraw on the host)'),
     (r'^optim_bench', 'python tools/optim_bench.py   (optim.SGD.step(clip_norm=10.) against the reference\'s clip_gradient + torch.optim.SGD.step() on R-101\'s trainable shapes)'),
     (r'^optim_guard_bench', 'python tools/optim_guard_bench.py   (optim.SGD.step(clip_norm=10., guard=True) against optim.SGD.step(clip_norm=10.) on R-101\'s trainable shapes, alternating)'),
+    (r'^optim_refactor_ab', 'python tools/kernel_resources.py stereo_rcnn_amd/csrc/optim.hip; python tools/optim_guard_bench.py --reps 40 with SRCNN_LIB_PATH = the parent commit\'s library and without, taking turns (parent, tree, parent, tree)'),
     (r'^conv_microbench', 'SWEEP=1 python tools/conv_bench.py f16s | f32'),
 ]
 
