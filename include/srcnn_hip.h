@@ -448,6 +448,132 @@ SRCNN_API int srcnn_conv2d_backward_f16x3_maxima(const srcnn_conv_bwd_desc *d, c
                                                  size_t workspace_bytes, srcnn_stream_t stream);
 SRCNN_API int srcnn_absmax(const float *x, long long rows, int len, long long stride, unsigned *word, srcnn_stream_t stream);
 
+/* ------------------------------------------------- 3 x f16 training calls: weights prepared once per step
+ * max|w| and the split of w are functions of the weights alone, and the weights change only in the optimiser step: what every
+ * srcnn_conv2d_forward_f16x3 call (clear, max|w|, split) and every srcnn_conv2d_backward_f16x3 call (clear, max|w|, re-layout +
+ * split) computes for itself can be computed once per step for ALL layers.  srcnn_train_weights_prepare does that for a list; the
+ * two *_prepared entries are the *_maxima entries reading its results.  Every result keeps the bits of the plain entries.
+ *
+ * srcnn_train_weight_desc, one layer (field order: w, w_amax, w_hi, w_lo, wt_hi, wt_lo, Cout, KH, KW, Cin):
+ *   w       the folded fp32 weight in engine layout (Cout, KH, KW, Cin), 16-byte aligned, Cin a multiple of 32;
+ *   w_amax  one word (4-byte aligned) that receives the float bits of max|w| (0 for an all-zero weight);
+ *   w_hi, w_lo    the forward planes (Cp, KH KW, Cin) float16, Cp = Cout rounded up to 32, rows [Cout, Cp) zero -- what the plain
+ *                 forward's split writes into its workspace;
+ *   wt_hi, wt_lo  the backward planes (Cin, KH KW, Cp) float16, element (c, tap, n) = split(w[n][tap][c]), columns [Cout, Cp) zero --
+ *                 what the plain backward's re-layout + split writes.  All four planes 16-byte aligned, Cp KH KW Cin halves each.
+ *   t = s w, hi = f16(t), lo = f16(t - hi), s = 2^(14 - floor(log2 max|w|)) with the exponent clamped to +-126 (an all-zero weight:
+ *   s = 2^126, exact-zero planes).
+ * `layers_host` is a HOST array.  It travels in kernel-argument blocks, 48 layers per block, into a
+ * table in the workspace (srcnn_train_weights_workspace_bytes(n) = n records of 80 bytes, rounded up to
+ * 256; 0 for n < 1): nothing is copied by the host runtime, nothing is read back.  Launches, one stream, in order:
+ *   (1) per 48 layers one small launch that writes their table rows and clears their words;
+ *   (2) ONE launch over the whole list that finds every layer's max|w|: a layer is cut into chunks of 8192 floats, a workgroup takes
+ *       one chunk and finds its layer by a binary search over the table's running chunk counts; one integer atomicMax on the float
+ *       bits per wave (order-independent).  A clear and an atomicMax on the same word cannot share a launch without a device-scope
+ *       fence, which is why (1) clears;
+ *   (3) ONE launch that writes every layer's four planes: the unit of work is 32 rows of w x up to 8 K tiles (a K tile = 32 channels
+ *       of one tap), found by the same search, so RCNN_top's (2048, 7, 7, 256) is thousands of units and a (24, 1, 1, 512) head
+ *       two.  Per K tile the 32 x 32 floats are read as one float4 per thread, split, parked in LDS as halves, and leave as
+ *       16-byte runs on both sides: 8 channels of a row for w_hi / w_lo, 8 rows of a channel (read transposed from LDS) for wt_*.
+ * So a list of up to 48 layers takes three launches and every further block of that many one more.
+ * No host read, no device-scope fence, no float atomics; every plane element is written exactly once (pass uninitialised buffers).
+ * Errors, before any launch (nothing is written): a null list / workspace, n_layers < 1, "layer i: ..." for a null or misaligned
+ * pointer, non-positive sizes, Cin not a multiple of 32 or a layer of 2^31 elements or more (SRCNN_ERR_ARG); a workspace smaller
+ * than the query's (SRCNN_ERR_WORKSPACE).
+ *
+ * srcnn_conv2d_forward_f16x3_prepared: srcnn_conv2d_forward_f16x3_maxima (same descriptor, x_amax, y_amax, validation, workspace
+ *   query) with w_amax, w_hi, w_lo of the layer as srcnn_train_weights_prepare left them and plane_bytes, the bytes each plane
+ *   holds.  Neither the scan of w nor the split is launched; the clear launch zeroes the max|x| word only when the call scans x
+ *   itself, copies *w_amax into the workspace word the GEMM reads s_w from, and clears y_amax.  The GEMM kernel is the same.
+ * srcnn_conv2d_backward_f16x3_prepared: srcnn_conv2d_backward_f16x3_maxima likewise with w_amax, wt_hi, wt_lo; the three may be
+ *   NULL when dx is not asked for (the weight gradient reads no weights).
+ *   Additional refusals, before any launch: a null word or plane ("null"), a word not 4-byte or a plane not 16-byte aligned
+ *   ("aligned"), plane_bytes below Cp KH KW Cin halves ("plane_bytes"). */
+typedef struct srcnn_train_weight_desc {
+    const float *w;
+    unsigned *w_amax;
+    void *w_hi, *w_lo;
+    void *wt_hi, *wt_lo;
+    int Cout, KH, KW, Cin;
+} srcnn_train_weight_desc;
+SRCNN_API size_t srcnn_train_weights_workspace_bytes(int n_layers);
+SRCNN_API int srcnn_train_weights_prepare(const srcnn_train_weight_desc *layers_host, int n_layers, void *workspace,
+                                          size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_conv2d_forward_f16x3_prepared(const srcnn_conv_fwd_f16x3_desc *d, const unsigned *x_amax, unsigned *y_amax,
+                                                  const unsigned *w_amax, const void *w_hi, const void *w_lo, size_t plane_bytes,
+                                                  void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_conv2d_backward_f16x3_prepared(const srcnn_conv_bwd_desc *d, const unsigned *x_amax, const unsigned *w_amax,
+                                                   const void *wt_hi, const void *wt_lo, size_t plane_bytes, void *workspace,
+                                                   size_t workspace_bytes, srcnn_stream_t stream);
+
+/* ------------------------------------------------- training: frozen-BN fold + engine layout of every weight, both directions
+ * What feeds srcnn_train_weights_prepare: every layer's parameter (as nn.Conv2d / nn.Linear / nn.ConvTranspose2d hold it), with
+ * its frozen BatchNorm folded in, written in the conv engine's layout (Cout, KH, KW, Cin) -- and, on the way back, the gradient of
+ * that folded tensor carried to the parameter.  The arithmetic is stereo_rcnn_amd.autograd._fold's, operation for operation, so
+ * the results carry the bits of the eager torch path (float64, one rounding per operation, never an FMA):
+ *   forward   s = (double)gamma / sqrt((double)var + 1e-5);  w' = (float)((double)w * s);
+ *             b' = (float)((double)beta - (double)mean * s)                    without a convolution bias,
+ *             b' = (float)((double)bias * s + ((double)beta - (double)mean * s))   with one;
+ *   backward  dw = (float)((double)dw' * s);  db = (float)((double)db' * s);  the BN tensors receive nothing;
+ *   without a BN both directions move data and compute nothing.
+ *
+ * srcnn_train_fold_desc, one layer (field order: w[3], bias[3], grad_w[3], grad_b[3], bn_weight, bn_bias, bn_mean, bn_var, dst_w,
+ * dst_b, rows[3], n_parts, kind, Cout, KH, KW, Cin):
+ *   n_parts 1..3 source parts, concatenated along the output rows (rpn_head is two, box_heads three): part p is the parameter
+ *           w[p] with rows[p] output rows and its optional bias[p] (all parts carry one, or none does); the rows sum to Cout;
+ *   kind    SRCNN_TRAIN_FOLD_CONV       part (rows, Cin, KH, KW) -> dst_w (Cout, KH, KW, Cin) (RCNN_top.0's (2048, 512, 7, 7) ->
+ *                                       (2048, 1, 1, 49 * 512) is this kind: the same memory);
+ *           SRCNN_TRAIN_FOLD_LINEAR     part (rows, Cin) -> dst_w (Cout, 1, 1, Cin), a copy; KH = KW = 1;
+ *           SRCNN_TRAIN_FOLD_DECONV2X2  one part (Cin, Cout, 2, 2) -> dst_w (4 Cout, 1, 1, Cin), row (i, j, co) = (2 i + j) Cout + co;
+ *                                       KH = KW = 2, rows[0] = Cout; dst_b (4 Cout) is bias four times;
+ *   bn_*    the frozen BatchNorm's weight, bias, running_mean, running_var (Cout floats each): all four or none; one part only;
+ *   dst_w, dst_b   the folded weight and bias.  dst_b is required with a BN or a bias and must be NULL otherwise;
+ *   grad_w[p], grad_b[p]   (backward only) receive the gradient of part p in the PARAMETER's own contiguous layout.
+ * Cin is a multiple of 32, KH KW <= 128; w[p], dst_w, grad_w[p] and the dw_folded entries are 16-byte aligned (vector loads and
+ * stores), every other pointer 4-byte.
+ *
+ * srcnn_train_weights_fold writes dst_w and dst_b of every layer.
+ * srcnn_train_weights_fold_backward takes dw_folded_host[i] / db_folded_host[i], the gradients of layer i's dst_w / dst_b (HOST
+ * arrays of n device pointers, the arrays themselves may not be NULL).  A NULL dw entry skips the layer's weights, a NULL db
+ * entry its biases: nothing of theirs is written (a layer with both NULL costs no work).  db of a layer without a convolution
+ * bias reaches no parameter and is ignored.  THE DECONVOLUTION'S BIAS STAYS EAGER: its adjoint is the sum of four floats whose
+ * order torch.Tensor.repeat's backward does not document, so the entry refuses a non-NULL db_folded_host[i] for a DECONV2X2
+ * layer and the caller keeps `bias.repeat(4)` (256 floats) as a torch operator; the forward's copy is exact and is done here.
+ *
+ * Conventions are srcnn_train_weights_prepare's.  `layers_host` is a HOST array; it travels in kernel-argument blocks,
+ * SRCNN_TRAIN_FOLD_LAYERS_PER_BLOCK layers per block, into a table in the workspace (srcnn_train_fold_workspace_bytes(n) = n
+ * records of 144 bytes rounded up to 256; 0 for n < 1).  Launches, one stream, in order: per block of layers one small launch
+ * that writes their table rows, then ONE launch that does all the work.  Its unit is R output rows x C input channels (all taps)
+ * with R C KH KW <= 4096 floats, found by a binary search over the table's running unit counts (RCNN_top.0 is 16384 units, a
+ * (24, 512) head three): the unit is read in the source's order, staged in LDS, and written in the destination's order, so both
+ * sides move as contiguous 16-byte runs (parameter side: C KH KW floats of a row; engine side: per tap C floats).
+ * No host read, no device-scope fence, no atomics; every destination element is written exactly once (pass uninitialised
+ * buffers); the same bits on every run.
+ * Errors, before any launch (nothing is written): a null list / workspace / gradient array, n_layers < 1, "layer i: ..." for a
+ * null or misaligned pointer, n_parts outside 1..3, non-positive sizes, Cin not a multiple of 32, rows not summing to Cout, an
+ * unknown kind, a BN over several parts or given in part, a bias on some parts only, dst_b not matching, a layer of 2^31 elements
+ * or more (SRCNN_ERR_ARG); a workspace smaller than the query's (SRCNN_ERR_WORKSPACE). */
+#define SRCNN_TRAIN_FOLD_CONV 0
+#define SRCNN_TRAIN_FOLD_LINEAR 1
+#define SRCNN_TRAIN_FOLD_DECONV2X2 2
+#define SRCNN_TRAIN_FOLD_LAYERS_PER_BLOCK 24
+typedef struct srcnn_train_fold_desc {
+    const float *w[3];
+    const float *bias[3];
+    float *grad_w[3];
+    float *grad_b[3];
+    const float *bn_weight, *bn_bias, *bn_mean, *bn_var;
+    float *dst_w, *dst_b;
+    int rows[3];
+    int n_parts, kind, Cout, KH, KW, Cin;
+} srcnn_train_fold_desc;
+SRCNN_API size_t srcnn_train_fold_workspace_bytes(int n_layers);
+SRCNN_API int srcnn_train_weights_fold(const srcnn_train_fold_desc *layers_host, int n_layers, void *workspace, size_t workspace_bytes,
+                                       srcnn_stream_t stream);
+SRCNN_API int srcnn_train_weights_fold_backward(const srcnn_train_fold_desc *layers_host, int n_layers,
+                                                const float *const *dw_folded_host, const float *const *db_folded_host,
+                                                void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+
 /* ------------------------------------------------- training: remaining adjoints
  * The three differentiable operators of the reference's training branch that are neither a convolution, a ROIAlign nor a loss:
  * _upsample_add (stereo_rcnn.py:91-108), MaxPool2d(1, stride 2) (stereo_rcnn.py:39,168) and the layout step of
@@ -931,6 +1057,55 @@ SRCNN_API int srcnn_grad_scale(float *const *g_host, const long long *numel_host
 SRCNN_API int srcnn_sgd_step(float *const *p_host, const float *const *g_host, float *const *m_host, const long long *numel_host,
                    const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors, float momentum,
                    int first_step, const float *coef, srcnn_stream_t stream);
+
+/* ------------------------------------------------- training: optimiser step over accumulated gradients, skipped when not finite
+ * srcnn_sgd_step forms g * coef; one Inf or NaN in any gradient makes the norm Inf or NaN, the coefficient 0 or NaN and the
+ * product NaN on that element: parameter and momentum buffer are lost for good, and nothing reads the device to notice.  The pair
+ * below is srcnn_grad_norm + srcnn_sgd_step with two additions: every gradient enters multiplied by the host float grad_scale
+ * (1 / N after N backward passes have summed into .grad: the update of the mean gradient), and the update is predicated on a
+ * DEVICE word that says whether the norm is finite.  Nothing is read back.
+ *
+ * Every convention is that of "training: optimiser step" above: HOST arrays of device pointers and long long numels, an
+ * entry with numel 0 skipped, at most SRCNN_OPT_TENSORS_PER_LAUNCH tensors per launch, chunks of SRCNN_OPT_CHUNK elements, float4
+ * where all pointers of a tensor are 16-byte aligned and single floats otherwise with the same arithmetic, every float32 operation
+ * rounded once, no atomics, results independent of the grid and of alignment.
+ *
+ * srcnn_grad_norm_guarded: out is THREE device floats.
+ *     x      = g * grad_scale                                   (one rounding per element, before the square)
+ *     out[0] = sqrt(sum over every listed element of x * x)     srcnn_grad_norm's two stages in srcnn_grad_norm's order
+ *     out[1] = clip_norm / max(out[0], clip_norm)               (1 where clip_norm is +infinity: "do not clip")
+ *     out[2] = out[0] is finite ? 1.0f : 0.0f
+ * With grad_scale == 1.0f, out[0] and out[1] carry srcnn_grad_norm's bits.  The squares and the per-chunk sums are float32, and
+ * a float32 sum of squares is finite exactly when every term is finite and the sum did not overflow: out[2] is 0 for an Inf or a
+ * NaN anywhere in the list AND for finite gradients whose squares (or a chunk's sum of them) overflow float32.  Such a step has no
+ * usable norm, so it counts as a bad step too.  clip_norm: > 0, finite or +infinity.  workspace:
+ * srcnn_grad_norm_workspace_bytes(n_tensors, numel_host) bytes.
+ *
+ * srcnn_sgd_step_guarded: ok is a device float, e.g. out + 2 of srcnn_grad_norm_guarded on the same stream; every workgroup loads
+ * it once (a uniform value: no branch depends on a gradient's data).
+ *   *ok != 0:  per element, in this order, every operation rounded once
+ *                  g' = g * grad_scale
+ *                  then srcnn_sgd_step's sequence on g' (d = clipped[i] && coef ? g' * *coef : g'; the weight decay; the momentum
+ *                  buffer; p = p - lr[i] * m).
+ *              With grad_scale == 1.0f, p and m carry srcnn_sgd_step's bits.
+ *   *ok == 0:  no gradient is read and p is not written.  With first_step == 0, m is not written either.  With first_step != 0
+ *              (the buffers are uninitialised), m is written as zeros: the next step, which is no first step any more, then
+ *              computes momentum * 0 + d = d, which is what a first step would have stored (to the bit, but that a d of -0
+ *              is stored as +0), so a freshly allocated buffer never keeps what the allocator left in it and the skipped step
+ *              leaves no trace in the arithmetic.
+ *   skipped:   NULL, or a device unsigned that counts the skipped steps: on a bad step one thread of the call's FIRST launch adds
+ *              one with a plain load and store (a list longer than one launch still counts once; a list without elements
+ *              launches nothing and counts nothing).  Do not share it between streams that run concurrently.
+ * coef: NULL or a device float (out + 1).  clipped_host: NULL = every tensor is clipped.  Tensors must not overlap.
+ *
+ * Errors (SRCNN_ERR_ARG / SRCNN_ERR_WORKSPACE, before any launch): those of srcnn_grad_norm / srcnn_sgd_step; a grad_scale that
+ * is not finite or <= 0; a clip_norm that is <= 0 or NaN; a null or misaligned ok; a misaligned skipped. */
+SRCNN_API int srcnn_grad_norm_guarded(const float *const *g_host, const long long *numel_host, int n_tensors, float clip_norm,
+                                      float grad_scale, float *out, void *workspace, size_t workspace_bytes, srcnn_stream_t stream);
+SRCNN_API int srcnn_sgd_step_guarded(float *const *p_host, const float *const *g_host, float *const *m_host, const long long *numel_host,
+                                     const float *lr_host, const float *weight_decay_host, const int *clipped_host, int n_tensors,
+                                     float momentum, int first_step, float grad_scale, const float *coef, const float *ok,
+                                     unsigned *skipped, srcnn_stream_t stream);
 
 /* ------------------------------------------------------------------ weight preparation
  * What engine.prep_conv / prep_conv_shortcut / prep_stem / prep_deconv2x2 / prep_linear_stack, ConvW.split_f16x3 and

@@ -12,11 +12,6 @@ Nothing of the header is written a second time here: at import `parse_header` re
 Type rule: scalars by C type; a pointer to a declared struct is POINTER(Struct); srcnn_stream_t and every other pointer is
 c_void_p (device memory: callers pass data_ptr()); a non-struct pointer that the HOST reads or writes is POINTER(pointee) --
 the arguments the header names *_host, and those `_HOST_ARRAYS` lists.  What the parser does not understand raises with its text.
-
-EXTENSIONS: further headers of include/ that declare entries of the same library on top of srcnn_hip.h's types (they #include it).
-Each is parsed the same way with srcnn_hip.h's structures and handle types known; its constants and structures become attributes
-of this module like the main header's, and its signatures are bound by lib() with them.  HEADER, _SIGNATURES and
-declared_symbols() stay what srcnn_hip.h alone declares; extension_symbols(header) lists what one extension header adds.
 """
 import collections
 import ctypes
@@ -88,14 +83,13 @@ def _ctype(ctype, depth, host, where):
     return ctype
 
 
-def parse_header(text, host_arrays=None, known=None):
+def parse_header(text, host_arrays=None):
     """What a header text declares -> Header(constants {NAME: int}, SRCNN_ stripped; structs {C name: ctypes.Structure};
-    signatures {name: (restype, [argtypes])}).  host_arrays: {function: arguments typed as host arrays without a _host suffix}.
-    known: {type name: (ctype or None, pointer levels)} the text may use without declaring (an extension header's base header)."""
+    signatures {name: (restype, [argtypes])}).  host_arrays: {function: arguments typed as host arrays without a _host suffix}."""
     host_arrays = {k: list(v) for k, v in (host_arrays or {}).items()}
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants, structs, signatures = {}, collections.OrderedDict(), collections.OrderedDict()
-    types = dict(_BASE_TYPES, **(known or {}))
+    types = dict(_BASE_TYPES)
 
     def fresh(name, where):
         if name in constants or name in types or name in signatures:
@@ -170,41 +164,11 @@ globals().update(HEADER.constants)                                      # FMT_F3
 globals().update((s.__name__, s) for s in HEADER.structs.values())      # ConvDesc, ConvBwdDesc, KittiSplit, PrepLayer, ...
 _SIGNATURES = HEADER.signatures
 
-EXTENSIONS = ("srcnn_train_weights.h", "srcnn_train_fold.h", "srcnn_optim_guard.h")        # include/: headers on top of srcnn_hip.h (the module docstring)
-
-
-def _read_extensions():
-    known = {"srcnn_stream_t": (None, 1)}
-    known.update((cname, (cls, 0)) for cname, cls in HEADER.structs.items())
-    out = collections.OrderedDict()
-    for name in EXTENSIONS:
-        path = os.path.join(os.path.dirname(HEADER_PATH), name)
-        if not os.path.exists(path):
-            raise RuntimeError("include/%s not found at %s: the ctypes binding is derived from it" % (name, path))
-        with open(path) as f:
-            h = out[name] = parse_header(f.read(), known=known)
-        clash = (set(h.constants) & set(HEADER.constants)) | (set(h.signatures) & set(_SIGNATURES))
-        if clash:
-            raise ValueError("include/%s declares again: %s" % (name, ", ".join(sorted(clash))))
-    return out
-
-
-EXTENSION_HEADERS = _read_extensions()
-_EXTENSION_SIGNATURES = collections.OrderedDict((k, v) for h in EXTENSION_HEADERS.values() for k, v in h.signatures.items())
-for _h in EXTENSION_HEADERS.values():
-    globals().update(_h.constants)
-    globals().update((s.__name__, s) for s in _h.structs.values())                  # TrainWeightDesc, TrainFoldDesc
-
 _lib = None
 
 
 def declared_symbols():
     return sorted(_SIGNATURES)
-
-
-def extension_symbols(header=EXTENSIONS[0]):
-    """The entries ONE extension header declares (default: the first extension, srcnn_train_weights.h)."""
-    return sorted(EXTENSION_HEADERS[header].signatures)
 
 
 def lib():
@@ -218,7 +182,7 @@ def lib():
         from . import streams
         streams.hip_may_start()            # the hardware-queue count HIP will start with is decided no later than here
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_EXTENSION_SIGNATURES.items()):
+        for name, (res, args) in _SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -39,7 +39,7 @@ whoever steps prepares again (stereo_rcnn_amd.training.TrainWeights).
 
 fold_all.  fold_conv / fold_linear / fold_deconv2x2 are torch operators per layer (a float64 fold, a permute().contiguous(), a
 torch.cat) with their autograd nodes.  fold_all(specs) is the same for a whole list of layers as ONE node over two library calls
-(csrc/train_fold.hip: the fold and its adjoint, include/srcnn_train_fold.h), with the same bits in both directions;
+(csrc/train_fold.hip: the fold and its adjoint, include/srcnn_hip.h), with the same bits in both directions;
 TrainWeights.prepare(device_fold=True) uses it.
 """
 import collections

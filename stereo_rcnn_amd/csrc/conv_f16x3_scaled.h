@@ -5,7 +5,6 @@
 // backward round alike.  include/srcnn_hip.h states the scheme.
 #pragma once
 #include "conv_tile_4w.h"
-#include "../../include/srcnn_train_weights.h"
 #include <cstdint>
 
 namespace srcnn {

@@ -25,14 +25,12 @@
 //   stage 2  one workgroup, float64: thread t adds workspace[t], workspace[t + 256], .. in that order starting from 0, the same
 //            butterfly and four-term sum in double; thread 0 writes (float)sqrt(sum) and the coefficient.
 //
-// srcnn_grad_norm_guarded / srcnn_sgd_step_guarded (include/srcnn_optim_guard.h) are the same two passes over gradients that
+// srcnn_grad_norm_guarded / srcnn_sgd_step_guarded (include/srcnn_hip.h, "skipped when not finite") are the same two passes over gradients that
 // several backward passes summed: every gradient enters as g * grad_scale, the norm leaves a third word (1 where it is finite), and
 // the update runs only under that word, so one Inf or NaN in a gradient costs one step and not the run.  They are the same code:
 // grad_norm_partial_kernel<SCALED> and sgd_step_kernel<GUARDED> hold the one statement of the summation and of the update, and
 // the plain instantiations compile without the multiplication, the word and the branch.
 #include "layer_list.h"
-
-#include "../../include/srcnn_optim_guard.h"
 
 #include <climits>
 #include <cmath>

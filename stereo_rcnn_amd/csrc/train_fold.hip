@@ -1,5 +1,5 @@
 // Training: the frozen-BN fold and the re-layout of EVERY layer's weight on the device, and its adjoint, each in a fixed number of
-// launches (include/srcnn_train_fold.h states the contract).  What stereo_rcnn_amd.autograd's fold_conv / fold_linear /
+// launches (include/srcnn_hip.h states the contract).  What stereo_rcnn_amd.autograd's fold_conv / fold_linear /
 // fold_deconv2x2 + .contiguous() + torch.cat do per layer with eager operators, and what torch autograd does on the way back
 // through them.  The float64 fold is bn_fold.h's, which csrc/prep_weights.hip calls too (one rounding per operation, contraction
 // off), so the results carry the eager path's bits.
@@ -21,8 +21,6 @@
 // The rows' biases are written by the units of the first channel chunk.
 #include "bn_fold.h"
 #include "layer_list.h"
-
-#include "../../include/srcnn_train_fold.h"
 
 namespace srcnn {
 

@@ -1,5 +1,5 @@
 // 3 x f16 training: max|w| and the hi / lo planes of EVERY layer's weight, once per optimiser step, in a fixed number of launches
-// (include/srcnn_train_weights.h states the contract).  What srcnn_conv2d_forward_f16x3 (f16x3_clear_scales,
+// (include/srcnn_hip.h states the contract).  What srcnn_conv2d_forward_f16x3 (f16x3_clear_scales,
 // absmax_kernel over w, fwd_weight_split) and srcnn_conv2d_backward_f16x3 (the clear, absmax_kernel over the same w,
 // bwd_weight_relayout_split) do per call and per direction is a function of the weights alone; the *_prepared entries of
 // conv_forward_f16x3.hip / conv_backward_f16x3.hip read the results instead.  pow2_scale and split_f16 are conv_f16x3_scaled.h's, so

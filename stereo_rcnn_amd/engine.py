@@ -916,7 +916,7 @@ def _fold_descs(specs):
 
 def fold_train_weights(specs, workspace=None):
     """Every layer's folded weight in the engine's layout and its folded bias in ONE srcnn_train_weights_fold call
-    (csrc/train_fold.hip, include/srcnn_train_fold.h): what autograd.fold_conv / fold_linear / fold_deconv2x2 + .contiguous() (and
+    (csrc/train_fold.hip, include/srcnn_hip.h): what autograd.fold_conv / fold_linear / fold_deconv2x2 + .contiguous() (and
     torch.cat for several parts) compute, bit for bit, in a fixed number of launches.  specs: FoldSpec's.  Returns [(w, b or None)],
     fresh tensors without a graph (autograd.fold_all is the differentiable form).  workspace: prepare_train_weights's, of
     srcnn_train_fold_workspace_bytes(len(specs)) bytes."""
@@ -939,7 +939,7 @@ def fold_train_weights_backward(specs, dws, dbs, workspace=None):
     folded weight / bias (contiguous float32, the folded tensor's shape) or None.  Returns per layer ([dw of each part], [db of each
     part]) in the parameters' own shapes, contiguous; None where nothing arrived (a None dw: every part's weight; a None db, or a layer
     without a convolution bias: every part's bias -- a frozen BN's tensors receive nothing).  A deconvolution's db is refused: its
-    bias stays the caller's bias.repeat(4) (include/srcnn_train_fold.h)."""
+    bias stays the caller's bias.repeat(4) (include/srcnn_hip.h, "frozen-BN fold")."""
     L = _lib.lib()
     specs, descs = _fold_descs(specs)
     dws, dbs = list(dws), list(dbs)

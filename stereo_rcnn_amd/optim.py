@@ -60,7 +60,7 @@ def grad_norm(grads, clip_norm):
 
 def grad_norm_guarded(grads, clip_norm, grad_scale=1.0):
     """(3,) float32 device tensor {L2 norm of grad_scale * g over `grads`, clip_norm / max(norm, clip_norm), 1 where the norm is
-    finite else 0} (include/srcnn_optim_guard.h).  clip_norm float('inf'): the coefficient is 1."""
+    finite else 0} (include/srcnn_hip.h).  clip_norm float('inf'): the coefficient is 1."""
     return _norm("srcnn_grad_norm_guarded", grads, 3, float(clip_norm), float(grad_scale))
 
 
@@ -81,7 +81,7 @@ class SGD(torch.optim.Optimizer):
     clip_norm / max(norm, clip_norm); the other parameters (the reference's `uncert`) use their gradient as it is.  The
     (norm, coefficient) pair stays on the device as `self.last_norm`.
 
-    step(..., guard=True, grad_scale=s) (keywords; include/srcnn_optim_guard.h): every gradient enters as g * s (s = 1 / N after N
+    step(..., guard=True, grad_scale=s) (keywords; include/srcnn_hip.h, "skipped when not finite"): every gradient enters as g * s (s = 1 / N after N
     backward passes have summed into .grad), and the whole update -- the unclipped parameters' too -- runs only where the norm of
     the scaled gradients is finite: on an Inf, a NaN or an overflowing norm no parameter and no momentum buffer changes (a buffer
     created by that very step becomes zeros, which makes the next step the first one) and `self.skipped_steps`, a one-element

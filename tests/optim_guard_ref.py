@@ -1,4 +1,4 @@
-"""numpy restatements of the guarded optimiser pair (include/srcnn_optim_guard.h), float32 with every operation rounded once and
+"""numpy restatements of the guarded optimiser pair (include/srcnn_hip.h), float32 with every operation rounded once and
 in the kernels' order -- what srcnn_grad_norm_guarded and srcnn_sgd_step_guarded are compared with BIT FOR BIT:
   * grad_norm_guarded_f32: (norm, coefficient, ok) of a list of gradients, the two summation stages of optim_ref.grad_norm_f32
     on g * grad_scale;

@@ -38,10 +38,12 @@ def test_structure_layout_is_the_c_compilers(tmp_path):
         want[(cname, '-')] = (ctypes.sizeof(cls), 0)
         for field, _ in cls._fields_:
             want[(cname, field)] = (getattr(cls, field).offset, getattr(cls, field).size)
-    assert len(_lib.HEADER.structs) == 10 and len(want) == 10 + 192
+    assert len(_lib.HEADER.structs) == 12 and len(want) == 12 + 219
     assert got == want, sorted(set(got.items()) ^ set(want.items()))
     assert want[('srcnn_conv_desc', '-')] == (288, 0) and want[('srcnn_conv_desc', 'up_W')] == (280, 4)
     assert want[('srcnn_prep_layer', '-')] == (200, 0)
+    assert want[('srcnn_train_weight_desc', '-')] == (6 * 8 + 4 * 4, 0)             # six pointers, four ints
+    assert want[('srcnn_train_fold_desc', '-')] == ((4 * 3 + 6) * 8 + (3 + 6) * 4 + 4, 0) == (184, 0)   # 18 pointers, 9 ints, tail padding
 
 
 # ---------------------------------------------------------------------------------------------- the parser on pinned text
@@ -170,11 +172,11 @@ def _declarations():
 
 def test_the_real_header_follows_the_convention():
     decls = _declarations()
-    assert sorted(decls) == _lib.declared_symbols() and len(decls) == 111
+    assert sorted(decls) == _lib.declared_symbols() and len(decls) == 120
     structs = _lib.HEADER.structs
     assert [s.__name__ for s in structs.values()] == [
-        'ConvDesc', 'ConvBwdDesc', 'ConvFwdF16x3Desc', 'AnchorTargetParams', 'ProposalTargetParams', 'PrepLayer', 'GtSlot',
-        'TrainImage', 'KittiSplit', 'KittiMatchDesc']
+        'ConvDesc', 'ConvBwdDesc', 'ConvFwdF16x3Desc', 'TrainWeightDesc', 'TrainFoldDesc', 'AnchorTargetParams',
+        'ProposalTargetParams', 'PrepLayer', 'GtSlot', 'TrainImage', 'KittiSplit', 'KittiMatchDesc']
     assert all(getattr(_lib, s.__name__) is s for s in structs.values())
     scalars = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'float': ctypes.c_float,
                'double': ctypes.c_double, 'size_t': ctypes.c_size_t}
@@ -199,14 +201,14 @@ def test_the_real_header_follows_the_convention():
                     listed.add((fn, name))
             else:
                 assert t is ctypes.c_void_p, (fn, text)
-    assert listed == table and host == 22      # exactly the table's entries are typed without the suffix
+    assert listed == table and host == 33      # exactly the table's entries are typed without the suffix
 
 
 def test_every_integer_macro_is_an_attribute():
     text = open(HEADER).read()
     macros = re.findall(r'^#define[ \t]+(\w+)(?:[ \t]+(\S.*?))?[ \t]*$', text, re.M)
     ints = {n[len('SRCNN_'):]: int(v.strip('()')) for n, v in macros if re.fullmatch(r'\(-?\d+\)|-?\d+', v)}
-    assert len(ints) == 34 and len(macros) == 36 and ints == _lib.HEADER.constants
+    assert len(ints) == 38 and len(macros) == 40 and ints == _lib.HEADER.constants
     for name, v in ints.items():
         assert getattr(_lib, name) == v and type(getattr(_lib, name)) is int
     assert not hasattr(_lib, 'API') and not hasattr(_lib, 'HIP_H')

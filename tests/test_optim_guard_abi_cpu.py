@@ -1,8 +1,9 @@
-"""CPU: the C ABI of the guarded optimiser pair as the header-derived binding sees it (include/srcnn_optim_guard.h ->
-stereo_rcnn_amd._lib): the header is an extension beside the other two, its two entries bind, every refusal comes before the first
-launch (so it is checkable without a GPU -- the pattern of tests/test_optim_abi_cpu.py), and the Python keywords that reach it
-(SGD.step's guard / grad_scale, train_step's accum_steps / guard) refuse what they must."""
+"""CPU: the C ABI of the guarded optimiser pair as the header-derived binding sees it (include/srcnn_hip.h, "optimiser step over
+accumulated gradients, skipped when not finite" -> stereo_rcnn_amd._lib): the one header declares its two entries, they bind,
+every refusal comes before the first launch (so it is checkable without a GPU -- the pattern of tests/test_optim_abi_cpu.py), and
+the Python keywords that reach it (SGD.step's guard / grad_scale, train_step's accum_steps / guard) refuse what they must."""
 import ctypes
+import glob
 import inspect
 import os
 
@@ -10,7 +11,6 @@ import pytest
 
 from stereo_rcnn_amd import _lib
 
-HEADER = 'srcnn_optim_guard.h'
 NEW = ['srcnn_grad_norm_guarded', 'srcnn_sgd_step_guarded']
 P = 4096            # a non-null, 16-byte aligned "device pointer" (never dereferenced: every call below is refused first)
 BIG = 1 << 40
@@ -18,25 +18,23 @@ INF = float('inf')
 NAN = float('nan')
 
 
-def test_header_parses_and_is_bound_beside_the_others():
-    assert _lib.EXTENSIONS == ('srcnn_train_weights.h', 'srcnn_train_fold.h', HEADER)
-    assert _lib.extension_symbols(HEADER) == NEW and not set(NEW) & set(_lib.declared_symbols())
-    assert not _lib.EXTENSION_HEADERS[HEADER].structs and not _lib.EXTENSION_HEADERS[HEADER].constants
-    text = open(os.path.join(os.path.dirname(_lib.HEADER_PATH), HEADER)).read()
-    assert '#include "srcnn_hip.h"' in text
-    # the arithmetic is stated as srcnn_hip.h states srcnn_sgd_step's
+def test_the_entries_are_declared_by_the_one_header():
+    assert set(NEW) <= set(_lib.declared_symbols())
+    assert [os.path.basename(p) for p in glob.glob(os.path.join(os.path.dirname(_lib.HEADER_PATH), '*.h'))] == ['srcnn_hip.h']
+    text = open(_lib.HEADER_PATH).read()
+    # the arithmetic is stated as the header states srcnn_sgd_step's
     for phrase in ("g' = g * grad_scale", 'out[2] = out[0] is finite', 'momentum * 0 + d', 'overflow'):
         assert phrase in text, phrase
 
 
 def test_signatures():
-    S = _lib._EXTENSION_SIGNATURES
+    S = _lib._SIGNATURES
     I, F, V, Z = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
     hp, hl, hf, hi = ctypes.POINTER(V), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(F), ctypes.POINTER(I)
     assert S['srcnn_grad_norm_guarded'] == (I, [hp, hl, I, F, F, V, V, Z, V])
     assert S['srcnn_sgd_step_guarded'] == (I, [hp, hp, hp, hl, hf, hf, hi, I, F, I, F, V, V, V, V])
     # the plain pair's arguments in the plain pair's order, the new ones put in: grad_scale; grad_scale, ok, skipped
-    plain_norm, plain_step = _lib._SIGNATURES['srcnn_grad_norm'][1], _lib._SIGNATURES['srcnn_sgd_step'][1]
+    plain_norm, plain_step = S['srcnn_grad_norm'][1], S['srcnn_sgd_step'][1]
     assert S['srcnn_grad_norm_guarded'][1] == plain_norm[:4] + [F] + plain_norm[4:]
     assert S['srcnn_sgd_step_guarded'][1] == plain_step[:10] + [F] + plain_step[10:11] + [V, V] + plain_step[11:]
 
@@ -71,7 +69,7 @@ def _i(*v):
 
 def test_symbols_resolve(L):
     for name in NEW:
-        assert getattr(L, name).argtypes == _lib._EXTENSION_SIGNATURES[name][1]
+        assert getattr(L, name).argtypes == _lib._SIGNATURES[name][1]
 
 
 def test_grad_norm_guarded_refusals(L):

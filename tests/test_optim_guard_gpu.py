@@ -1,4 +1,4 @@
-"""GPU: the guarded optimiser pair -- srcnn_grad_norm_guarded + srcnn_sgd_step_guarded (include/srcnn_optim_guard.h) and
+"""GPU: the guarded optimiser pair -- srcnn_grad_norm_guarded + srcnn_sgd_step_guarded (include/srcnn_hip.h) and
 optim.SGD.step(guard=..., grad_scale=...) -- against the plain pair on copies and against the float32 restatement of
 tests/optim_guard_ref.py.  EVERY comparison is equality of bits; there is no tolerance in this file.
 

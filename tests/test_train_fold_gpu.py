@@ -1,4 +1,4 @@
-"""GPU: srcnn_train_weights_fold / srcnn_train_weights_fold_backward (csrc/train_fold.hip, include/srcnn_train_fold.h) and
+"""GPU: srcnn_train_weights_fold / srcnn_train_weights_fold_backward (csrc/train_fold.hip, include/srcnn_hip.h) and
 autograd.fold_all over them, against the eager folds they replace -- autograd.fold_conv / fold_linear / fold_deconv2x2 +
 .contiguous() (torch.cat for several parts) and torch autograd through them -- on the same device.  Every comparison is on int32
 bit views.  ONE list crosses the table search, the unit edges (rows and channels that do not fill a unit, several channel chunks

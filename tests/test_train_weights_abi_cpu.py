@@ -1,9 +1,9 @@
-"""CPU: the C ABI of the once-per-step weight preparation as the header-derived binding sees it (include/srcnn_train_weights.h ->
-stereo_rcnn_amd._lib): the descriptor's documented field order, the four new entries' signatures, the workspace query's growth."""
+"""CPU: the C ABI of the once-per-step weight preparation as the header-derived binding sees it (include/srcnn_hip.h, "weights
+prepared once per step" -> stereo_rcnn_amd._lib): the descriptor's documented field order, the four entries' signatures, the
+workspace query's growth.  The descriptor's layout against the C compiler's is tests/test_abi_header_cpu.py's, with every structure."""
 import ctypes
+import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
@@ -19,24 +19,8 @@ def test_descriptor_field_order():
     assert ctypes.sizeof(_lib.TrainWeightDesc) == 6 * 8 + 4 * 4
 
 
-def test_descriptor_layout_is_the_c_compilers(tmp_path):
-    cc = shutil.which('cc')
-    assert cc, 'no host C compiler (cc) on PATH: the layout cannot be checked'
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "srcnn_train_weights.h"', 'int main(void) {',
-             '    printf("- %zu 0\\n", sizeof(srcnn_train_weight_desc));']
-    lines += ['    printf("%s %%zu %%zu\\n", offsetof(srcnn_train_weight_desc, %s), sizeof(((srcnn_train_weight_desc *)0)->%s));' % (f, f, f)
-              for f in FIELDS]
-    src, exe = tmp_path / 'layout.c', tmp_path / 'layout'
-    src.write_text('\n'.join(lines + ['    return 0;', '}', '']))
-    subprocess.check_call([cc, '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(_lib.HEADER_PATH), str(src), '-o', str(exe)])
-    got = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in subprocess.check_output([str(exe)]).decode().split('\n') if ln}
-    want = {f: (getattr(_lib.TrainWeightDesc, f).offset, getattr(_lib.TrainWeightDesc, f).size) for f in FIELDS}
-    want['-'] = (ctypes.sizeof(_lib.TrainWeightDesc), 0)
-    assert got == want
-
-
 def test_signatures():
-    S = dict(_lib._SIGNATURES, **_lib._EXTENSION_SIGNATURES)
+    S = _lib._SIGNATURES
     desc = ctypes.POINTER(_lib.TrainWeightDesc)
     assert S['srcnn_train_weights_workspace_bytes'] == (Z, [I])
     assert S['srcnn_train_weights_prepare'] == (I, [desc, I, P, Z, P])
@@ -48,15 +32,15 @@ def test_signatures():
     assert S['srcnn_conv2d_backward_f16x3_prepared'][1][:2] == S['srcnn_conv2d_backward_f16x3_maxima'][1][:2]
 
 
-def test_the_extension_header_is_bound_beside_the_main_one():
+def test_the_entries_are_declared_by_the_one_header():
     new = ['srcnn_conv2d_backward_f16x3_prepared', 'srcnn_conv2d_forward_f16x3_prepared', 'srcnn_train_weights_prepare',
            'srcnn_train_weights_workspace_bytes']
-    assert _lib.extension_symbols() == new and not set(new) & set(_lib.declared_symbols())
-    assert list(_lib.EXTENSION_HEADERS['srcnn_train_weights.h'].structs) == ['srcnn_train_weight_desc']
-    assert 'srcnn_train_weight_desc' not in _lib.HEADER.structs
+    assert set(new) <= set(_lib.declared_symbols())
+    assert _lib.HEADER.structs['srcnn_train_weight_desc'] is _lib.TrainWeightDesc
+    assert [os.path.basename(p) for p in glob.glob(os.path.join(os.path.dirname(_lib.HEADER_PATH), '*.h'))] == ['srcnn_hip.h']
 
 
-RECORD, PER_BLOCK = 80, 48          # include/srcnn_train_weights.h: bytes of one table record, layers of one kernel-argument block
+RECORD, PER_BLOCK = 80, 48          # include/srcnn_hip.h: bytes of one table record, layers of one kernel-argument block
 
 
 def test_a_block_of_records_fits_the_argument_block():

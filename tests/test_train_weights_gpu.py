@@ -1,5 +1,5 @@
 """GPU: the f16x3 weights of a whole list of layers from one call (srcnn_train_weights_prepare, csrc/train_weights.hip) and the two
-entries that read them (srcnn_conv2d_forward_f16x3_prepared, srcnn_conv2d_backward_f16x3_prepared; include/srcnn_train_weights.h).
+entries that read them (srcnn_conv2d_forward_f16x3_prepared, srcnn_conv2d_backward_f16x3_prepared; include/srcnn_hip.h).
 
 max |w| and the split are functions of the weights alone, so every comparison is a bit-equality: the words against engine.absmax,
 the planes against a torch restatement of pow2_scale / split_f16 (s from the word, hi = f16(w s), lo = f16(w s - hi), the forward
@@ -79,7 +79,7 @@ def test_list_of_one(m, weights, index):
 
 
 def test_more_layers_than_one_argument_block(m, weights, dev):
-    n = 48 + 3                  # include/srcnn_train_weights.h: 48 layers travel in one kernel-argument block
+    n = 48 + 3                  # include/srcnn_hip.h: 48 layers travel in one kernel-argument block
     g = torch.Generator().manual_seed(9)
     ws = [(torch.randn(8 + i, 1, 1, 32, generator=g) * (1 + i)).to(dev) for i in range(n)]
     _check(m, ws, m.prepare_train_weights(ws))

@@ -3,7 +3,7 @@
     python tools/optim_guard_bench.py [--out profiles/optim_guard_bench.txt] [--reps 40]
 
   * plain   : stereo_rcnn_amd.optim.SGD.step(clip_norm=10.) -- srcnn_grad_norm + srcnn_sgd_step;
-  * guarded : the same call with guard=True -- srcnn_grad_norm_guarded + srcnn_sgd_step_guarded (include/srcnn_optim_guard.h): one
+  * guarded : the same call with guard=True -- srcnn_grad_norm_guarded + srcnn_sgd_step_guarded (include/srcnn_hip.h): one
     more multiplication per gradient element in each pass, a third word from the norm, the update under that word;
   * accum 1/2 : guard=True, grad_scale=0.5 (the call that ends two accumulated micro-batches): the same kernels, another scale.
 Both move 24 bytes per element (norm: read g 4; step: read p, g, m, write p, m 20); the guarded pair adds three words.
